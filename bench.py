@@ -14,8 +14,12 @@ chunk on RCCL (``zk_allgather_rows`` inside libzernike_hip.so -- no torch.distri
 chunk's kernel runs.  `value` is that whole-job throughput; the sharded-kernel-only figure is reported
 beside it (``kernel_only_patches_per_s``, ``allgather``).
 
-Rank 0 prints ONE JSON line.  Besides the contract keys it carries
-  roofline       -- the batch kernel: algorithmic bytes / HIP-event kernel time vs the 8 TB/s HBM peak
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and prints the contract keys with
+  roofline       -- the batch kernel: algorithmic bytes / HIP-event kernel time of the timed steps vs the 8 TB/s HBM peak
+  allgather      -- N > 1: the timed loops with and without the exchange, and the gathered matrix verified
+--dump-outputs DIR also writes what the last timed step computed (DIR/moments.npy: a seeded sample of its rows).
+Every other measurement runs only with --full (each still has its --no-* switch):
+  roofline.this_box, allgather.ms_alone / transport -- this box's bare stream rates, the exchange on its own
   cpu_baseline   -- the oracle's restatement of the reference CPU path (same NumPy call) on this host
   north_star_4096, config2_batch, config2_dense, config3_per_gpu, dense_frame, symmetry_pipeline -- the other
                     BASELINE configs as far as one GPU carries them, each with its own roofline object (N = 1)
@@ -49,6 +53,13 @@ def parse():
                     help="N>1: chunks a rank's block is cut into (kernel of chunk c+1 overlaps the transfer of chunk c)")
     ap.add_argument("--kernel-only-value", action="store_true",
                     help="N>1: take `value` from the loop WITHOUT the all-gather (default: with it)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every side measurement (CPU baselines, the other BASELINE configs, "
+                         "per-kernel rooflines, this box's stream rates, the consumers, N>1: configs[3] / [4] and the "
+                         "all-gather alone); a plain run times the steps and prints the line, nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/*.npy (a fixed, seeded sample of "
+                         "rows of the float64 moment matrix, at most 48 MiB, and the float64 indices of those rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dense", action="store_true", help="skip the dense-frame side measurement")
     ap.add_argument("--no-maps", action="store_true", help="skip the configs[4] symmetry-map measurement")
@@ -59,7 +70,7 @@ def parse():
     ap.add_argument("--no-high-order", action="store_true", help="skip the matrix-core plain sum at (40 px, n_max 20)")
     ap.add_argument("--no-host-api", action="store_true", help="skip the NumPy-in / NumPy-out measurement")
     ap.add_argument("--no-multi-frame", action="store_true", help="N>1: skip configs[3] (8 frames per rank)")
-    ap.add_argument("--only-timed-loop", action="store_true", help="skip every side measurement (profiling runs)")
+    ap.add_argument("--only-timed-loop", action="store_true", help="skip every side measurement, also under --full (profiling runs)")
     ap.add_argument("--no-clustering", action="store_true", help="skip the k-means consumer on the resident moment matrix")
     return ap.parse_args()
 
@@ -302,6 +313,26 @@ def _kernel_source_hash():
     return h.hexdigest()[:16]
 
 
+DUMP_BYTES = 48 << 20
+
+
+def dump_outputs(path, moments):
+    """--dump-outputs: the (N, N_poly) float64 moment matrix the timed step wrote, as a caller of the path receives it --
+    all of it if it fits DUMP_BYTES, else a fixed sample of rows (seed 0, ascending) -- and the indices of those rows."""
+    import numpy as np
+    import torch
+    n, n_poly = moments.shape
+    torch.cuda.synchronize()
+    n_rows = min(n, DUMP_BYTES // (8 * (n_poly + 1)))
+    rows = np.arange(n) if n_rows == n else np.sort(np.random.default_rng(0).choice(n, size=n_rows, replace=False))
+    idx = torch.from_numpy(rows).to(moments.device)
+    sample = moments.index_select(0, idx).to(torch.float64).cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "moments.npy"), sample)
+    np.save(os.path.join(path, "moment_rows.npy"), rows.astype(np.float64))
+    print(f"[bench] wrote {path}/moments.npy {sample.shape} (rows {n_rows} of {n}) and moment_rows.npy", file=sys.stderr)
+
+
 # ---------------------------------------------------------------------------------------------------------
 def worker(args):
     import numpy as np
@@ -334,10 +365,11 @@ def worker(args):
         # the one-GPU rehearsal under an outside launcher (python -m torch.distributed.run ... bench.py --gpus N, the driver's
         # form): the launcher did not give the ranks their host ids, so each takes its own before RCCL is initialised
         os.environ.update(D.one_gpu_rank_env(rank, {}))
+    side_runs = args.full and not args.only_timed_loop                  # a plain run: the headline and nothing else
     rccl_log = None
-    if world > 1 and backend == "rccl":
-        # which transport RCCL connects the ranks over goes into the line (allgather.transport): INFO output of its INIT
-        # phase into a file of this rank's own, parsed after the gathers have run
+    if world > 1 and backend == "rccl" and side_runs:
+        # which transport RCCL connects the ranks over goes into the line (allgather.transport, --full): INFO output of
+        # its INIT phase into a file of this rank's own, parsed after the gathers have run
         os.environ.update(D.rccl_debug_env(rank))
         rccl_log = os.environ.get("NCCL_DEBUG_FILE")
     dead = Deadman(rank, world, json_fd, args)
@@ -411,13 +443,18 @@ def worker(args):
         spread = {"min": step_ms[0], "median": step_ms[len(step_ms) // 2], "max": step_ms[-1]} if step_ms else None
         return dt, launches, kernel_ms, spread
 
+    in_step = world > 1 and not args.kernel_only_value
     dead.enter("timed loop (kernels only)", limit)
     el_kernel, l_kernel, ms_kernel, spread_kernel = timed_loop(step_kernel)
+    if args.dump_outputs and not in_step and rank == 0:
+        dump_outputs(args.dump_outputs, mine)                          # what the last timed step wrote, before anything else
     gather = None
     verified = True
     if world > 1:
         dead.enter("timed loop (kernel + all-gather per step)", limit)
         el_gather, l_gather, ms_gather, spread_gather = timed_loop(step_gather)
+        if args.dump_outputs and in_step and rank == 0:
+            dump_outputs(args.dump_outputs, full)
         dead.enter("all-gather verification", limit)
         # verification: my block is what my kernel wrote; every other block carries its owner's checksum
         # (recomputed with the same launches as the timed step: a wave's summation order depends on its index within a
@@ -443,42 +480,43 @@ def worker(args):
         verified = ok
         del check
         fence()
-        dead.enter("all-gather alone (3 passes)", limit)
-        t1 = time.perf_counter()
-        for _ in range(3):
-            comm.allgather_rows(full, 1, n_total, n_poly, n_local, 0, n_local, D._current_stream_ptr(full))
-            comm.join(D._current_stream_ptr(full))
-        fence()
-        alone_ms = comm.max_over_ranks((time.perf_counter() - t1) / 3 * 1e3)
-        # what RCCL connected the ranks over, from every rank's own log (P2P/IPC = xGMI inside a node; NET/Socket in the
-        # one-GPU rehearsal), and how many ranks the communicator holds
-        counts = {}
-        try:
-            if rccl_log:
-                with open(rccl_log.replace("%h", socket.gethostname()).replace("%p", str(os.getpid())), errors="replace") as fh:
-                    counts = D.rccl_transport_summary(fh.read())
-        except OSError:
-            counts = {}
-        blob = json.dumps(counts).encode()
-        blob = (blob if len(blob) <= 256 else b"{}").ljust(256)          # equal-sized payloads on every rank
-        all_counts = [json.loads(b.decode()) for b in comm.allgather_host(blob)]
-        ranks_seen = int(comm.ranks_seen()) if backend == "rccl" else world
-        link_GBps = rl.XGMI_LINKS * rl.XGMI_LINK_GBS
-        received = (world - 1) * n_local * n_poly * 8 / (alone_ms * 1e-3) / 1e9
-        gather = {"verified": ok, "own_block_equals_recomputation": own_ok, "ms_alone": alone_ms, "chunks": args.gather_chunks,
-                  "transport": D.describe_transport(all_counts, rehearsal) if backend == "rccl" else "gloo (rehearsal)",
-                  "transport_channels_per_rank": all_counts, "ranks_seen": ranks_seen,
-                  "xgmi_bound_GBps_per_rank": link_GBps,
-                  "frac_of_xgmi_bound": received / link_GBps,
+        gather = {"verified": ok, "own_block_equals_recomputation": own_ok, "chunks": args.gather_chunks,
+                  "ranks_seen": int(comm.ranks_seen()) if backend == "rccl" else world,
                   "backend": {"rccl": "rccl (zk_allgather_rows in libzernike_hip.so)", "gloo": "gloo (rehearsal)"}.get(backend, backend),
                   "ms_per_step_with_allgather": el_gather / args.steps * 1e3,
                   "value_with_allgather": n_total / (el_gather / args.steps),
                   "ms_per_step_kernel_only": el_kernel / args.steps * 1e3,
                   "value_kernel_only": n_total / (el_kernel / args.steps),
-                  "bytes_per_rank_out": n_local * n_poly * 8, "gathered_bytes": n_total * n_poly * 8,
-                  "GBps_received_per_rank": (world - 1) * n_local * n_poly * 8 / (alone_ms * 1e-3) / 1e9}
+                  "bytes_per_rank_out": n_local * n_poly * 8, "gathered_bytes": n_total * n_poly * 8}
+        if side_runs:
+            dead.enter("all-gather alone (3 passes)", limit)
+            t1 = time.perf_counter()
+            for _ in range(3):
+                comm.allgather_rows(full, 1, n_total, n_poly, n_local, 0, n_local, D._current_stream_ptr(full))
+                comm.join(D._current_stream_ptr(full))
+            fence()
+            alone_ms = comm.max_over_ranks((time.perf_counter() - t1) / 3 * 1e3)
+            # what RCCL connected the ranks over, from every rank's own log (P2P/IPC = xGMI inside a node; NET/Socket in the
+            # one-GPU rehearsal)
+            counts = {}
+            try:
+                if rccl_log:
+                    with open(rccl_log.replace("%h", socket.gethostname()).replace("%p", str(os.getpid())), errors="replace") as fh:
+                        counts = D.rccl_transport_summary(fh.read())
+            except OSError:
+                counts = {}
+            blob = json.dumps(counts).encode()
+            blob = (blob if len(blob) <= 256 else b"{}").ljust(256)          # equal-sized payloads on every rank
+            all_counts = [json.loads(b.decode()) for b in comm.allgather_host(blob)]
+            link_GBps = rl.XGMI_LINKS * rl.XGMI_LINK_GBS
+            received = (world - 1) * n_local * n_poly * 8 / (alone_ms * 1e-3) / 1e9
+            gather.update({"ms_alone": alone_ms,
+                           "transport": D.describe_transport(all_counts, rehearsal) if backend == "rccl" else "gloo (rehearsal)",
+                           "transport_channels_per_rank": all_counts,
+                           "xgmi_bound_GBps_per_rank": link_GBps,
+                           "frac_of_xgmi_bound": received / link_GBps,
+                           "GBps_received_per_rank": received})
 
-    in_step = world > 1 and not args.kernel_only_value
     elapsed, launches, kernel_ms, spread = ((el_gather, l_gather, ms_gather, spread_gather) if in_step
                                             else (el_kernel, l_kernel, ms_kernel, spread_kernel))
 
@@ -512,7 +550,7 @@ def worker(args):
     }
     if gather is not None:
         result["allgather"] = gather
-    if not args.only_timed_loop and world == 1:
+    if side_runs and world == 1:
         # what THIS box sustains on a plain stream over the very buffer the kernel reads (same physical pages), and on a copy
         # into the buffer it writes: a slow box or an unlucky placement shows here, a bad access pattern only in the kernel
         real_bytes = (traffic or n_local * (per_patch - 2 * K * 4))          # PMC traffic, else rows 0 / K-1 not fetched
@@ -553,7 +591,7 @@ def worker(args):
     # others, rank 0 delivers the line it has (Deadman), and the job's exit code is non-zero.  A section that stalls
     # ends the same way through its phase limit.
     side = {}
-    if not args.only_timed_loop and not args.no_clustering:
+    if side_runs and not args.no_clustering:
         dead.enter("side section: clustering", limit)
         try:
             side["clustering"] = clustering_section(comm, world, dev, mine, n_local, n_poly,
@@ -564,7 +602,7 @@ def worker(args):
                 traceback.print_exc()
                 dead.fire(f"clustering section raised {type(exc).__name__}: {exc}", 5)
             side["clustering"] = {"error": f"{type(exc).__name__}: {exc}"}      # one rank: nobody waits for us
-    if world > 1 and not args.only_timed_loop:
+    if world > 1 and side_runs:
         side.update(multi_rank_sections(args, comm, rank, world, dev, plan, z, dead, limit))
         bad = [k for k in ("multi_frame", "sharded_maps") if k in side and not side[k].get("verified", True)]
         if bad:
@@ -580,7 +618,7 @@ def worker(args):
         return
     result.update(side)
 
-    if world == 1 and not args.only_timed_loop:
+    if world == 1 and side_runs:
         del patches, full, mine
         torch.cuda.empty_cache()
         single_gpu_sections(args, result, dev, plan, z, f_dev, frame)

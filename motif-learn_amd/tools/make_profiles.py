@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turn the raw rocprofv3 output of tools/profile_round.sh (gpurun_out/<tag>_*) into the summaries under profiles/:
+"""Turn the raw rocprofv3 output of tools/profile_round.sh (profile_out/<tag>_*) into the summaries under profiles/:
 <tag>_kernel_stats_bench.csv, <tag>_bench_line_under_rocprof.json, <tag>_pmc_hbm.txt (+ profiles/traffic.json),
 <tag>_sq_counters.txt.   python3 motif-learn_amd/tools/make_profiles.py r02"""
 import collections
@@ -12,12 +12,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 TAG = sys.argv[1] if len(sys.argv) > 1 else "r03"
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+G, P = os.path.join(ROOT, "profile_out"), os.path.join(ROOT, "profiles")
 TOOL = os.path.join(ROOT, "motif-learn_amd", "tools", "pmc_summary.py")
 
 rows = list(csv.DictReader(open(os.path.join(G, f"{TAG}_stats", "b_kernel_stats.csv"))))
 with open(os.path.join(P, f"{TAG}_kernel_stats_bench.csv"), "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no-4096 --no-cpu-baseline --no-host-api   (1 x MI355X)\n")
+    f.write("# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --no-4096 --no-cpu-baseline --no-host-api   (1 x MI355X)\n")
     f.write(f"# zk_* kernels only (torch copy / fill kernels of the harness omitted); bench line of the same run: profiles/{TAG}_bench_line_under_rocprof.json\n")
     w = csv.writer(f)
     w.writerow(["Name", "Calls", "TotalDurationNs", "AverageNs", "MinNs", "MaxNs"])

@@ -70,3 +70,15 @@ box:77:90 [0] NCCL INFO Channel 01 : 0[3000] -> 1[3000] via SHM/direct/direct
     assert D.rccl_debug_env(0, base={"NCCL_DEBUG": "INFO", "NCCL_DEBUG_FILE": "/x"}) == {}
     raised = D.rccl_debug_env(0, base={"NCCL_DEBUG": "VERSION", "NCCL_DEBUG_FILE": "/x"})      # below INFO: no channel lines
     assert raised == {"NCCL_DEBUG": "INFO", "NCCL_DEBUG_SUBSYS": "INIT,P2P,NET,SHM"}
+
+
+def test_a_plain_run_has_no_side_measurements_and_full_opts_in(monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` is the headline alone: the side measurements wait for --full, and nothing
+    is written unless --dump-outputs names a directory."""
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert (a.gpus, a.steps, a.warmup) == (1, 7, 2) and not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = b.parse()
+    assert a.full and a.dump_outputs == "out"

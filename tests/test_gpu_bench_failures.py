@@ -43,7 +43,7 @@ def test_no_stand_in_when_the_product_communicator_is_unavailable():
 
 def test_two_rccl_ranks_deliver_a_verified_line():
     # the success path of the same harness: real RCCL between two ranks (a host id per rank), every section verified
-    rc, line, err = _run({"ZK_BENCH_FRAMES_PER_RANK": "2", "ZK_BENCH_MAPS_FRAME": "512"}, "--steps", "3", "--warmup", "1")
+    rc, line, err = _run({"ZK_BENCH_FRAMES_PER_RANK": "2", "ZK_BENCH_MAPS_FRAME": "512"}, "--steps", "3", "--warmup", "1", "--full")
     assert rc == 0, err[-3000:]
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["config"]["allgather_in_step"]
     assert line["allgather"]["verified"] and line["allgather"]["own_block_equals_recomputation"]
