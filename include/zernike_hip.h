@@ -370,6 +370,33 @@ int zk_denoise_fft(int device, const void* image_host, int dtype, int64_t height
 int zk_wavelet_sigma(int device, const void* image_host, int dtype, int64_t height, int64_t width, double* sigma_out);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Key-point detection: the device side of local_max (reference features/_local_max_v2.py), the step ahead of
+ * zk_transform_points.  No plan involved; blocking.
+ *
+ *   candidates   pixels equal to the maximum of their 3 x 3 neighbourhood and > threshold, off the 1-px border
+ *                (skimage.feature.peak_local_max(image, min_distance=1, threshold_abs=threshold)); a constant image has
+ *                none.  has_threshold 0: the threshold is the image's minimum (computed on the device).  Otherwise
+ *                `threshold` is compared with the exact value of every pixel as float64: the caller rounds it the way
+ *                NumPy's comparison would (a Python float against a float32 image: to float32 first).
+ *   suppression  candidates in descending intensity, ties in raster order (row, then column); a kept candidate drops
+ *                every other one at dx^2 + dy^2 <= min_distance^2 (filter_peaks_by_distance; the reference's tie order
+ *                is not stable).
+ *   points       (x, y) = (column, row) of the kept candidates in that order.
+ * dtype: ZK_F32 / ZK_F64 / ZK_U8 / ZK_U16 / ZK_I16 (the narrow formats are widened exactly on the device), C-contiguous
+ * (height, width).  Both calls write min(n, capacity) rows and always report n in n_found: call again with capacity n
+ * when it was short.  zk_local_max_dev writes int32 rows in the layout zk_transform_points_dev reads and runs on
+ * hip_stream (it synchronises it: n crosses to the host).
+ * zk_local_max_last_launches: suppression launches of the calling thread's last call (tools and tests).
+ * ------------------------------------------------------------------------------------------------------ */
+int zk_local_max(int device, const void* image_host, int dtype, int64_t height, int64_t width, double min_distance,
+                 int has_threshold, double threshold, int64_t* points_host /* (cap, 2) x, y */, int64_t capacity,
+                 int64_t* n_found);
+int zk_local_max_dev(int device, const void* image_dev, int dtype, int64_t height, int64_t width, double min_distance,
+                     int has_threshold, double threshold, int32_t* points_dev /* zk_transform_points_dev layout */,
+                     int64_t capacity, int64_t* n_found_host, void* hip_stream);
+int64_t zk_local_max_last_launches(void);
+
+/* ------------------------------------------------------------------------------------------------------
  * First downstream consumer of the moment matrix: the two streaming passes of
  *   pca(X, n_components)   reference features/_dimension_reduction.py:3-6 (sklearn PCA(n).fit_transform(X))
  * on a float64 matrix X (N, D), D <= 127 (45 moments at n_max 8).

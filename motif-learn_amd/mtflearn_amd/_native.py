@@ -100,6 +100,11 @@ SYMBOLS = {
                                  POINTER(c_double), POINTER(c_double)]),
     "zk_denoise_fft": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_double, POINTER(c_double)]),
     "zk_wavelet_sigma": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, POINTER(c_double)]),
+    "zk_local_max": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_double, c_int, c_double, c_void_p, c_int64,
+                             POINTER(c_int64)]),
+    "zk_local_max_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_double, c_int, c_double, c_void_p, c_int64,
+                                 POINTER(c_int64), c_void_p]),
+    "zk_local_max_last_launches": (c_int64, []),
     "zk_gram": (c_int, [c_int, POINTER(c_double), c_int64, c_int, POINTER(c_double), POINTER(c_void_p)]),
     "zk_project": (c_int, [c_int, c_void_p, c_int64, c_int, POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double),
                            c_int]),
@@ -396,6 +401,11 @@ class Plan:
                                             pts.ctypes.data_as(POINTER(c_int32)), pts.shape[0],
                                             out.ctypes.data_as(POINTER(c_double))), "zk_transform_points")
         return out
+
+    def transform_points_dev(self, image_ptr, code, height, width, points_ptr, n_points, out_ptr, stream=0):
+        """``zk_transform_points_dev``: (n_points, 2) int32 (x, y) on the device -> (n_points, n_poly) float64 on the device."""
+        check(self._lib.zk_transform_points_dev(self._h, c_void_p(image_ptr), code, height, width, c_void_p(points_ptr),
+                                                n_points, c_void_p(out_ptr), c_void_p(stream)), "zk_transform_points_dev")
 
     def frame_maps(self, image, n_complex, folds=None, m_unselect=(0, 1), p=2, theta=None, want_abs=True):
         """Fused frame -> (rot_maps, |Z^c|, mirror_map); any of them None when not requested."""

@@ -24,13 +24,14 @@ device pointers.
 from __future__ import annotations
 
 import struct
+from ctypes import byref, c_int64, c_void_p
 
 import numpy as np
 
 from . import _native
 
 __all__ = ["shard_bounds", "one_gpu_rank_env", "RcclComm", "TorchComm", "DeviceCompute", "patch_moments_device",
-           "frame_moments_device", "frame_maps_device", "sharded_patch_moments", "sharded_frame_moments",
+           "frame_moments_device", "frame_maps_device", "local_max_device", "points_moments_device", "sharded_patch_moments", "sharded_frame_moments",
            "sharded_frame_maps", "sharded_frames_moments"]
 
 
@@ -232,6 +233,91 @@ def frame_maps_device(plan: "_native.Plan", image, n_complex, folds=(2, 3, 4, 6)
     plan.frame_maps_dev(image.data_ptr(), code, h, w, row0, n_rows, folds, m_unselect, p, theta,
                         ptr(rot), ptr(ab), ptr(mir), stream)
     return rot, ab, mir
+
+
+def _image_code(image):
+    """ZK_* code of a 2-D device image for ``zk_local_max_dev``: the two float types and the narrow detector formats."""
+    if _is_native(image):
+        code = _native.dtype_code(image.dtype)
+        name = image.dtype
+    else:
+        import torch
+        code = {torch.float32: _native.ZK_F32, torch.float64: _native.ZK_F64, torch.uint8: _native.ZK_U8,
+                torch.int16: _native.ZK_I16, getattr(torch, "uint16", None): _native.ZK_U16}.get(image.dtype)
+        name = image.dtype
+    if code is None:
+        raise TypeError(f"local_max_device takes float32, float64, uint8, uint16 or int16 images, not {name}")
+    return code
+
+
+def _numpy_dtype(image):
+    if _is_native(image):
+        return image.dtype
+    import torch
+    return {torch.float32: np.float32, torch.float64: np.float64, torch.uint8: np.uint8, torch.int16: np.int16,
+            getattr(torch, "uint16", None): np.uint16}[image.dtype]
+
+
+def _empty_points(n, like):
+    if _is_native(like):
+        return _native.DeviceArray((n, 2), np.int32, like.device.index)
+    import torch
+    return torch.empty((n, 2), dtype=torch.int32, device=like.device)
+
+
+def local_max_device(image, min_distance, threshold=None):
+    """:func:`mtflearn_amd.features.local_max` of a frame resident on the GPU (a torch tensor or a
+    :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` of float32 / float64 / uint8 / uint16 / int16).  Returns the
+    ``(N, 2)`` int32 ``(x, y)`` points as a device array of the same kind, in the layout :func:`points_moments_device`
+    reads: the frame never crosses to the host, only the point count does.  Runs on torch's current stream."""
+    from .features.peaks import _check_distance, _comparison_threshold
+    if len(image.shape) != 2:
+        raise ValueError(f"local_max_device needs a 2D image, not {len(image.shape)}-D")
+    if not image.is_cuda:
+        raise ValueError("image must live on the GPU")
+    if not _is_native(image) and not image.is_contiguous():
+        image = image.contiguous()
+    code = _image_code(image)
+    r = _check_distance(min_distance)
+    has_t, t = (0, 0.0) if threshold is None else (1, _comparison_threshold(_numpy_dtype(image), threshold))
+    h, w = (int(v) for v in image.shape)
+    lib = _native.load()
+    stream = c_void_p(_current_stream_ptr(image))
+    capacity = max(1024, h * w // 8)                   # kept points of a real frame: a few % of its pixels
+    out = _empty_points(capacity, image)
+    n = c_int64()
+    for _ in range(2):                                  # the second pass only when the first guess was short
+        _native.check(lib.zk_local_max_dev(image.device.index, c_void_p(image.data_ptr()), code, h, w, r, has_t, t,
+                                           c_void_p(out.data_ptr()), capacity, byref(n), stream), "zk_local_max_dev")
+        if n.value <= capacity:
+            break
+        capacity = n.value
+        out = _empty_points(capacity, image)
+    n = n.value
+    return out[:n]
+
+
+def points_moments_device(plan: "_native.Plan", image, points, out=None):
+    """Moments of the windows centred on device-resident key points (``zk_transform_points_dev``): ``image`` an
+    ``(H, W)`` float32 / float64 frame, ``points`` ``(N, 2)`` int32 ``(x, y)`` (what :func:`local_max_device` returns),
+    both torch tensors or both :class:`~mtflearn_amd._native.DeviceArray`.  Returns the ``(N, n_poly)`` float64 moments
+    on the device -- ``ZPs.transform_at(frame, points)`` with neither the frame nor the points crossing PCIe."""
+    _check_operand(plan, image, "image")
+    _check_operand(plan, points, "points")
+    code = _dtype_code(image)
+    if len(points.shape) != 2 or points.shape[1] != 2 or points.element_size() != 4 or not (
+            points.dtype == np.int32 if _is_native(points) else str(points.dtype) == "torch.int32"):
+        raise TypeError("points must be an (N, 2) int32 array of (x, y)")
+    h, w = image.shape
+    n = int(points.shape[0])
+    if out is None:
+        out = _empty_like((n, plan.n_poly), image)
+    else:
+        _check_operand(plan, out, "out")
+        assert tuple(out.shape) == (n, plan.n_poly) and _is_f64(out)
+    if n:
+        plan.transform_points_dev(image.data_ptr(), code, h, w, points.data_ptr(), n, out.data_ptr(), _current_stream_ptr(image))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------
