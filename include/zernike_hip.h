@@ -397,6 +397,46 @@ int zk_local_max_dev(int device, const void* image_dev, int dtype, int64_t heigh
 int64_t zk_local_max_last_launches(void);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Background removal: the device side of the reference's background/ subpackage, the step ahead of local_max.  No plan
+ * involved.  dtype: ZK_F32 / ZK_F64 / ZK_U8 / ZK_U16 / ZK_I16, C-contiguous (height, width).  Edges follow SciPy's
+ * 'reflect' mode (dcba|abcd), folded again and again when a window or a radius exceeds the frame.
+ *
+ *   opening       scipy.ndimage.grey_opening(image, size=(size_y, size_x)) (background/_morphology.py): a flat minimum
+ *                 filter of window [i - k/2, i - k/2 + k - 1] per axis, then a flat maximum filter of window
+ *                 [i - (k - 1 - k/2), i + k/2] (SciPy's dilation origin, shifted by one on an even axis).  Sizes >= 1; an
+ *                 axis of size 1 is left alone.  Background in the image's dtype, exact.
+ *   rolling ball  skimage.restoration.rolling_ball(image, radius) (background/_rolling_ball.py), restated from scikit-image's
+ *                 published algorithm (parity unpinned: scikit-image is not a dependency): offsets o in [-R, R]^2 with
+ *                 R = ceil(radius) and |o| <= radius, diff[o] = k(0) - k(o) with k(o) = sqrt(max(radius^2 - |o|^2, 0));
+ *                 background(p) = min over o of img[p + o] + diff[o], +inf outside the frame.  Arithmetic in float32 for
+ *                 ZK_F32 and float64 otherwise, cast back to the image's dtype (integers truncate).  0 < radius <= 1536.
+ *   baseline      background/_baseline.py: num_iters rounds of gaussian_filter (axis 0, then axis 1) and np.minimum(., image),
+ *                 float64 throughout.  weights_y / weights_x: radius + 1 values w[0..r] of scipy.ndimage's symmetric kernel,
+ *                 w[0] the centre (radius 0 with w[0] = 1 for an axis SciPy skips); each tap in SciPy's order,
+ *                 t = x[0] w[0], then t += (x[-j] + x[+j]) w[j] for j = r .. 1, unfused: bit for bit SciPy's.
+ *
+ * residual (optional, NULL to skip): image - background in the background's type (NumPy's wrap-around for integers), then
+ * max(., 0) when clip is non-zero.  Opening and rolling ball write background and residual in the image's dtype, baseline in
+ * float64.  NaN or inf pixels are not pinned.  The _dev variants take device pointers and run on hip_stream (they
+ * synchronise it once their scratch is released); nothing crosses to the host.
+ * ------------------------------------------------------------------------------------------------------ */
+int zk_background_opening(int device, const void* image_host, int dtype, int64_t height, int64_t width, int64_t size_y,
+                          int64_t size_x, int clip, void* background_host, void* residual_host);
+int zk_background_opening_dev(int device, const void* image_dev, int dtype, int64_t height, int64_t width, int64_t size_y,
+                              int64_t size_x, int clip, void* background_dev, void* residual_dev, void* hip_stream);
+int zk_background_rolling_ball(int device, const void* image_host, int dtype, int64_t height, int64_t width, double radius,
+                               int clip, void* background_host, void* residual_host);
+int zk_background_rolling_ball_dev(int device, const void* image_dev, int dtype, int64_t height, int64_t width, double radius,
+                                   int clip, void* background_dev, void* residual_dev, void* hip_stream);
+int zk_background_baseline(int device, const void* image_host, int dtype, int64_t height, int64_t width, const double* weights_y,
+                           int64_t radius_y, const double* weights_x, int64_t radius_x, int64_t num_iters, int clip,
+                           double* background_host, double* residual_host);
+int zk_background_baseline_dev(int device, const void* image_dev, int dtype, int64_t height, int64_t width,
+                               const double* weights_y /* host */, int64_t radius_y, const double* weights_x /* host */,
+                               int64_t radius_x, int64_t num_iters, int clip, double* background_dev, double* residual_dev,
+                               void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * First downstream consumer of the moment matrix: the two streaming passes of
  *   pca(X, n_components)   reference features/_dimension_reduction.py:3-6 (sklearn PCA(n).fit_transform(X))
  * on a float64 matrix X (N, D), D <= 127 (45 moments at n_max 8).

@@ -3,7 +3,8 @@
 ``from mtflearn_amd import ZPs, zmoments`` mirrors ``from mtflearn import ZPs, zmoments``
 (reference ``mtflearn/__init__.py:37-38``).  Only this path and the rows SURVEY 8(f) names around it are provided
 (``mtflearn_amd.features``: parameter pickers, ``pca``; ``mtflearn_amd.clustering``: ``kmeans_lbs`` / ``gmm_lbs`` /
-``sort_lbs``; ``mtflearn_amd.manifold``: ``ForceGraph8``); see DESIGN.md.
+``sort_lbs``; ``mtflearn_amd.manifold``: ``ForceGraph8``; ``mtflearn_amd.background``: ``estimate_background_*`` /
+``remove_background_*`` and their parameter picker); see DESIGN.md.
 """
 __version__ = "0.1.0"
 

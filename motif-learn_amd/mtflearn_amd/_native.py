@@ -105,6 +105,16 @@ SYMBOLS = {
     "zk_local_max_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_double, c_int, c_double, c_void_p, c_int64,
                                  POINTER(c_int64), c_void_p]),
     "zk_local_max_last_launches": (c_int64, []),
+    "zk_background_opening": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "zk_background_opening_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                                          c_void_p]),
+    "zk_background_rolling_ball": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_double, c_int, c_void_p, c_void_p]),
+    "zk_background_rolling_ball_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_double, c_int, c_void_p, c_void_p,
+                                               c_void_p]),
+    "zk_background_baseline": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                       c_int, c_void_p, c_void_p]),
+    "zk_background_baseline_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                           c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "zk_gram": (c_int, [c_int, POINTER(c_double), c_int64, c_int, POINTER(c_double), POINTER(c_void_p)]),
     "zk_project": (c_int, [c_int, c_void_p, c_int64, c_int, POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double),
                            c_int]),

@@ -31,7 +31,7 @@ import numpy as np
 from . import _native
 
 __all__ = ["shard_bounds", "one_gpu_rank_env", "RcclComm", "TorchComm", "DeviceCompute", "patch_moments_device",
-           "frame_moments_device", "frame_maps_device", "local_max_device", "points_moments_device", "sharded_patch_moments", "sharded_frame_moments",
+           "frame_moments_device", "frame_maps_device", "local_max_device", "points_moments_device", "remove_background_device", "sharded_patch_moments", "sharded_frame_moments",
            "sharded_frame_maps", "sharded_frames_moments"]
 
 
@@ -236,7 +236,7 @@ def frame_maps_device(plan: "_native.Plan", image, n_complex, folds=(2, 3, 4, 6)
 
 
 def _image_code(image):
-    """ZK_* code of a 2-D device image for ``zk_local_max_dev``: the two float types and the narrow detector formats."""
+    """ZK_* code of a 2-D device image for ``zk_local_max_dev`` and ``zk_background_*_dev``: the two float types and the narrow detector formats."""
     if _is_native(image):
         code = _native.dtype_code(image.dtype)
         name = image.dtype
@@ -246,7 +246,7 @@ def _image_code(image):
                 torch.int16: _native.ZK_I16, getattr(torch, "uint16", None): _native.ZK_U16}.get(image.dtype)
         name = image.dtype
     if code is None:
-        raise TypeError(f"local_max_device takes float32, float64, uint8, uint16 or int16 images, not {name}")
+        raise TypeError(f"device images must be float32, float64, uint8, uint16 or int16, not {name}")
     return code
 
 
@@ -318,6 +318,51 @@ def points_moments_device(plan: "_native.Plan", image, points, out=None):
     if n:
         plan.transform_points_dev(image.data_ptr(), code, h, w, points.data_ptr(), n, out.data_ptr(), _current_stream_ptr(image))
     return out
+
+
+def _empty_image(shape, dtype, like):
+    """Uninitialised device array of ``shape`` and NumPy ``dtype`` on ``like``'s device, of ``like``'s kind."""
+    if _is_native(like):
+        return _native.DeviceArray(shape, dtype, like.device.index)
+    import torch
+    tdtype = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.uint8): torch.uint8,
+              np.dtype(np.int16): torch.int16, np.dtype(np.uint16): getattr(torch, "uint16", None)}[np.dtype(dtype)]
+    return torch.empty(shape, dtype=tdtype, device=like.device)
+
+
+def remove_background_device(image, method, parameter, clip=True, **method_kw):
+    """:mod:`mtflearn_amd.background` on a frame resident on the GPU (a torch tensor or a
+    :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` of float32 / float64 / uint8 / uint16 / int16).
+
+    ``method``: ``"opening"`` (``parameter`` = size), ``"rolling_ball"`` (radius) or ``"baseline"`` (sigma; ``num_iters``
+    as a keyword, default 10).  Returns ``(residual, background)`` as device arrays of the image's kind, in the image's dtype
+    (float64 for the baseline), the same numbers as the host ``remove_background_*``.  Runs on torch's current stream and no
+    pixel crosses to the host, so a frame goes to :func:`local_max_device` and :func:`points_moments_device` without PCIe."""
+    from .background import _method_parameter
+    if len(image.shape) != 2:
+        raise ValueError("image must be a 2D array.")
+    param = _method_parameter(method, parameter, method_kw)
+    if not image.is_cuda:
+        raise ValueError("image must live on the GPU")
+    if not _is_native(image) and not image.is_contiguous():
+        image = image.contiguous()
+    code = _image_code(image)
+    h, w = (int(v) for v in image.shape)
+    out_dtype = np.float64 if method == "baseline" else _numpy_dtype(image)
+    background = _empty_image((h, w), out_dtype, image)
+    residual = _empty_image((h, w), out_dtype, image)
+    lib = _native.load()
+    args = (image.device.index, c_void_p(image.data_ptr()), code, h, w)
+    outs = (int(bool(clip)), c_void_p(background.data_ptr()), c_void_p(residual.data_ptr()), c_void_p(_current_stream_ptr(image)))
+    if method == "opening":
+        _native.check(lib.zk_background_opening_dev(*args, param[0], param[1], *outs), "zk_background_opening_dev")
+    elif method == "rolling_ball":
+        _native.check(lib.zk_background_rolling_ball_dev(*args, param, *outs), "zk_background_rolling_ball_dev")
+    else:
+        (wy, wx), iters = param
+        _native.check(lib.zk_background_baseline_dev(*args, wy.ctypes.data_as(c_void_p), len(wy) - 1, wx.ctypes.data_as(c_void_p),
+                                                     len(wx) - 1, iters, *outs), "zk_background_baseline_dev")
+    return residual, background
 
 
 # ---------------------------------------------------------------------------------------------------------
