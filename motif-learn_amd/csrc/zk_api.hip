@@ -131,7 +131,7 @@ static int build_generic_tables(zk_plan* p, const double* basis) {
           basis[((size_t)j * K + pix[t].x) * K + pix[t].y] * inv_area;
   }
   // dense mode of the kernels that sum the caller's own numbers follows the reference's convolution (zk_plan::conv_flip)
-  p->conv_flip = !getenv("ZK_NO_CONV_FLIP");
+  p->conv_flip = !zk_switch_on(ZK_NO_CONV_FLIP);
   std::vector<double> sign((size_t)p->n_chunks * CH, 1.0);
   for (int j = 0; j < NP; ++j) sign[j] = (p->conv_flip && (p->n[j] & 1)) ? -1.0 : 1.0;
   ZK_HIP(hipMalloc((void**)&p->d_sign, sign.size() * sizeof(double)));
@@ -199,12 +199,6 @@ extern "C" int zk_plan_create(int size, int n_poly, const int32_t* n, const int3
   if (!rc) rc = zk_fold_build(p, basis);
   if (!rc) rc = zk_sep_build(p, basis);
   if (!rc) rc = zk_direct_build(p, basis);  // the plain sum on the matrix cores: sets of >= 92 functions (n_max >= 13)
-  if (!rc) {
-    // From which order ZK_PATH_AUTO leaves the polynomial kernels for the plain sum (see resolve_path); ZK_AUTO_DIRECT_NMAX
-    // in the environment moves the switch for A/B measurements.
-    const char* env = getenv("ZK_AUTO_DIRECT_NMAX");
-    p->auto_direct_from = env && *env ? atoi(env) : ZK_AUTO_DIRECT_NMAX_DEFAULT;
-  }
   if (rc) {
     std::string keep = g_last_error;
     zk_plan_destroy(p);
@@ -227,7 +221,7 @@ static bool path_available(const zk_plan* p, int mode, int dtype, int path) {
 }
 
 // Does ZK_PATH_AUTO take the plain sum over the caller's own numbers (matrix cores) for this plan?  Yes for every large
-// set without polynomial tables (n_max > 24, other sets), and for the full Zernike sets from order `auto_direct_from`:
+// set without polynomial tables (n_max > 24, other sets), and for the full Zernike sets from order ZK_AUTO_DIRECT_FROM:
 // the polynomial kernels substitute the exact polynomial for the caller's values and recombine Legendre sums whose
 // coefficients grow like (1 + sqrt 2)^n, so their distance from the reference's np.dot grows with the order -- measured
 // against reference outputs on structured inputs (tests/golden: st_*), profiles/r04_high_orders.txt -- while the plain
@@ -236,19 +230,19 @@ bool zk_plan_auto_direct(const zk_plan* p, int mode, int dtype) {
   if (!path_available(p, mode, dtype, ZK_PATH_DIRECT)) return false;
   if (!p->sep) return true;
   const int n_max = zk_full_set_nmax(p);
-  return n_max >= p->auto_direct_from;
+  return n_max >= ZK_AUTO_DIRECT_FROM;
 }
 
 // ZK_PATH_AUTO: separable (batches: its stream form where the plan prefers it), else folded (frame), else generic.
 // `n_units` = patches of the call (batch mode).
 static int resolve_path(const zk_plan* p, int mode, int dtype, int64_t n_units = 0) {
   if (p->path != ZK_PATH_AUTO) return path_available(p, mode, dtype, p->path) ? p->path : -1;
-  if (!getenv("ZK_NO_DIRECT")) {
+  if (zk_auto_direct_allowed()) {
     if (zk_plan_auto_direct(p, mode, dtype))
       return mode == 1 || n_units >= 64 ? ZK_PATH_DIRECT : ZK_PATH_GENERIC;  // (less than a wave of patches: the per-lane sum)
     // a full Zernike set of an order that AUTO serves with the plain sum, but outside the matrix-core kernels' shapes (dense windows
     // whose staged tile exceeds the LDS: float64 above ~100 px, float32 above ~150): the per-lane plain sum -- slow, and exact
-    if (p->sep && zk_full_set_nmax(p) >= p->auto_direct_from) return ZK_PATH_GENERIC;
+    if (p->sep && zk_full_set_nmax(p) >= ZK_AUTO_DIRECT_FROM) return ZK_PATH_GENERIC;
   }
   if (mode == 0 && path_available(p, mode, dtype, ZK_PATH_STREAM) &&
       (zk_sep_stream_preferred(p, dtype, n_units) || !path_available(p, mode, dtype, ZK_PATH_SEPARABLE)))
@@ -330,7 +324,7 @@ extern "C" int zk_transform_frame_dev(zk_plan* p, const void* image, int dtype, 
   if (path < 0) return zk_fail(ZK_E_BADARG, "the forced kernel path is not available for this plan / dtype");
   // n_max <= 8 and windows up to 65 px: the strip form of the dense kernel (two outputs per lane, zk_sep_strip.hip);
   // ZK_NO_STRIP in the environment keeps the one-output kernel (A/B measurements, tests)
-  if (path == ZK_PATH_SEPARABLE && zk_sep_strip_available(p, dtype) && !getenv("ZK_NO_STRIP"))
+  if (path == ZK_PATH_SEPARABLE && zk_sep_strip_available(p, dtype) && !zk_switch_on(ZK_NO_STRIP))
     return zk_launch_sep_strip(p, image, dtype, H, W, row0, n_rows, out, s);
   if (path == ZK_PATH_SEPARABLE) return zk_launch_sep_frame(p, image, dtype, H, W, row0, n_rows, out, s);
   if (path == ZK_PATH_FOLDED) return zk_launch_fast_frame(p, image, dtype, H, W, row0, n_rows, out, s);

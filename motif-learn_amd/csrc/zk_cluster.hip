@@ -936,8 +936,6 @@ __global__ __launch_bounds__(256, 2) void wgram_mfma_kernel(const double* __rest
 // pass with sums 0.67 -> 0.46 ms, labels only 0.45 -> 0.31, seeding 0.41 -> 0.36): two tile buffers (the next tile's DMA under
 // this tile's arithmetic) only while eight waves still fit a CU's 160 KiB, else one
 int tile_bufs(const zk_rows* m, size_t extra = 0) {
-  static const int forced = getenv("ZK_TILE_NBUF") ? atoi(getenv("ZK_TILE_NBUF")) : 0;  // experiments
-  if (forced == 1 || forced == 2) return forced;
   return 8 * ((size_t)2 * TILE * m->D * sizeof(double) + extra + 512) <= 160 * 1024 ? 2 : 1;
 }
 size_t tile_lds(const zk_rows* m, int nbuf) { return (size_t)nbuf * TILE * m->D * sizeof(double); }
@@ -945,8 +943,7 @@ size_t tile_lds(const zk_rows* m, int nbuf) { return (size_t)nbuf * TILE * m->D 
 // persistent single-wave workgroups: as many per CU as the LDS tile allows (at most 8), never more than tiles
 int row_grid(const zk_rows* m, size_t lds_bytes) {
   // (LDS is handed out in 512-byte granules: a 64 x 45 tile of doubles is exactly 45 of them, and SEVEN fit a CU's 160 KiB)
-  static const int margin = getenv("ZK_ROW_GRID_MARGIN") ? atoi(getenv("ZK_ROW_GRID_MARGIN")) : 0;
-  int per_cu = (int)((160 * 1024) / (((lds_bytes + 511) & ~(size_t)511) + margin));
+  int per_cu = (int)((160 * 1024) / ((lds_bytes + 511) & ~(size_t)511));
   per_cu = std::max(1, std::min(per_cu, 8));
   const long long tiles = (m->N + TILE - 1) / TILE;
   return (int)std::min<long long>(tiles, (long long)per_cu * m->n_cu);
@@ -1492,7 +1489,7 @@ extern "C" int zk_gmm_estep(zk_rows* m, const double* prec_chol, const double* m
     C[2 * c + 1] = log_w[c];
   }
   // matrix-core form (D <= 48, k <= 8: the factors of all components fit the LDS of a CU beside the waves' row blocks)
-  static const bool no_mfma = getenv("ZK_ESTEP_VALU") != nullptr;  // A/B runs: the scalar-operand kernel
+  const bool no_mfma = zk_switch_on(ZK_ESTEP_VALU);  // A/B runs: the scalar-operand kernel
   const int NB = (D + 15) / 16;
   if (NB <= 3 && k <= 8 && D >= 2 && !no_mfma) {
     const int psteps = 2 * NB * (NB + 1);
@@ -1529,11 +1526,9 @@ extern "C" int zk_gmm_estep(zk_rows* m, const double* prec_chol, const double* m
     if (rc) return rc;
     // twelve waves per workgroup (three per SIMD) while the factors and the waves' row blocks fit a CU's LDS, else eight: the
     // chains are 4 / 8 / 12 MFMAs long, and short dependent chains gain from a third wave (tools/micro_mfma64_chain.hip)
-    static const int forced_nw = getenv("ZK_ESTEP_WAVES") ? atoi(getenv("ZK_ESTEP_WAVES")) : 0;
     const size_t lds_tab = ((size_t)k * psteps * 64 + (size_t)k * NB * 16) * sizeof(double);
     const size_t lds_wave = ((size_t)16 * D + 4 + 128) * sizeof(double);
-    int nw = lds_tab + 12 * lds_wave <= 160 * 1024 ? 12 : 8;
-    if (forced_nw == 8 || (forced_nw == 12 && nw == 12)) nw = forced_nw;
+    const int nw = lds_tab + 12 * lds_wave <= 160 * 1024 ? 12 : 8;
     const size_t lds = lds_tab + nw * lds_wave;
     if ((rc = check_lds(lds))) return rc;
     const long long n_blocks = (m->N + 15) / 16;
@@ -1611,7 +1606,7 @@ static int rows_gram(zk_rows* m, const double* w_dev, int count, const double* s
   int rc = upload_tab(m, m->h_buf);
   m->h_buf.clear();
   if (rc) return rc;
-  static const bool no_mfma = getenv("ZK_WGRAM_VALU") != nullptr;  // A/B runs: the register-tiled kernel
+  const bool no_mfma = zk_switch_on(ZK_WGRAM_VALU);  // A/B runs: the register-tiled kernel
   if (D1 <= 48 && D >= 2 && !no_mfma) {
     // matrix-core form: every component of the call in one pass; `sets` groups of six waves (one per block of the triangle),
     // each set walking its share of the tiles

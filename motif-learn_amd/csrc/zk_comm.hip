@@ -191,7 +191,7 @@ extern "C" int zk_comm_init_rank(int device, int rank, int world, const void* id
   c->device = device;
   c->rank = rank;
   c->world = world;
-  if (const char* a = getenv("ZK_COMM_ALGO")) {
+  if (const char* a = zk_switch_str(ZK_COMM_ALGO)) {
     if (!strcmp(a, "p2p")) c->algo = 1;
     else if (!strcmp(a, "allgather")) c->algo = 2;
     else if (!strcmp(a, "bcast")) c->algo = 3;
@@ -294,7 +294,7 @@ extern "C" int zk_comm_init_tcp(int device, int rank, int world, const char* hos
       // address that is not assigned locally (a VIP, a NAT or service address) cannot be bound at all -- both fall back
       // to every interface.  ZK_COMM_BIND_ADDR (an IPv4 literal, or "any") overrides.
       bool literal = inet_pton(AF_INET, host, &a.sin_addr) == 1;
-      const char* force = getenv("ZK_COMM_BIND_ADDR");
+      const char* force = zk_switch_str(ZK_COMM_BIND_ADDR);
       if (force && *force) {
         if (!strcmp(force, "any")) a.sin_addr.s_addr = htonl(INADDR_ANY);
         else if (inet_pton(AF_INET, force, &a.sin_addr) != 1) {
@@ -701,9 +701,8 @@ extern "C" int zk_clock_monitor_start(int device, double max_ms, zk_clock_monito
   if (e == hipSuccess) {
     *m->h_flag = 1;
     for (int k = 0; k < 4; ++k) m->h_out[k] = 0;
-    const char* md = getenv("ZK_CLOCK_MONITOR_MODE");
     hipLaunchKernelGGL(clock_monitor_kernel, dim3(1), dim3(64), 0, m->stream, (volatile int*)d_flag, d_out,
-                       (unsigned long long)(max_ms * 1e5), md ? atoi(md) : 0);
+                       (unsigned long long)(max_ms * 1e5), (int)zk_switch_int(ZK_CLOCK_MONITOR_MODE, 0));
     e = hipGetLastError();
   }
   if (e != hipSuccess) {

@@ -511,7 +511,7 @@ int zk_direct_build(zk_plan* p, const double* basis) {
     d->n_chunks = (blocks + ZK_DIRECT_FB_MAX - 1) / ZK_DIRECT_FB_MAX;
     d->fb_hi = (blocks + d->n_chunks - 1) / d->n_chunks;
     d->n_hi = blocks % d->n_chunks ? blocks % d->n_chunks : d->n_chunks;
-    if (getenv("ZK_DIRECT_CH96")) d->fb_hi = ZK_DIRECT_FB_MAX, d->n_hi = d->n_chunks;
+    if (zk_switch_on(ZK_DIRECT_CH96)) d->fb_hi = ZK_DIRECT_FB_MAX, d->n_hi = d->n_chunks;
   }
   size_t cols = 0;  // columns of all chunks together
   for (int c = 0; c < d->n_chunks; ++c) cols += 16 * d->chunk_fb(c);

@@ -428,8 +428,7 @@ extern "C" int zk_rows_knn_correlation(zk_rows* m, int k, int local_connectivity
       if (p) (void)hipFree(p);
   };
   // k <= 16 and D <= 96: the matrix-core kernel on the blocked copy (ZK_KNN_SCALAR=1 keeps the scalar-operand kernel for A/B)
-  const char* force_scalar = getenv("ZK_KNN_SCALAR");
-  const bool mfma = k <= 16 && D <= 96 && N < (1LL << 31) - 64 && !(force_scalar && force_scalar[0] == '1');
+  const bool mfma = k <= 16 && D <= 96 && N < (1LL << 31) - 64 && zk_switch_int(ZK_KNN_SCALAR, 0) != 1;
   // feature steps of the blocked copy: the kernel instance that holds D (zero features beyond it)
   const int steps = D <= 8 ? 2 : D <= 16 ? 4 : D <= 32 ? 8 : (D + 15) / 16 * 4;
   const long long Np64 = (N + 63) & ~63LL;
@@ -461,8 +460,7 @@ extern "C" int zk_rows_knn_correlation(zk_rows* m, int k, int local_connectivity
     // its lists again -- 100 000 x 45 in 1 / 2 / 4 / 8 / 16 parts: 28 / 27 / 29 / 32 / 38 ms -- so only up to one round of
     // resident workgroups)
     const unsigned tiles = tiles1;
-    int parts = (int)(3u * 256u / tiles);
-    if (const char* pe = getenv("ZK_KNN_PARTS")) parts = atoi(pe);
+    int parts = (int)zk_switch_int(ZK_KNN_PARTS, 3u * 256u / tiles);
     if (parts > n_stages / 16) parts = (int)(n_stages / 16);
     parts = parts < 1 ? 1 : parts > 16 ? 16 : parts;
     int* d_pind = nullptr;

@@ -72,11 +72,8 @@ int widen(int dtype, const void* in, float* out, long long n, hipStream_t s) {
 
 size_t chunk_bytes(const zk_plan* p) {
   if (p->host_chunk) return p->host_chunk;
-  if (const char* e = getenv("ZK_HOST_CHUNK_MB")) {
-    const long mb = atol(e);
-    if (mb > 0) return (size_t)mb << 20;
-  }
-  return (size_t)256 << 20;
+  const long mb = zk_switch_int(ZK_HOST_CHUNK_MB, 256);
+  return (size_t)(mb > 0 ? mb : 256) << 20;
 }
 
 int ring_get(zk_plan* p, zk_host_ring** out) {

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "zernike_hip.h"
+#include "zk_switches.h"
 
 // basis functions per accumulation pass of the generic kernel: 64 when the whole set fits one pass, else 32
 // (batch (56, n_max 25): 25.9 ms at 16 -> 13.6 at 32 -> 12.8 at 64; batch (32, 8): 14.5 -> 9.8 -> 2.6;
@@ -51,7 +52,6 @@ struct zk_plan {
 
   // ---- large sets, batch mode: DMA-staged direct sums, CH functions per launch (zk_direct_patches.hip) ----
   struct zk_direct_tables* direct = nullptr;  // nullptr below 92 functions
-  int auto_direct_from = 1 << 30;             // full Zernike sets: ZK_PATH_AUTO takes the plain sum from this n_max on
 
   // ---- symmetry maps: fold weights + cos / sin(m theta) (zk_sep_maps.hip).  One device table per distinct
   // (folds, m_unselect, theta) option set, kept for the life of the plan (a few KiB each, at most
@@ -180,9 +180,9 @@ int zk_direct_build(zk_plan* p, const double* basis);  // zk_direct_patches.hip
 void zk_direct_free(zk_plan* p);
 bool zk_direct_patches_available(const zk_plan* p, int dtype);
 bool zk_plan_auto_direct(const zk_plan* p, int mode, int dtype);  // zk_api.hip: does ZK_PATH_AUTO take the plain sum?
-#ifndef ZK_AUTO_DIRECT_NMAX_DEFAULT
-#define ZK_AUTO_DIRECT_NMAX_DEFAULT 17
-#endif
+// may ZK_PATH_AUTO take the plain sum at all?  (asked by resolve_path and by the symmetry maps, which follow it)
+static inline bool zk_auto_direct_allowed() { return !zk_switch_on(ZK_NO_DIRECT); }
+#define ZK_AUTO_DIRECT_FROM 17  // full Zernike sets: ZK_PATH_AUTO takes the plain sum from this n_max on
 int zk_launch_direct_patches(zk_plan* p, const void* in, int dtype, int64_t n_patches, double* out, hipStream_t s);
 bool zk_direct_frame_available(const zk_plan* p, int dtype);
 int zk_launch_direct_frame(zk_plan* p, const void* in, int dtype, int64_t H, int64_t W, int64_t row0, int64_t n_rows, double* out,

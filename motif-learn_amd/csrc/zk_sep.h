@@ -199,22 +199,11 @@ struct zk_sep_tables {
   stream_tables stream[2];
 };
 
-// Timing-only ablation builds of the batch kernels (make ABLATE=n -> libzernike_hip_ablate<n>.so; outputs
-// are wrong by construction): 1 = no arithmetic (DMA + LDS reads + stores), 2 = no DMA (arithmetic on
-// stale LDS), 3 = no output stores.  cdna_hip_programming.md section 5.4 rule 17: stubbed values are kept live.
-#ifndef ZK_ABLATE
-#define ZK_ABLATE 0
-#endif
-// Cache policy of the streamed operands: aux = 2 is "nt" (non-temporal).  Every patch byte is read
-// exactly once by one CU and every moment is written once, so both streams bypass cache retention:
-// interleaved A/B on one device, median of 31 rounds (profiles/r01_ablation.txt):
+// Cache policy of the batch kernels' streamed operands: aux = 2 is "nt" (non-temporal), and the moments leave by
+// non-temporal stores.  Every patch byte is read exactly once by one CU and every moment is written once, so both
+// streams bypass cache retention: interleaved A/B on one device, median of 31 rounds (profiles/r01_ablation.txt):
 //   default policy 3.365 ms | nt loads 3.136 | nt loads + nt stores 3.124 | nt stores only 3.288
-#ifndef ZK_DMA_AUX
-#define ZK_DMA_AUX 2
-#endif
-#ifndef ZK_STORE_NT
-#define ZK_STORE_NT 1
-#endif
+#define ZK_AUX_NT 2
 
 #ifdef __HIPCC__
 // Row sums of one row pair: S(a, parity of b) of zk_sep.h's header comment.
@@ -502,20 +491,12 @@ __device__ __forceinline__ void zk_batch_store_rows(const double (&z)[NP], const
     for (int k = lane; 2 * k < vd + mis; k += 64) {
       const f64x2 v = *(const f64x2*)(slab + 2 * k);
       const int e = 2 * k - mis;  // output element of v.x
-#if ZK_ABLATE == 3
-      asm volatile("" ::"v"(v));
-#else
       if (e >= 0 && e + 2 <= vd) {
-#if ZK_STORE_NT
         __builtin_nontemporal_store(v, (f64x2*)(dst + e));
-#else
-        *(f64x2*)(dst + e) = v;
-#endif
       } else {
         if (e >= 0 && e < vd) dst[e] = v.x;
         if (e + 1 >= 0 && e + 1 < vd) dst[e + 1] = v.y;
       }
-#endif
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // slab reads done before the next pass overwrites
   }
@@ -552,11 +533,7 @@ __device__ __forceinline__ void zk_batch_store_rows_pair(const double (&z)[NP], 
       const f64x2 v = *(const f64x2*)(slab + 2 * k);
       const int e = 2 * k - mis;
       if (e >= 0 && e + 2 <= vd) {
-#if ZK_STORE_NT
         __builtin_nontemporal_store(v, (f64x2*)(dst + e));
-#else
-        *(f64x2*)(dst + e) = v;
-#endif
       } else {
         if (e >= 0 && e < vd) dst[e] = v.x;
         if (e + 1 >= 0 && e + 1 < vd) dst[e + 1] = v.y;

@@ -499,7 +499,10 @@ int zk_maps_planes_g2(zk_plan* p, const void* in, int dtype, int64_t H, int64_t 
   //  28.8 ms with 1-GiB bands, 45 ms at 256 MiB, 187 ms at 32 MiB)
   int64_t band = (int64_t)((size_t)1 << 30) / ((int64_t)p->n_poly * W * (int64_t)sizeof(double));
   band = band < 8 ? 8 : (band > n_rows ? n_rows : band);
-  if (p->path != ZK_PATH_SEPARABLE && zk_plan_auto_direct(p, 1, dtype) && !getenv("ZK_NO_DIRECT")) band = zk_direct_band_rows(p, W, band, n_rows);
+  // the bands' moments from the kernel family ZK_PATH_AUTO takes at this order (zk_api.hip: the plain sum on the matrix
+  // cores where the polynomial kernels miss the parity criterion), unless the separable family is forced
+  const bool direct = p->path != ZK_PATH_SEPARABLE && zk_plan_auto_direct(p, 1, dtype) && zk_auto_direct_allowed();
+  if (direct) band = zk_direct_band_rows(p, W, band, n_rows);
   const size_t need = (size_t)p->n_poly * band * W * sizeof(double);
   if (p->d_scratch_bytes < need) {
     if (p->d_scratch) ZK_HIP(hipFree(p->d_scratch));
@@ -513,9 +516,6 @@ int zk_maps_planes_g2(zk_plan* p, const void* in, int dtype, int64_t H, int64_t 
     const int64_t nb = n_rows - b0 < band ? n_rows - b0 : band;
     const long long keep = p->out_plane;
     p->out_plane = 0;  // the scratch matrix is compact
-    // the band's moments from the kernel family ZK_PATH_AUTO takes at this order (zk_api.hip: the plain sum on the matrix
-    // cores where the polynomial kernels miss the parity criterion), unless the separable family is forced
-    const bool direct = p->path != ZK_PATH_SEPARABLE && zk_plan_auto_direct(p, 1, dtype) && !getenv("ZK_NO_DIRECT");
     int rc = direct ? zk_launch_direct_frame(p, in, dtype, H, W, row0 + b0, nb, p->d_scratch, s)
                     : zk_launch_sep_frame(p, in, dtype, H, W, row0 + b0, nb, p->d_scratch, s);
     p->out_plane = keep;

@@ -59,9 +59,6 @@
 // buffers' placement, tools/placement.py).  Starting every wave at a different unit spreads the rows in
 // flight over the whole patch period.  A wave starts at the first unit of some row pair, so the units
 // of a row stay consecutive.
-#ifndef ZK_ROTATE
-#define ZK_ROTATE 1
-#endif
 
 namespace {
 
@@ -78,9 +75,6 @@ namespace {
 // 32 KiB = 128 KiB) keep the next unit's DMA in flight during the whole of the current unit's arithmetic.
 #ifndef ZK_BATCH_DEPTH_1W
 #define ZK_BATCH_DEPTH_1W 2
-#endif
-#ifndef ZK_BATCH_PIPE
-#define ZK_BATCH_PIPE 1  // wide units: software-pipelined scalar loads (see quarter())
 #endif
 #define ZK_BATCH_DEPTH(NMAX, MASK) (((NMAX) <= ZK_BATCH_2W || (MASK) != 15) ? 1 : ZK_BATCH_DEPTH_1W)
 
@@ -106,7 +100,7 @@ __device__ __forceinline__ void zk_patch_body(
   constexpr int SH = RUN == 8 ? 1 : 2;  // rotation = patch >> SH makes ds_read_b128 conflict-free
   // nt only where a run is a whole 128-B line: 64-B runs share their line with another unit of the same
   // row, which must still find it in L2 (default policy: 3.70 -> 2.14 ms at K=16, 8.9 -> 6.0 ms at K=48)
-  constexpr int DMA_AUX = RUN == 8 ? ZK_DMA_AUX : 0;
+  constexpr int DMA_AUX = RUN == 8 ? ZK_AUX_NT : 0;
   constexpr int DEPTH = PAIR ? 2 : ZK_BATCH_DEPTH(NMAX, MASK);  // slabs of 16 KiB (per wave, or per pair)
   constexpr int NDMA = PAIR ? 8 : 16;                           // DMA instructions this wave issues per unit
 
@@ -155,15 +149,13 @@ __device__ __forceinline__ void zk_patch_body(
   const ZK_CONST double* px = zk_const(xq);
   [[maybe_unused]] const ZK_CONST double* p1 = zk_const(pfull);
 
-  // first unit of this wave (see ZK_ROTATE): the start of some row pair; the loop visits off, off+1, ...,
+  // first unit of this wave (unit-order rotation, above): the start of some row pair; the loop visits off, off+1, ...,
   // wrapping around, so the units of a row stay consecutive
   const int off = n_row_starts > 0 ? zk_const(row_starts)[(int)((group * 7) % n_row_starts)] : 0;
   auto unit_at = [&](int k) { return k + off < n_units ? k + off : k + off - n_units; };
-#if ZK_ABLATE != 2
   issue(unit_at(0), wl);
   if constexpr (DEPTH == 2)
     if (n_units > 1) issue(unit_at(1), wl + 4096);
-#endif
   for (int k = 0; k < n_units; ++k) {
     const int u = unit_at(k);
     const int c0 = utab[8 * u + 4], cmin = utab[8 * u + 5], r = utab[8 * u + 6];
@@ -204,15 +196,8 @@ __device__ __forceinline__ void zk_patch_body(
       if (rearm) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // unit is in VGPRs: the slab may be re-armed
         if constexpr (PAIR) __syncthreads();                  // ... once the partner has read it too
-#if ZK_ABLATE != 2
         if (k + DEPTH < n_units) issue(unit_at(k + DEPTH), ws);
-#endif
       }
-#if ZK_ABLATE == 1
-#pragma unroll
-      for (int i = 0; i < 2; ++i) asm volatile("" ::"v"(A[i]), "v"(B[i]), "v"(C[i]), "v"(D[i]));
-      if (false)
-#endif
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -227,7 +212,6 @@ __device__ __forceinline__ void zk_patch_body(
     // wide units: 8 quadrant columns (2 granules of the line + 2 of its mirror line) of a single row
     auto quarter = [&](int q0, bool rearm, auto first_row) {
       gran_t A[2], B[2];
-#if ZK_BATCH_PIPE
       // The Legendre row of pixel c+1 is fetched (scalar loads) while pixel c is being accumulated: with one
       // wave per SIMD nothing else hides the scalar-cache latency, and a load - wait - use sequence per pixel cost
       // 40 % of the wave's time (profiles/r02_sq_counters.txt).  The pixels of a quarter run branch-free
@@ -239,7 +223,6 @@ __device__ __forceinline__ void zk_patch_body(
       const ZK_CONST double* prow = p1 + (c0 + PXG * q0) * SROW;
 #pragma unroll
       for (int t = 0; t < NMAX; ++t) Pn[t] = prow[t];
-#endif
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         A[i] = lds_granule(0, q0 + i);
@@ -248,16 +231,8 @@ __device__ __forceinline__ void zk_patch_body(
       if (rearm) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if constexpr (PAIR) __syncthreads();
-#if ZK_ABLATE != 2
         if (k + DEPTH < n_units) issue(unit_at(k + DEPTH), ws);
-#endif
       }
-#if ZK_ABLATE == 1
-#pragma unroll
-      for (int i = 0; i < 2; ++i) asm volatile("" ::"v"(A[i]), "v"(B[i]));
-      if (false)
-#endif
-#if ZK_BATCH_PIPE
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -281,18 +256,6 @@ __device__ __forceinline__ void zk_patch_body(
           acc.template row_pixel_p0<decltype(first_row)::value>((double)av, (double)bv, Pc);
         }
       }
-#else
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int e = 0; e < PXG; ++e) {
-          const int c = c0 + PXG * (q0 + i) + e;
-          if (c >= cmin)  // wave-uniform: quadrant pixel inside the disk
-            acc.template row_pixel<decltype(first_row)::value>((double)A[i][e], (double)B[i][PXG - 1 - e],
-                                                               px + c * ZK_SEP_ROW);
-        }
-      }
-#endif
     };
     if constexpr (WIDE) {
       const bool second = (utab[8 * u + 7] >> 1) & 1;
@@ -303,19 +266,15 @@ __device__ __forceinline__ void zk_patch_body(
           else quarter(q0, q0 == 6, std::true_type{});
         }
       }
-#if ZK_ABLATE != 1
       if (rend) {
         acc.pair_combine();
         acc.row_end(px + r * ZK_SEP_ROW);
       }
-#endif
     } else {
       const bool outer = cmin < c0 + 2 * PXG, inner = cmax > c0 + 2 * PXG;  // which halves hold disk pixels
       if (outer) half(0, !inner);
       if (inner) half(2, true);
-#if ZK_ABLATE != 1
       if (rend) acc.row_end(px + r * ZK_SEP_ROW);
-#endif
     }
   }
 
@@ -406,17 +365,15 @@ int launch_one(zk_plan* p, const void* in, int64_t n_patches, double* out, hipSt
     // SIMD instead of one: (32, 12) 4.70 -> 5.39 TB/s, (32, 14) 3.96 -> 4.78, (32, 16) 2.66 -> 3.43, (40, 12) 3.65 -> 3.88.
     // Wide units (float32 K % 64 == 0, float64 K % 32 == 0) stay on the one-wave kernel with its pipelined scalar loads,
     // where each wave of a pair would use half of every Legendre row it fetches: (128, 12) 6.18 vs 5.30, (64, 16) 3.53 vs
-    // 2.93 (profiles/r02_batch_sweep.txt).  ZK_BATCH_PAIR=0 / 1 in the environment forces one form (A/B runs).
-    static const char* const force = getenv("ZK_BATCH_PAIR");
-    const bool use_pair = force ? force[0] != '0' : !WIDE;
-    if (use_pair) {
+    // 2.93 (profiles/r02_batch_sweep.txt).
+    if (!WIDE) {
       auto pk = zk_patch_pair_kernel<NMAX, RUN, TIN, WIDE>;
       const long long pblocks = (waves + 1) / 2;
       int rc = zk_prof_begin(p, s);
       if (rc) return rc;
       hipLaunchKernelGGL(pk, dim3((unsigned)pblocks), dim3(256), 65536, s, (const TIN*)in, out, bt.d_units, t->d_xq, t->d_T,
                          t->d_colmap, bt.n_units, p->n_poly, (long long)n_patches, p->size * p->size * (int)sizeof(TIN), ppp,
-                         bt.d_row_starts, ZK_ROTATE ? bt.n_row_starts : 0, t->d_pfull);
+                         bt.d_row_starts, bt.n_row_starts, t->d_pfull);
       ZK_HIP(hipGetLastError());
       return zk_prof_end(p, s);
     }
@@ -429,7 +386,7 @@ int launch_one(zk_plan* p, const void* in, int64_t n_patches, double* out, hipSt
   if (rc) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, s, (const TIN*)in,
                      out, bt.d_units, t->d_xq, t->d_T, t->d_colmap, bt.n_units, p->n_poly, (long long)n_patches,
-                     p->size * p->size * (int)sizeof(TIN), ppp, bt.d_row_starts, ZK_ROTATE ? bt.n_row_starts : 0,
+                     p->size * p->size * (int)sizeof(TIN), ppp, bt.d_row_starts, bt.n_row_starts,
                      t->d_pfull);
   ZK_HIP(hipGetLastError());
   return zk_prof_end(p, s);

@@ -148,7 +148,7 @@ int launch_one(zk_plan* p, const void* img, const int32_t* pts, int64_t H, int64
                      p->n_poly, perm)
   // whole-row 16-byte loads: float32 frames, windows of 8 .. 64 px (ZK_POINTS_NO_WIDE=1 in the environment: A/B, tests)
   const int K = p->size;
-  const bool wide_ok = sizeof(T) == 4 && K >= 8 && K <= 64 && !getenv("ZK_POINTS_NO_WIDE");
+  const bool wide_ok = sizeof(T) == 4 && K >= 8 && K <= 64 && !zk_switch_on(ZK_POINTS_NO_WIDE);
   if constexpr (sizeof(T) == 4) {
     if (wide_ok && K <= 32) ZK_POINTS_LAUNCH(4);
     else if (wide_ok) ZK_POINTS_LAUNCH(8);
@@ -250,8 +250,7 @@ __global__ __launch_bounds__(256) void zk_points_scatter_kernel(const int32_t* _
 // fills the plan's index list with the points in bucket order; *perm_out = nullptr when the call is not worth it
 int bucket_points(zk_plan* p, const int32_t* pts, int64_t H, int64_t W, int64_t n_points, const int32_t** perm_out, hipStream_t s) {
   *perm_out = nullptr;
-  const bool off = getenv("ZK_POINTS_NO_BUCKET") != nullptr;
-  if (off || n_points < 4096 || n_points > 0x7fffffffLL) return 0;  // (a few waves: nothing to gain; int32 indices)
+  if (zk_switch_on(ZK_POINTS_NO_BUCKET) || n_points < 4096 || n_points > 0x7fffffffLL) return 0;  // (a few waves: nothing to gain; int32 indices)
   const int bx = (int)((W + 255) >> 8);
   int rh_shift = 0;
   while ((((H - 1) >> rh_shift) + 1) * (long long)bx > (1 << 20)) ++rh_shift;

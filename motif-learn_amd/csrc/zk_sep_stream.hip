@@ -21,7 +21,7 @@
 // float32 up to n_max 8, issue-bound above (profiles/r01_stream_sweep.txt).  The position in the
 // stream -- row, column, inside the disk or not -- is wave-uniform and lives in SGPRs; a row may be flushed
 // in pieces (the sums are linear), so a wave can start at any line of the patch (channel spreading, see
-// ZK_ROTATE in zk_sep_patches.hip).
+// the unit-order rotation in zk_sep_patches.hip).
 //
 // Roofline: algorithmic bytes K*K*s + 8*N_poly per patch; HBM-bound.
 #include "zk_sep.h"
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(ZK_STREAM_WG, (NMAX <= 12 ? 2 : 1)) void zk_patch_s
 #pragma unroll
       for (int pg = 0; pg < 8; ++pg)
         __builtin_amdgcn_global_load_lds(ZK_GLOBAL_PTR(wbase + (poff[pg] + bo)), ZK_LDS_PTR(dst + pg * 256), 16, 0,
-                                         ZK_DMA_AUX);
+                                         ZK_AUX_NT);
     } else {  // straddled lines are shared with the neighbouring units: keep them in L2
 #pragma unroll
       for (int pg = 0; pg < 8; ++pg)
@@ -138,10 +138,8 @@ __global__ __launch_bounds__(ZK_STREAM_WG, (NMAX <= 12 ? 2 : 1)) void zk_patch_s
   auto unit_at = [&](int k) { return k + off < n_units ? k + off : k + off - n_units; };
   const int lbase = lane * 32, rot = lane >> 1;  // float index of this lane's line image; granule rotation
 
-#if ZK_ABLATE != 2
   issue(unit_at(0), 0);
   if (n_units > 1) issue(unit_at(1), 1);
-#endif
   for (int k = 0; k < n_units; ++k) {
     const int u = unit_at(k);
     const int t0 = utab[4 * u + 1], urow = utab[4 * u + 2];
@@ -160,10 +158,6 @@ __global__ __launch_bounds__(ZK_STREAM_WG, (NMAX <= 12 ? 2 : 1)) void zk_patch_s
       if (g < 7) nv4 = granule(g + 1);
       const int tg = t0 + PXG * g;
       if (tg + PXG - 1 < ts) continue;  // the current row has not begun (te >= tg always holds)
-#if ZK_ABLATE == 1
-      asm volatile("" ::"v"(v));
-      if (false)
-#endif
       {
         // The loop body is straight-line code plus ONE conditional block, the row end (with any more
         // control flow around the moment updates the compiler keeps two copies of M and moves them every
@@ -209,9 +203,7 @@ __global__ __launch_bounds__(ZK_STREAM_WG, (NMAX <= 12 ? 2 : 1)) void zk_patch_s
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // slab consumed: re-arm it with unit k + 2
-#if ZK_ABLATE != 2
     if (k + 2 < n_units) issue(unit_at(k + 2), k & 1);
-#endif
   }
   acc.stream_row_end(X, pf + rr * SROW);
 

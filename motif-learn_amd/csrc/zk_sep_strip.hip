@@ -160,9 +160,6 @@ __global__ __launch_bounds__(256, 2) void zk_frame_strip_kernel(
 //   * the code is software-pipelined by hand: block j waits for ITS operands (requested by block j + 1), requests those
 //     of block j - 1 into the other register set (static: sets alternate with j), then does its 11 f64 operations.
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef ZK_STRIP2
-#define ZK_STRIP2 1
-#endif
 
 // Operand requests the compiler cannot move: the pipeline below relies on a block's operands being REQUESTED one block
 // ahead.  Written as plain loads, LLVM sinks each request into the block that uses it (it is dead on the path that leaves
@@ -182,18 +179,6 @@ typedef double zk_v4d __attribute__((ext_vector_type(4)));
 typedef double zk_v2d __attribute__((ext_vector_type(2)));
 template <int N>
 struct zk_sgpr_row;  // N doubles of one table row in SGPRs
-#ifdef ZK_EXP_HALF_TABLE  // timing experiment only (wrong moments): half the scalar bytes per column pair, every value used twice
-template <>
-struct zk_sgpr_row<8> {
-  zk_v4d v;
-  template <int OFF>
-  __device__ __forceinline__ void request(const ZK_CONST double* p, double& after) {
-    asm volatile("s_load_dwordx8 %0, %2, %3" : "=s"(v), "+v"(after) : "s"(p), "n"(OFF));
-  }
-  __device__ __forceinline__ void wait(double& a, double& b) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(v), "+v"(a), "+v"(b)); }
-  __device__ __forceinline__ double operator[](int i) const { return v[i & 3]; }
-};
-#else
 template <>
 struct zk_sgpr_row<8> {
   zk_v8d v;
@@ -204,7 +189,6 @@ struct zk_sgpr_row<8> {
   __device__ __forceinline__ void wait(double& a, double& b) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(v), "+v"(a), "+v"(b)); }
   __device__ __forceinline__ double operator[](int i) const { return v[i]; }
 };
-#endif
 template <>
 struct zk_sgpr_row<6> {
   zk_v4d a;
@@ -444,8 +428,8 @@ __global__ __launch_bounds__(256, 2) void zk_frame_strip2_kernel(
 // profiles/r04_strip_trace.txt: the wave slots of zk_frame_strip2_kernel<8> are occupied 0.96-0.98 of the kernel's
 // duration -- no dispatch gap -- and its 0.73 VALU-busy is the scalar data path: a sweep block needs 8 fresh SGPR doubles
 // (64 B) per 11 f64 operations, eight waves of a CU ask for 5.8 B per clock where the scalar cache delivers ~5.6,
-// i.e. the 0.7 FMA per clock a CU gets from once-used scalars.  Fetching half the table row (ZK_EXP_HALF_TABLE, wrong
-// results, timing only) took the wave's life from 96.1 k to 85.0 k clocks.  So the sweeps here take NO scalar operand:
+// i.e. the 0.7 FMA per clock a CU gets from once-used scalars.  Fetching half the table row (a timing-only build, wrong
+// results) took the wave's life from 96.1 k to 85.0 k clocks.  So the sweeps here take NO scalar operand:
 //   * the whole x table of the window -- P_1 .. P_nmax of the 16 column pairs, 128 doubles -- lives in 8 VGPR pairs, lane
 //     e of every row of 16 lanes holding entry e (two columns x 8 degrees per register pair), loaded once per workgroup;
 //     a block multiplies with `v_fmac_f64_dpp ... row_newbcast:e` (the one DPP control the FP64 pipe accepts: lane e of
@@ -477,9 +461,6 @@ __global__ __launch_bounds__(256, 2) void zk_frame_strip2_kernel(
 // of scalar-operand delivery (512 B at ~5.6 B per clock) and 64 clocks of LDS reads.  Kept as an opt-in (ZK_STRIP_V3=1 in the environment, parity-tested) and as the record of
 // what bounds the round-3 kernel; ZK_PATH_AUTO stays on zk_frame_strip2_kernel.
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef ZK_STRIP3
-#define ZK_STRIP3 1
-#endif
 
 template <int E>  // acc += T[lane E of my row of 16] * x
 __device__ __forceinline__ void zk_fmac_bcast(double& acc, double t, double x) {
@@ -672,13 +653,12 @@ template <int NMAX, typename T>
 int launch_one(zk_plan* p, const void* in, int64_t H, int64_t W, int64_t row0, int64_t n_rows, double* out,
                hipStream_t s) {
   const zk_sep_tables* t = p->sep;
-  static const bool v1 = getenv("ZK_STRIP_V1") != nullptr;  // A/B runs: the round-2 kernel
-  const bool v3 = getenv("ZK_STRIP_V3") != nullptr;  // opt-in: round 4's kernel with the x table in VGPR lanes (see above)
   if constexpr (NMAX <= 8) {
-    if (ZK_STRIP3 && !v1 && v3 && t->d_strip_rows && p->size % 2 == 0 && p->size <= 32)
+    // opt-in: round 4's kernel with the x table in VGPR lanes (see above)
+    if (zk_switch_on(ZK_STRIP_V3) && t->d_strip_rows && p->size % 2 == 0 && p->size <= 32)
       return launch_strip3<NMAX, T>(p, in, H, W, row0, n_rows, out, s);
   }
-  if (ZK_STRIP2 && !v1 && t->d_strip_rows && p->size % 2 == 0) {
+  if (t->d_strip_rows && p->size % 2 == 0) {
     if (p->size <= 32) return launch_strip2<NMAX, T, 16>(p, in, H, W, row0, n_rows, out, s);
     return launch_strip2<NMAX, T, 32>(p, in, H, W, row0, n_rows, out, s);
   }
@@ -723,7 +703,7 @@ bool zk_sep_strip_available(const zk_plan* p, int dtype) {
   (void)dtype;
   if (!zk_sep_frame_available(p, dtype) || p->sep->kernel_nmax > 12 || !p->sep->d_pfull || !p->sep->d_cmin) return false;
   // n_max 9 - 12: only the two-pass form exists (even window sizes, zk_sep.hip builds its tables)
-  static const bool no12 = getenv("ZK_STRIP_NO_SPLIT") != nullptr;  // A/B runs: the one-output kernel
+  const bool no12 = zk_switch_on(ZK_STRIP_NO_SPLIT);  // A/B runs: the one-output kernel
   if (p->sep->kernel_nmax > 8 && (no12 || !p->sep->d_psplit || !p->sep->d_strip_rows || p->size % 2 != 0)) return false;
   // two workgroups per CU must fit (two waves per SIMD is what the kernel is compiled for): K <= 65.  Beyond,
   // the one-output kernel is ahead again (72 px: 4.7 vs 5.0 ms per 2048^2).

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import sys
 import threading
 import weakref
 from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_int32, c_int64, c_void_p
@@ -220,6 +221,23 @@ def device_count():
     return n
 
 
+def require_device():
+    if device_count() == 0:
+        raise RuntimeError("no HIP device visible: mtflearn_amd computes on MI355X only (there is no CPU fallback)")
+
+
+def default_device():
+    """GPU of a call that names none: ``MTFLEARN_AMD_DEVICE``, else ``LOCAL_RANK``, else torch's current device when
+    torch is already imported and has initialised HIP, else 0."""
+    for var in ("MTFLEARN_AMD_DEVICE", "LOCAL_RANK"):
+        if os.environ.get(var, "") != "":
+            return int(os.environ[var])
+    torch = sys.modules.get("torch")
+    if torch is not None and torch.cuda.is_available() and torch.cuda.is_initialized():
+        return int(torch.cuda.current_device())
+    return 0
+
+
 class ClockMonitor:
     """``with ClockMonitor(device) as m: ...`` -- the mean shader clock (``m.ghz``) over the ``m.ms`` the block took, sampled by
     one resident wave (``zk_clock_monitor_start / _stop``).  Inside the block synchronise the STREAM the work runs on, not
@@ -326,9 +344,7 @@ class Plan:
         self.device = int(device)
         n32 = np.ascontiguousarray(n, dtype=np.int32)
         m32 = np.ascontiguousarray(m, dtype=np.int32)
-        if device_count() == 0:
-            raise RuntimeError("no HIP device visible: mtflearn_amd computes on MI355X only "
-                               "(there is no CPU fallback)")
+        require_device()
         handle = c_void_p()
         check(lib.zk_plan_create(self.size, self.n_poly, n32.ctypes.data_as(POINTER(c_int32)),
                                  m32.ctypes.data_as(POINTER(c_int32)),

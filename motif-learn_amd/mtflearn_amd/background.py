@@ -22,7 +22,6 @@ from ctypes import c_void_p
 import numpy as np
 
 from . import _native
-from .features.peaks import _device
 from .features.zernike_polys import ZPs
 
 __all__ = [
@@ -98,17 +97,12 @@ def _baseline_weights(sigma):
 
 
 # ----------------------------------------------------------------------------------------------- device calls
-def _require_device(lib):
-    if _native.device_count() == 0:
-        raise RuntimeError("no HIP device visible: mtflearn_amd computes on MI355X only (there is no CPU fallback)")
-
-
 def _run(method, image, param, clip, want_residual):
     """One ``zk_background_*`` call on a host image: returns ``(residual or None, background)`` in the dtypes the reference
     returns.  The five device formats cross PCIe as they are; any other dtype is widened the way ``ZPs`` widens it, and
     the result (and the residual, in the image's own dtype) is taken back to it on the host."""
     lib = _native.load()
-    _require_device(lib)
+    _native.require_device()
     operand = ZPs._device_operand(image)
     code = _native.dtype_code(operand.dtype)
     h, w = operand.shape
@@ -117,7 +111,7 @@ def _run(method, image, param, clip, want_residual):
     background = np.empty((h, w), dtype=out_dtype)
     residual = np.empty((h, w), dtype=out_dtype) if (want_residual and (native or method == "baseline")) else None
     res_ptr = residual.ctypes.data_as(c_void_p) if residual is not None else None
-    args = (_device(), operand.ctypes.data_as(c_void_p), code, h, w)
+    args = (_native.default_device(), operand.ctypes.data_as(c_void_p), code, h, w)
     if method == "opening":
         _native.check(lib.zk_background_opening(*args, param[0], param[1], int(bool(clip)), background.ctypes.data_as(c_void_p),
                                                 res_ptr), "zk_background_opening")

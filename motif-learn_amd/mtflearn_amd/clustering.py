@@ -27,7 +27,6 @@ import os
 import numpy as np
 
 from . import _native
-from .features.pickers import _device
 
 __all__ = ["kmeans_lbs", "gmm_lbs", "sort_lbs", "seg_lbs", "normalize_xy", "DeviceRows", "kmeans_fit", "gmm_fit_predict",
            "gather_labels"]
@@ -44,9 +43,8 @@ class DeviceRows:
 
     def __init__(self, X=None, device=None, _adopt=None):
         self._lib = _native.load()
-        if _native.device_count() == 0:
-            raise RuntimeError("no HIP device visible: mtflearn_amd computes on MI355X only (there is no CPU fallback)")
-        self.device = _device() if device is None else int(device)
+        _native.require_device()
+        self.device = _native.default_device() if device is None else int(device)
         handle = c_void_p()
         if _adopt is not None:
             ptr, n, d = _adopt
@@ -160,8 +158,9 @@ class DeviceRows:
         d1 = self.n_features + 1
         n = 1 if count is None else int(count)
         out = np.empty((n, d1, d1))
-        # the matrix-core pass takes 2 .. 47 features (and ZK_WGRAM_VALU forces the vector kernel for A/B runs): otherwise three
-        per_pass = 8 if 2 <= self.n_features <= 47 and not os.environ.get("ZK_WGRAM_VALU") else 3
+        # the matrix-core pass takes 2 .. 47 features, the vector kernel three components; ZK_WGRAM_VALU forces the vector kernel
+        # (A/B runs), and the library reads it at every call by the same rule (set at all), so the two sides always agree
+        per_pass = 8 if 2 <= self.n_features <= 47 and "ZK_WGRAM_VALU" not in os.environ else 3
         for c0 in range(0, n, per_pass):
             cc = min(per_pass, n - c0)
             _native.check(self._lib.zk_gmm_moments(self._h, int(component) + c0, cc, _p(shift), _p(out[c0:c0 + cc])), "zk_gmm_moments")

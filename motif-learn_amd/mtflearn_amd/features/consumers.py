@@ -21,7 +21,6 @@ from ctypes import POINTER, byref, c_double, c_void_p
 import numpy as np
 
 from .. import _native
-from .pickers import _device
 
 __all__ = ["pca"]
 
@@ -88,9 +87,8 @@ def pca(X, n_components=2, reconstruct=False, comm=None):
     if n < 2:
         raise ValueError("PCA needs at least two samples")
     lib = _native.load()
-    if _native.device_count() == 0:
-        raise RuntimeError("no HIP device visible: mtflearn_amd computes on MI355X only (there is no CPU fallback)")
-    dev = _device()
+    _native.require_device()
+    dev = _native.default_device()
     gram = np.empty((d + 1, d + 1), dtype=np.float64)
     x_dev = c_void_p()
     _native.check(lib.zk_gram(dev, X.ctypes.data_as(POINTER(c_double)), n, d, gram.ctypes.data_as(POINTER(c_double)),

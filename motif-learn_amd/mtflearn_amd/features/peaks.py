@@ -17,18 +17,6 @@ from .zernike_polys import ZPs
 __all__ = ["local_max"]
 
 
-def _device():
-    import os
-    import sys
-    for var in ("MTFLEARN_AMD_DEVICE", "LOCAL_RANK"):
-        if os.environ.get(var, "") != "":
-            return int(os.environ[var])
-    torch = sys.modules.get("torch")
-    if torch is not None and torch.cuda.is_available() and torch.cuda.is_initialized():
-        return int(torch.cuda.current_device())
-    return 0
-
-
 def _comparison_threshold(dtype, threshold):
     """``t`` (a Python float) such that ``float64(v) > t`` equals NumPy 2's ``v > threshold`` for every value ``v`` of
     ``dtype``.  NumPy compares in the promoted type (NEP 50: a Python scalar takes the array's kind where it can), so
@@ -85,12 +73,11 @@ def local_max(image, min_distance, threshold=None):
     r = _check_distance(min_distance)
     has_t, t = (0, 0.0) if threshold is None else (1, _comparison_threshold(image.dtype, threshold))
     lib = _native.load()
-    if _native.device_count() == 0:
-        raise RuntimeError("no HIP device visible: mtflearn_amd computes on MI355X only (there is no CPU fallback)")
+    _native.require_device()
     operand = ZPs._device_operand(image)
     code = _native.dtype_code(operand.dtype)
     h, w = operand.shape
-    device = _device()
+    device = _native.default_device()
     ptr = operand.ctypes.data_as(c_void_p)
     capacity = max(1024, h * w // 8)                   # kept points of a real frame: a few % of its pixels
     out = np.empty((capacity, 2), dtype=np.int64)

@@ -36,18 +36,6 @@ __all__ = ["standardize_image", "autocorrelation", "radial_profile", "find_highe
            "estimate_n_max", "_get_cumulative_energy"]
 
 
-def _device():
-    import os
-    import sys
-    for var in ("MTFLEARN_AMD_DEVICE", "LOCAL_RANK"):
-        if os.environ.get(var, "") != "":
-            return int(os.environ[var])
-    torch = sys.modules.get("torch")
-    if torch is not None and torch.cuda.is_available() and torch.cuda.is_initialized():
-        return int(torch.cuda.current_device())
-    return 0
-
-
 def _operand(image):
     """C-contiguous float32 / float64 image (what NumPy's float64 promotion would compute on, see ZPs)."""
     image = np.asarray(image)
@@ -73,12 +61,11 @@ def _call(code, what):
 
 def _autocorr_mean(image, window, origins, standardize):
     lib = _native.load()
-    if _native.device_count() == 0:
-        raise RuntimeError("no HIP device visible: mtflearn_amd computes on MI355X only (there is no CPU fallback)")
+    _native.require_device()
     img = _operand(image)
     org = _origins(origins)
     out = np.empty((window, window), dtype=np.float64)
-    _call(lib.zk_autocorr_mean(_device(), img.ctypes.data_as(c_void_p), _native.dtype_code(img.dtype), img.shape[0], img.shape[1],
+    _call(lib.zk_autocorr_mean(_native.default_device(), img.ctypes.data_as(c_void_p), _native.dtype_code(img.dtype), img.shape[0], img.shape[1],
                                window, org.ctypes.data_as(POINTER(c_int32)), org.shape[0], int(bool(standardize)),
                                out.ctypes.data_as(POINTER(c_double))), "zk_autocorr_mean")
     return out
@@ -117,10 +104,9 @@ def radial_profile(data, center=None, method="max"):
     h, w = data.shape
     ci, cj = (h // 2, w // 2) if center is None else (int(center[0]), int(center[1]))
     lib = _native.load()
-    if _native.device_count() == 0:
-        raise RuntimeError("no HIP device visible: mtflearn_amd computes on MI355X only (there is no CPU fallback)")
+    _native.require_device()
     out = np.empty(int(lib.zk_polar_radii(h, w)), dtype=np.float64)
-    _call(lib.zk_polar_profile(_device(), data.ctypes.data_as(POINTER(c_double)), 1, h, w, ci, cj, methods[method],
+    _call(lib.zk_polar_profile(_native.default_device(), data.ctypes.data_as(POINTER(c_double)), 1, h, w, ci, cj, methods[method],
                                out.ctypes.data_as(POINTER(c_double))), "zk_polar_profile")
     return out
 
@@ -178,11 +164,10 @@ def denoise_fft(image, p):
     if not (0 < p <= 1):
         raise ValueError("Fraction p must be between 0 and 1.")
     lib = _native.load()
-    if _native.device_count() == 0:
-        raise RuntimeError("no HIP device visible: mtflearn_amd computes on MI355X only (there is no CPU fallback)")
+    _native.require_device()
     img = _operand(image)
     out = np.empty(img.shape, dtype=np.float64)
-    _call(lib.zk_denoise_fft(_device(), img.ctypes.data_as(c_void_p), _native.dtype_code(img.dtype), img.shape[0], img.shape[1],
+    _call(lib.zk_denoise_fft(_native.default_device(), img.ctypes.data_as(c_void_p), _native.dtype_code(img.dtype), img.shape[0], img.shape[1],
                              float(p), out.ctypes.data_as(POINTER(c_double))), "zk_denoise_fft")
     return out
 
@@ -194,14 +179,13 @@ def estimate_sigma(image):
     (``zk_wavelet_sigma``).  Restated from scikit-image / PyWavelets (not installed here): **parity-unpinned**; it only
     decides which branch ``estimate_n_max`` takes (``sigma > t``)."""
     lib = _native.load()
-    if _native.device_count() == 0:
-        raise RuntimeError("no HIP device visible: mtflearn_amd computes on MI355X only (there is no CPU fallback)")
+    _native.require_device()
     img = _operand(image)
     if img.ndim != 2:
         raise ValueError("estimate_sigma needs a 2-D image")
     from ctypes import byref
     sigma = c_double()
-    _call(lib.zk_wavelet_sigma(_device(), img.ctypes.data_as(c_void_p), _native.dtype_code(img.dtype), img.shape[0], img.shape[1],
+    _call(lib.zk_wavelet_sigma(_native.default_device(), img.ctypes.data_as(c_void_p), _native.dtype_code(img.dtype), img.shape[0], img.shape[1],
                                byref(sigma)), "zk_wavelet_sigma")
     return float(sigma.value)
 
@@ -233,14 +217,13 @@ def _window_1d(window_type, size):
 
 def _power_spectra(image, size, origins, window_type):
     lib = _native.load()
-    if _native.device_count() == 0:
-        raise RuntimeError("no HIP device visible: mtflearn_amd computes on MI355X only (there is no CPU fallback)")
+    _native.require_device()
     img = _operand(image)
     org = _origins(origins)
     win = _window_1d(window_type, size)
     win_p = None if win is None else np.ascontiguousarray(win, dtype=np.float64).ctypes.data_as(POINTER(c_double))
     out = np.empty((org.shape[0], size, size), dtype=np.float64)
-    _call(lib.zk_power_spectra(_device(), img.ctypes.data_as(c_void_p), _native.dtype_code(img.dtype), img.shape[0], img.shape[1],
+    _call(lib.zk_power_spectra(_native.default_device(), img.ctypes.data_as(c_void_p), _native.dtype_code(img.dtype), img.shape[0], img.shape[1],
                                size, org.ctypes.data_as(POINTER(c_int32)), org.shape[0], win_p,
                                out.ctypes.data_as(POINTER(c_double))), "zk_power_spectra")
     return out
@@ -252,7 +235,7 @@ def _radial_profiles(stack):
     stack = np.ascontiguousarray(stack, dtype=np.float64)
     n, h, w = stack.shape
     out = np.empty((n, int(lib.zk_polar_radii(h, w))), dtype=np.float64)
-    _call(lib.zk_polar_profile(_device(), stack.ctypes.data_as(POINTER(c_double)), n, h, w, -1, -1, 1,
+    _call(lib.zk_polar_profile(_native.default_device(), stack.ctypes.data_as(POINTER(c_double)), n, h, w, -1, -1, 1,
                                out.ctypes.data_as(POINTER(c_double))), "zk_polar_profile")
     return out
 

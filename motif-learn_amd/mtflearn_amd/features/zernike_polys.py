@@ -25,8 +25,6 @@ staging memory.  Large results are page-locked arrays out of a recycling pool (`
 """
 from __future__ import annotations
 
-import os
-import sys
 import threading
 import warnings
 
@@ -128,13 +126,7 @@ class ZPs(BaseEstimator, TransformerMixin):
     def _pick_device(self):
         if getattr(self, "_device", None) is not None:
             return self._device
-        for var in ("MTFLEARN_AMD_DEVICE", "LOCAL_RANK"):
-            if os.environ.get(var, "") != "":
-                return int(os.environ[var])
-        torch = sys.modules.get("torch")
-        if torch is not None and torch.cuda.is_available() and torch.cuda.is_initialized():
-            return int(torch.cuda.current_device())
-        return 0
+        return _native.default_device()
 
     def to_device(self, index):
         """Bind this transformer to GPU ``index`` (drops a plan created on another device)."""
