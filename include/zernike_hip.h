@@ -437,6 +437,57 @@ int zk_background_baseline_dev(int device, const void* image_dev, int dtype, int
                                void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Patch-SVD / patch-PCA denoising: the device side of the reference's denoise/ subpackage (_denoise_svd.py,
+ * _denoise_svd_memory_view.py), the step ahead of background removal.  No plan involved.
+ *
+ * A is the implicit (N, D) matrix whose row w = a * n_cols + b is the patch_h x patch_w window of the frame at origin
+ * (row_origins[a], col_origins[b]), flattened row-major: D = patch_h * patch_w, N = n_rows * n_cols.  The origin lists are
+ * HOST arrays in every form, strictly ascending, every window inside the frame (checked); A is never formed.  image: dtype
+ * ZK_F32 / ZK_F64 / ZK_U8 / ZK_U16 / ZK_I16, C-contiguous (height, width), widened to float64 as it is read; every other
+ * operand and result is float64, C-contiguous.
+ *
+ *   zk_windows_apply        Y (N, n_columns) = (A - 1 mean^T) Q, Q (D, n_columns); mean (D) may be NULL (no centring).
+ *   zk_windows_apply_t      Z (D, n_columns) = A^T Y, Y (N, n_columns).
+ *   zk_windows_moments      over the DENSE grid (every origin, step 1): mean (D) of the windows and their covariance
+ *                           cov (D, D) = (A - 1 mean^T)^T (A - 1 mean^T) / (N - 1) (divided by 1 when N == 1), computed from
+ *                           the products of the mean-centred frame with its own shifts (about 2 D height width products).
+ *                           Patches of at most 48 x 48.
+ *   zk_windows_reconstruct  out (height, width) = sum over the windows w on each pixel of (Y[w, :] V + mean)[d] / (number
+ *                           of windows on the pixel), d the pixel's place in window w; Y (N, n_components), V (n_components, D);
+ *                           mean may be NULL.  With V == NULL, Y is an explicit (N, patch_h, patch_w) batch of patches and
+ *                           n_components is ignored.  The windows of a pixel are added rows of the grid first, ascending (the
+ *                           reference's loop order); a pixel under no window is 0 / 0 = NaN.
+ *
+ * No atomics: every sum has a fixed order, two calls give the same bits.  The _dev forms take device pointers for the image,
+ * the operands and the results, run on hip_stream and synchronise it before they return (their tables and scratch are
+ * released); nothing but the origin lists crosses from the host.
+ * ------------------------------------------------------------------------------------------------------ */
+int zk_windows_apply(int device, const void* image_host, int dtype, int64_t height, int64_t width, int64_t patch_h, int64_t patch_w,
+                     const int32_t* row_origins, int64_t n_rows, const int32_t* col_origins, int64_t n_cols, const double* Q_host,
+                     int64_t n_columns, const double* mean_host, double* Y_host);
+int zk_windows_apply_dev(int device, const void* image_dev, int dtype, int64_t height, int64_t width, int64_t patch_h, int64_t patch_w,
+                         const int32_t* row_origins /* host */, int64_t n_rows, const int32_t* col_origins /* host */, int64_t n_cols,
+                         const double* Q_dev, int64_t n_columns, const double* mean_dev, double* Y_dev, void* hip_stream);
+int zk_windows_apply_t(int device, const void* image_host, int dtype, int64_t height, int64_t width, int64_t patch_h, int64_t patch_w,
+                       const int32_t* row_origins, int64_t n_rows, const int32_t* col_origins, int64_t n_cols, const double* Y_host,
+                       int64_t n_columns, double* Z_host);
+int zk_windows_apply_t_dev(int device, const void* image_dev, int dtype, int64_t height, int64_t width, int64_t patch_h,
+                           int64_t patch_w, const int32_t* row_origins /* host */, int64_t n_rows,
+                           const int32_t* col_origins /* host */, int64_t n_cols, const double* Y_dev, int64_t n_columns,
+                           double* Z_dev, void* hip_stream);
+int zk_windows_moments(int device, const void* image_host, int dtype, int64_t height, int64_t width, int64_t patch_h, int64_t patch_w,
+                       double* mean_host, double* cov_host);
+int zk_windows_moments_dev(int device, const void* image_dev, int dtype, int64_t height, int64_t width, int64_t patch_h,
+                           int64_t patch_w, double* mean_dev, double* cov_dev, void* hip_stream);
+int zk_windows_reconstruct(int device, int64_t height, int64_t width, int64_t patch_h, int64_t patch_w, const int32_t* row_origins,
+                           int64_t n_rows, const int32_t* col_origins, int64_t n_cols, const double* Y_host, int64_t n_components,
+                           const double* V_host, const double* mean_host, double* out_host);
+int zk_windows_reconstruct_dev(int device, int64_t height, int64_t width, int64_t patch_h, int64_t patch_w,
+                               const int32_t* row_origins /* host */, int64_t n_rows, const int32_t* col_origins /* host */,
+                               int64_t n_cols, const double* Y_dev, int64_t n_components, const double* V_dev,
+                               const double* mean_dev, double* out_dev, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * First downstream consumer of the moment matrix: the two streaming passes of
  *   pca(X, n_components)   reference features/_dimension_reduction.py:3-6 (sklearn PCA(n).fit_transform(X))
  * on a float64 matrix X (N, D), D <= 127 (45 moments at n_max 8).

@@ -3,6 +3,7 @@
 
   notebook 2 (batch):  key points -> patches -> ZPs.fit_transform(patches) -> rotation-invariant |Z_nm| -> rot_maps
   notebook 3 (dense):  ZPs.fit_transform(frame) -> rot_maps / mirror_map / |Z_nm| maps
+  resident chain:      frame on the device -> denoise -> background removal -> local maxima -> moments at them
 
 Only the import line differs from the reference (`from mtflearn import ZPs`).  Needs an MI355X.
 Run:  python motif-learn_amd/examples/notebook_flows.py
@@ -49,6 +50,20 @@ def main():
           f" max |rot - host rot| = {np.nanmax(np.abs(maps['rot_maps'] - rot)):.2e}")
     valid = zf.valid_mask
     print("         valid (un-padded) positions:", int(valid.sum()), "of", valid.size)
+
+    # ---- the front of the chain, device-resident: the notebooks' input frame is a denoised one -------------------
+    from mtflearn_amd import _native
+    from mtflearn_amd.distributed import (denoise_svd_device, local_max_device, points_moments_device,
+                                          remove_background_device)
+    t = time.perf_counter()
+    dev = _native.DeviceArray.from_numpy(frame)                            # the only trip of the frame over PCIe
+    clean = denoise_svd_device(dev, size, n_components=8)                  # reference: denoise_svd(frame, 32, 8)
+    residual, _ = remove_background_device(clean, "opening", 3 * size + 1)
+    peaks = local_max_device(residual, 5.0)                                # (N, 2) int32 (x, y) on the device
+    keep = peaks.numpy()
+    keep = keep[(keep.min(axis=1) >= size // 2) & (keep[:, 0] < 1024 - size // 2) & (keep[:, 1] < 1024 - size // 2)]
+    moments = points_moments_device(zps._device_plan(), clean, _native.DeviceArray.from_numpy(keep.astype(np.int32)))
+    print(f"chain  : denoise -> background -> local_max -> moments {moments.shape} in {1e3 * (time.perf_counter() - t):.1f} ms")
 
 
 if __name__ == "__main__":

@@ -4,11 +4,13 @@
 (reference ``mtflearn/__init__.py:37-38``).  Only this path and the rows SURVEY 8(f) names around it are provided
 (``mtflearn_amd.features``: parameter pickers, ``pca``; ``mtflearn_amd.clustering``: ``kmeans_lbs`` / ``gmm_lbs`` /
 ``sort_lbs``; ``mtflearn_amd.manifold``: ``ForceGraph8``; ``mtflearn_amd.background``: ``estimate_background_*`` /
-``remove_background_*`` and their parameter picker); see DESIGN.md.
+``remove_background_*`` and their parameter picker; ``mtflearn_amd.denoise``: ``denoise_svd`` / ``DenoiseSVD`` /
+``denoise_svd_memory_view``, the reference's other two top-level names); see DESIGN.md.
 """
 __version__ = "0.1.0"
 
 from .features import ZPs, zmoments
 from . import features
+from ._denoise_svd import DenoiseSVD, denoise_svd
 
-__all__ = ["ZPs", "zmoments", "features"]
+__all__ = ["ZPs", "zmoments", "features", "denoise_svd", "DenoiseSVD"]

@@ -116,6 +116,20 @@ SYMBOLS = {
                                        c_int, c_void_p, c_void_p]),
     "zk_background_baseline_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                            c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "zk_windows_apply": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                 c_void_p, c_int64, c_void_p, c_void_p]),
+    "zk_windows_apply_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                     c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "zk_windows_apply_t": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                   c_void_p, c_int64, c_void_p]),
+    "zk_windows_apply_t_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+                                       c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "zk_windows_moments": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "zk_windows_moments_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "zk_windows_reconstruct": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                       c_int64, c_void_p, c_void_p, c_void_p]),
+    "zk_windows_reconstruct_dev": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                           c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "zk_gram": (c_int, [c_int, POINTER(c_double), c_int64, c_int, POINTER(c_double), POINTER(c_void_p)]),
     "zk_project": (c_int, [c_int, c_void_p, c_int64, c_int, POINTER(c_double), POINTER(c_double), c_int, POINTER(c_double),
                            c_int]),

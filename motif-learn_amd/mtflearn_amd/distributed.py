@@ -31,7 +31,8 @@ import numpy as np
 from . import _native
 
 __all__ = ["shard_bounds", "one_gpu_rank_env", "RcclComm", "TorchComm", "DeviceCompute", "patch_moments_device",
-           "frame_moments_device", "frame_maps_device", "local_max_device", "points_moments_device", "remove_background_device", "sharded_patch_moments", "sharded_frame_moments",
+           "frame_moments_device", "frame_maps_device", "local_max_device", "points_moments_device", "remove_background_device", "denoise_svd_device",
+           "denoise_svd_memory_view_device", "sharded_patch_moments", "sharded_frame_moments",
            "sharded_frame_maps", "sharded_frames_moments"]
 
 
@@ -363,6 +364,40 @@ def remove_background_device(image, method, parameter, clip=True, **method_kw):
         _native.check(lib.zk_background_baseline_dev(*args, wy.ctypes.data_as(c_void_p), len(wy) - 1, wx.ctypes.data_as(c_void_p),
                                                      len(wx) - 1, iters, *outs), "zk_background_baseline_dev")
     return residual, background
+
+
+def _device_frame(image, what):
+    if len(image.shape) != 2:
+        raise ValueError(f"{what} needs a 2D image, not {len(image.shape)}-D")
+    if not image.is_cuda:
+        raise ValueError("image must live on the GPU")
+    if not _is_native(image) and not image.is_contiguous():
+        image = image.contiguous()
+    _image_code(image)
+    return image
+
+
+def denoise_svd_device(image, patch_size, n_components, extraction_step=None, return_s=False):
+    """:func:`mtflearn_amd.denoise_svd` of a frame resident on the GPU (a torch tensor or a
+    :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` of float32 / float64 / uint8 / uint16 / int16).  Returns the float64
+    clean frame as a device array of the same kind (and the singular values, a host array, with ``return_s``): the frame and
+    the result never cross to the host, only the thin factors of the randomized SVD do.  Runs on torch's current stream."""
+    from ._denoise_svd import _check_components, _denoise_svd_device, _svd_arguments
+    image = _device_frame(image, "denoise_svd_device")
+    patch, _, ii, jj = _svd_arguments(tuple(int(v) for v in image.shape), patch_size, extraction_step)
+    n_components = _check_components(n_components)
+    clean, s = _denoise_svd_device(image, patch, ii, jj, n_components)
+    return (clean, s) if return_s else clean
+
+
+def denoise_svd_memory_view_device(image, patch_size, n_components=None, threshold=0.9):
+    """:func:`mtflearn_amd.denoise.denoise_svd_memory_view` of a frame resident on the GPU (as :func:`denoise_svd_device`).
+    Returns ``(recon, explained_variance_ratio, n_components)`` with ``recon`` a float64 device array of the image's kind; the
+    ``(p^2, p^2)`` covariance and the eigenvectors are all that crosses to the host and back."""
+    from .denoise import _memory_view_device, _memory_view_patch
+    image = _device_frame(image, "denoise_svd_memory_view_device")
+    p = _memory_view_patch(tuple(int(v) for v in image.shape), patch_size)
+    return _memory_view_device(image, p, n_components, threshold)
 
 
 # ---------------------------------------------------------------------------------------------------------
