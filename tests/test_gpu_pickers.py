@@ -108,19 +108,43 @@ def test_estimate_patch_size_end_to_end(pg, po, pk, seed, window):
     assert 18 <= got <= 23             # honeycomb lattice with bond length 12 px: lattice constant 12 sqrt(3) = 20.8
 
 
+def test_estimate_patch_size_non_square_image(pg, po, pk):
+    """h != w: the default window is h // 2 and the x draws run to w - window."""
+    img = pg["noisy_192"][:, :160]
+    np.random.seed(3)
+    got = pk.estimate_patch_size(img)
+    np.random.seed(3)
+    ref = po.estimate_patch_size(img.astype(np.float64))
+    assert got == ref and got is not None
+    assert 18 <= got <= 23
+
+
 def test_estimate_n_max_end_to_end(pg, po, pk):
-    for img, seed in ((pg["noisy_192"], 1), (pg["lattice_192"], 2)):               # noisy image / clean image branch
-        np.random.seed(seed)
-        if pk.estimate_sigma(img) > 0.01:
-            got = pk.estimate_n_max(img, 32, n_samples=20)
+    for patch_size in (32, 64):        # at 32 every per-sample value sits on the lower clamp 12; at 64 they lie inside it
+        for img, seed in ((pg["noisy_192"], 1), (pg["lattice_192"], 2)):           # noisy image / clean image branch
             np.random.seed(seed)
-            ref = po.estimate_n_max(img, 32, n_samples=20)
-            assert got == ref
-        else:
-            got = pk.estimate_n_max(img, 32, n_samples=20)                         # adds unseeded noise: range check only
-        assert 12 <= got <= 16
+            if pk.estimate_sigma(img) > 0.01:
+                got = pk.estimate_n_max(img, patch_size, n_samples=20)
+                np.random.seed(seed)
+                ref = po.estimate_n_max(img, patch_size, n_samples=20)
+                assert got == ref
+            else:
+                got = pk.estimate_n_max(img, patch_size, n_samples=20)             # adds unseeded noise: range check only
+            assert 12 <= got <= patch_size // 2
     got = pk.estimate_n_max_from_patch(pg["noisy_192"][:64, :64].astype(np.float64), p=0.05)
     assert 12 <= got <= 32
+
+
+def test_estimate_n_max_per_sample_values_inside_the_clamp(pg, po, pk):
+    """Sample by sample, not only the median, at a patch size where the answer is not the clamp: at least half of the
+    oracle's values lie strictly between 12 and patch_size // 2, so they are what the spectra and profiles gave."""
+    img, patch_size = pg["noisy_192"], 64
+    np.random.seed(1)
+    ref = [int(v) for v in po.n_max_samples(img, patch_size, n_samples=20)]
+    assert sum(12 < v < patch_size // 2 for v in ref) >= len(ref) // 2
+    np.random.seed(1)
+    got = [int(v) for v in pk._n_max_samples(img, patch_size, 20, 0.01, 0.01)]
+    assert got == ref
 
 
 def test_wavelet_sigma_device_equals_oracle(pg, po, pk):

@@ -71,6 +71,61 @@ def test_oracle_wavelet_noise_estimate_tracks_sigma(pg, po):
     assert po.estimate_sigma(pg["lattice_192"]) < 0.01 < po.estimate_sigma(pg["noisy_192"])
 
 
+POLAR_SHAPES = [(1, 1), (1, 9), (9, 1), (2, 2), (7, 5), (257, 131), (181, 181), (182, 182), (1024, 1024)]
+
+
+@pytest.mark.parametrize("shape", POLAR_SHAPES, ids=lambda s: "%dx%d" % s)
+def test_scipy_warp_polar_agrees_with_restated_warp_polar(po, shape):
+    """tests/pickers_reference.py resamples with scipy.ndimage.map_coordinates, the oracle with its own floor / ceil
+    bilinear code; neither is scikit-image (not installed), but an error would have to be made twice, differently.
+    Measured: at most 1e-13 up to 64 x 64 (|data| 1.5 to 3), 5e-13 at 257 x 131, 2.3e-12 at 1024 x 1024."""
+    import pickers_reference as pr
+    rng = np.random.default_rng(21)
+    h, w = shape
+    tol = 1e-11 if h * w > 257 * 257 else 1e-12
+    for data in (rng.random(shape) + 0.5, rng.standard_normal(shape)):        # fill value 0 outside / inside the range
+        for center in (None, (0, 0), (h - 1, w - 1), (h // 3, (w // 2 + 1) % w)):
+            got = pr.warp_polar_ref(data, center)
+            ref = po.warp_polar_linear(data, (h // 2, w // 2) if center is None else center)
+            assert got.shape == ref.shape == (360, pr.polar_radii(h, w))
+            np.testing.assert_allclose(got, ref, rtol=0, atol=tol)
+
+
+def test_direct_lag_sum_agrees_with_oracle_autocorrelation(po):
+    import pickers_reference as pr
+    rng = np.random.default_rng(22)
+    img = rng.standard_normal((131, 260))
+    for ws in (1, 2, 3, 8, 31, 33, 50):
+        origins = [(0, 0), (131 - ws, 260 - ws), (0, 260 - ws), (131 - ws, 0), (17, 101)]
+        for standardize in (True, False) if ws > 1 else (False,):
+            got = pr.autocorr_mean_ref(img, ws, origins, standardize)
+            ref = po.autocorr_mean(img, ws, origins, standardize)
+            np.testing.assert_allclose(got, ref, rtol=0, atol=1e-12 * np.abs(ref).max())
+    flat = img.copy()
+    flat[40:48, 60:68] = 3.0
+    with pytest.raises(ValueError, match="Standard deviation is zero"):
+        pr.autocorr_mean_ref(flat, 8, [(0, 0), (40, 60)], True)
+
+
+def test_extended_precision_power_spectrum_agrees_with_oracle(po):
+    import pickers_reference as pr
+    rng = np.random.default_rng(23)
+    img = rng.standard_normal((260, 300))
+    for size in (1, 2, 3, 8, 31, 33, 48, 64, 97, 100, 255):
+        y, x = 260 - size, 7 if size < 255 else 0
+        patch = img[y:y + size, x:x + size]
+        for name in ("hann", None):
+            ref = po.cumulative_energy(patch, window_type=name)[2]
+            got = pr.power_spectra_ref(img, size, [(y, x)], pr.window_ref(name, size))[0]
+            np.testing.assert_allclose(got, ref, rtol=0, atol=1e-12 * max(ref.max(), np.finfo(float).tiny))
+    for name, fn in (("hanning", np.hanning), ("hamming", np.hamming), ("blackman", np.blackman)):   # the reference's calls
+        for size in (1, 2, 8, 33, 64):
+            np.testing.assert_allclose(pr.window_ref(name, size), fn(size), rtol=0, atol=1e-15)
+    from scipy.signal import windows
+    for size in (1, 2, 8, 33, 64):
+        np.testing.assert_allclose(pr.window_ref("tukey", size), windows.tukey(size, alpha=0.5), rtol=0, atol=1e-15)
+
+
 def test_picker_argument_errors_need_no_device():
     from mtflearn_amd.features import pickers
     with pytest.raises(ValueError, match="Invalid method 'median'"):
