@@ -22,7 +22,7 @@ int zk_rows_shape(const zk_rows* m, int* device, int64_t* n_rows, int* n_feature
 
 namespace {
 
-// z_r = (x_r - mean(x_r)) / |x_r - mean(x_r)|  (rows with no variation: zeros), written row-major (N, D) and feature-major
+// z_r = (x_r - mean(x_r)) / |x_r - mean(x_r)|  (rows with no variation, i.e. all features equal: zeros), written row-major (N, D) and feature-major
 // (D, Np) -- the second copy is what the candidates' coordinates are read from as scalar operands, eight candidates at a time
 __global__ __launch_bounds__(256) void unit_rows_kernel(const double* __restrict__ X, long long N, int D, long long Np,
                                                         double* __restrict__ Z, double* __restrict__ Zt) {
@@ -34,14 +34,15 @@ __global__ __launch_bounds__(256) void unit_rows_kernel(const double* __restrict
   }
   const double* x = X + r * D;
   double s = 0.0;
-  for (int f = 0; f < D; ++f) s += x[f];
+  bool varies = false;  // (a constant row's rounded mean need not be the constant: twelve times 0.1 is not 1.2)
+  for (int f = 0; f < D; ++f) s += x[f], varies |= x[f] != x[0];
   const double mean = s / D;
   double q = 0.0;
   for (int f = 0; f < D; ++f) {
     const double v = x[f] - mean;
     q += v * v;
   }
-  const double inv = q > 0.0 ? 1.0 / sqrt(q) : 0.0;
+  const double inv = varies && q > 0.0 ? 1.0 / sqrt(q) : 0.0;
   for (int f = 0; f < D; ++f) {
     const double v = (x[f] - mean) * inv;
     Z[r * D + f] = v;
@@ -182,14 +183,15 @@ __global__ __launch_bounds__(256) void unit_rows_blocked_kernel(const double* __
   const double* x = X + r * D;
   if (r < N) {
     double s = 0.0;
-    for (int f = 0; f < D; ++f) s += x[f];
+    bool varies = false;  // (see unit_rows_kernel)
+    for (int f = 0; f < D; ++f) s += x[f], varies |= x[f] != x[0];
     mean = s / D;
     double q = 0.0;
     for (int f = 0; f < D; ++f) {
       const double v = x[f] - mean;
       q += v * v;
     }
-    inv = q > 0.0 ? 1.0 / sqrt(q) : 0.0;
+    inv = varies && q > 0.0 ? 1.0 / sqrt(q) : 0.0;
   }
   for (int f = 0; f < 4 * steps; ++f) out[(f >> 2) * 64 + (f & 3) * 16] = r < N && f < D ? (x[f] - mean) * inv : 0.0;
 }

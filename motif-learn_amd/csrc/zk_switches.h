@@ -21,7 +21,7 @@
   X(ZK_POINTS_NO_WIDE, flag, off, call, "key points: window pixels by 4-byte loads instead of rows of 16-byte loads (same bits)")      \
   X(ZK_ESTEP_VALU, flag, off, call, "mixture E step on the vector pipe (the kernel of D > 48 or k > 8) instead of the matrix cores")   \
   X(ZK_WGRAM_VALU, flag, off, call, "mixture M step: the register-tiled kernel (that of D > 47) instead of the matrix cores")          \
-  X(ZK_KNN_SCALAR, integer, 0, call, "1: correlation kNN on the scalar-operand kernel (that of k > 16 or D > 96)")                     \
+  X(ZK_KNN_SCALAR, integer, 0, call, "1: correlation kNN, k <= 16: the four-wave scalar-operand knn_kernel<16, 4>, no matrix cores")   \
   X(ZK_KNN_PARTS, integer, auto, call, "parts of the candidate range of the matrix-core kNN (1 .. 16; default by matrix size)")        \
   X(ZK_HOST_CHUNK_MB, integer, 256, call, "MiB of input + output per chunk of the host-buffer pipeline (a plan's own setting wins)")   \
   X(ZK_CLOCK_MONITOR_MODE, integer, 0, call, "zk_clock_monitor: the resident wave naps (0), spins (1) or does FP64 work (2)")          \

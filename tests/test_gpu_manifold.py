@@ -1,6 +1,7 @@
 """The manifold consumer on the device: the neighbour search and affinities of ForceGraph8's
 ``compute_graph`` against scikit-learn's ``NearestNeighbors(metric='correlation')`` (what the reference calls) and the oracle's
-restatement of ``calculate_asymmetric_Pij`` / ``calculate_graph``; the class end to end against the oracle pipeline."""
+restatement of ``calculate_asymmetric_Pij`` / ``calculate_graph``; the class end to end against the oracle pipeline.
+The kernels one by one, against an extended-precision reference with a defined tie order: tests/test_gpu_graph_kernels.py."""
 import warnings
 
 import numpy as np
