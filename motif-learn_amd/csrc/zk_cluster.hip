@@ -437,12 +437,17 @@ __global__ __launch_bounds__(64) void owndist_kernel(const double* __restrict__ 
 //  Also tried: two rows per lane (128-row tiles) so that every scalar operand feeds two FMAs: 2.03 against 2.08 ms -- the
 //  halved occupancy takes back what the halved scalar traffic gives.)
 // ZK_EWAVES waves share a tile (every wave holds the same 64 rows, lane = row): the (component, column block) pairs are dealt
-// to the waves by cost on the host (`plan`: per wave a count and its (c, j0) pairs), each wave adds the squared norms of its
-// blocks into its own [k][64] LDS table, and after a barrier every wave combines the tables in wave order -- redundant but
-// cheap arithmetic -- for the log-sum-exp; the stores of the responsibilities are split by component.
+// to the waves by cost on the host (`plan`: per wave a count and its (c, j0) pairs), each wave adds the squared norm of a
+// block into slot (block mod ZK_EWAVES) of an LDS table [ZK_EWAVES][k][64], and after a barrier every wave adds a component's
+// slots in slot order -- redundant but cheap arithmetic -- for the log-sum-exp; the stores of the responsibilities are split
+// by component.  (The slot follows the block, not the wave that computed it: which wave did a block must not show in the sum, or
+// two identical components get log probabilities that differ in the last bit and the tie between them goes to either index.
+// A slot takes one block (D <= 64: a plain store) or two (an LDS atomic add onto the zeroed slot: a + b is b + a, so the order
+// in which the two waves arrive does not show either).)
 #ifndef ZK_EWAVES
 #define ZK_EWAVES 4
 #endif
+static_assert((ZK_EWAVES & (ZK_EWAVES - 1)) == 0 && ZK_EW * 2 * ZK_EWAVES >= 128, "a slot takes at most two column blocks");
 __global__ __launch_bounds__(64 * ZK_EWAVES) void estep_kernel(const double* __restrict__ X, long long N, int D, int DP,
                                                                const double* __restrict__ P, const double* __restrict__ B,
                                                                const double* __restrict__ cst /* [k][2]: logdet, logw */,
@@ -452,6 +457,7 @@ __global__ __launch_bounds__(64 * ZK_EWAVES) void estep_kernel(const double* __r
   extern __shared__ __attribute__((aligned(16))) double lds[];
   double* tile = lds;                  // [64][D]
   double* sqw = lds + TILE * D;        // [ZK_EWAVES][k][64]
+  const bool shared_slots = DP / ZK_EW > ZK_EWAVES;  // two blocks per slot (D <= 127 < ZK_EW * 2 * ZK_EWAVES)
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   double* mine = sqw + (long long)wave * k * 64;
@@ -474,7 +480,7 @@ __global__ __launch_bounds__(64 * ZK_EWAVES) void estep_kernel(const double* __r
         tile[q * TILE + lane] = e < total ? X[e] : 0.0;
       }
     }
-    for (int c = 0; c < k; ++c) mine[c * 64 + lane] = 0.0;
+    for (int c = 0; c < k; ++c) mine[c * 64 + lane] = 0.0;  // wave w clears slot w
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     const double* row = tile + lane * D;
@@ -519,7 +525,10 @@ __global__ __launch_bounds__(64 * ZK_EWAVES) void estep_kernel(const double* __r
       double sq = 0.0;
 #pragma unroll
       for (int jj = 0; jj < ZK_EW; ++jj) sq = __builtin_fma(a[jj], a[jj], sq);
-      mine[c * 64 + lane] += sq;
+      // every (c, j0) pair is in exactly one wave's plan
+      double* slot = sqw + ((long long)((j0 / ZK_EW) & (ZK_EWAVES - 1)) * k + c) * 64 + lane;
+      if (shared_slots) (void)__hip_atomic_fetch_add(slot, sq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      else *slot = sq;
     }
     __syncthreads();
     // weighted log probabilities of the 64 rows (every wave), log-sum-exp, outputs split by component / wave

@@ -162,18 +162,104 @@ def test_pca_of_a_resident_matrix():
         kmeans_fit(rows, 3)                                                     # and the same resident matrix clusters on
 
 
+EDGE_SHAPES = [(1, 1), (2, 1), (63, 2), (64, 3), (65, 64), (129, 127), (1000, 45), (4097, 66), (200, 91), (777, 5), (5000, 120),
+               (64 * 7, 33), (64 * 7 + 1, 80), (64 * 7 - 1, 81)]
+MATRIX_CORE_SHAPES = [(1, 2), (15, 16), (16, 17), (17, 32), (127, 33), (128, 45), (129, 48), (1000, 45), (4099, 40), (70001, 45)]
+
+
+def _edge_matrix(n, d):
+    rng = np.random.default_rng([99, n, d])
+    return rng.standard_normal((n, d)) * (1 + rng.random(d)) + rng.standard_normal(d) * 3
+
+
+def _edge_mixtures(X):
+    """(k, (prec_chol, means, log_det, log_w)) of the E-step part of test_row_passes_on_edge_shapes; every row of every one is
+    decided (tests/test_cluster_reference_cpu.py), so the labels are compared exactly."""
+    from scipy import linalg
+    n, d = X.shape
+    for k in (1, 2, 5, 12):
+        if k > n or d > 91 and k > 5:
+            continue
+        rng = np.random.default_rng([7, n, d, k])
+        means = X[rng.choice(n, k, replace=False)]
+        prec = np.zeros((k, d, d))
+        for c in range(k):
+            a = rng.standard_normal((d, d)) * 0.3 + np.eye(d) * 2
+            prec[c] = linalg.solve_triangular(linalg.cholesky(a @ a.T, lower=True), np.eye(d), lower=True).T
+        yield k, (prec, means, np.log(np.einsum("kii->ki", prec)).sum(axis=1), np.log(np.full(k, 1.0 / k)))
+
+
+EDGE_LLOYD_K = (1, 3, 8, 13, 16, 17, 40)
+
+
+def _edge_centres(X, mean, k):
+    """k rows of the centred matrix, nudged: the centres of the Lloyd part of test_row_passes_on_edge_shapes."""
+    rng = np.random.default_rng([8, len(X), X.shape[1], k])
+    return (X[rng.choice(len(X), k, replace=False)] - mean) + 0.01 * rng.standard_normal((k, X.shape[1]))
+
+
+def edge_lloyd_cases():
+    """(X, mean, centres) of every Lloyd pass whose labels test_row_passes_on_edge_shapes compares exactly or builds on: the
+    nudged centres, and the mixtures' means used as centres before resp_from_labels."""
+    for n, d in EDGE_SHAPES:
+        X = _edge_matrix(n, d)
+        mean = X.sum(axis=0) / n
+        for k in EDGE_LLOYD_K:
+            if k <= n:
+                yield X, mean, _edge_centres(X, mean, k)
+        for k, mix in _edge_mixtures(X):
+            yield X, mean, mix[1] - mean
+
+
+def edge_estep_cases():
+    for n, d in EDGE_SHAPES:
+        X = _edge_matrix(n, d)
+        for k, mix in _edge_mixtures(X):
+            yield X, mix
+
+
+def _matrix_core_matrix(n, d):
+    rng = np.random.default_rng([5, n, d])
+    return rng.standard_normal((n, d)) * (1 + rng.random(d)) + rng.standard_normal(d) * 2
+
+
+def _matrix_core_mixtures(X):
+    from scipy import linalg
+    n, d = X.shape
+    for k in (1, 4, 8):
+        if k > n:
+            continue
+        for kind in ("full", "diag"):
+            rng = np.random.default_rng([6, n, d, k, kind == "full"])
+            means = X[rng.choice(n, k, replace=False)] + 0.1 * rng.standard_normal((k, d))
+            prec = np.zeros((k, d, d))
+            for c in range(k):
+                if kind == "full":
+                    a = rng.standard_normal((d, d)) * 0.3 + np.eye(d) * 2
+                    prec[c] = linalg.solve_triangular(linalg.cholesky(a @ a.T, lower=True), np.eye(d), lower=True).T
+                else:
+                    prec[c] = np.diag(0.5 + rng.random(d))
+            log_det = np.log(np.einsum("kii->ki", prec)).sum(axis=1)
+            yield k, kind, (prec, means, log_det, np.log(rng.dirichlet(np.ones(k) * 5)))
+
+
+def matrix_core_estep_cases():
+    for n, d in MATRIX_CORE_SHAPES:
+        X = _matrix_core_matrix(n, d)
+        for k, kind, mix in _matrix_core_mixtures(X):
+            yield X, mix
+
+
 def test_row_passes_on_edge_shapes():
     """Every pass of csrc/zk_cluster.hip against its NumPy statement (the stand-in of tests/test_clustering_sharded_cpu.py) on
     the shapes where tiling can go wrong: 1 to 127 features (odd, even, exactly 64), row counts below / at / just past a
     64-row tile, one cluster to more than the register-resident limit, ragged last tiles."""
-    from scipy import linalg
+    import cluster_reference as ref
     from test_clustering_sharded_cpu import HostRows
     from mtflearn_amd.clustering import DeviceRows
     rng = np.random.default_rng(99)
-    shapes = [(1, 1), (2, 1), (63, 2), (64, 3), (65, 64), (129, 127), (1000, 45), (4097, 66), (200, 91), (777, 5), (5000, 120),
-              (64 * 7, 33), (64 * 7 + 1, 80), (64 * 7 - 1, 81)]
-    for n, d in shapes:
-        X = rng.standard_normal((n, d)) * (1 + rng.random(d)) + rng.standard_normal(d) * 3
+    for n, d in EDGE_SHAPES:
+        X = _edge_matrix(n, d)
         host = HostRows(X)
         with DeviceRows(X) as dev:
             np.testing.assert_allclose(dev.colsum(), host.colsum(), rtol=1e-12, atol=1e-9)
@@ -191,13 +277,16 @@ def test_row_passes_on_edge_shapes():
                 which = int(rng.integers(0, t))
                 vals = np.sort(rng.random(3)) * host._cand[which].sum()
                 pick_d, pick_h = dev.seed_pick(which, vals), host.seed_pick(which, vals)
-                near = np.abs(np.cumsum(host.closest)[pick_h] - vals) < 1e-9 * max(1.0, host.closest.sum())
-                assert np.all((pick_d == pick_h) | near)
+                assert np.all(pick_h == ref.seed_pick(host.closest, vals)[0])
+                # a draw is decided when it lies further from every cumulative sum than the roundings of the distance rows
+                # (D + 2 of 2^-53 |x|^2 each) can move one: an undecided draw may fall on the neighbouring row
+                decided = ref.seed_pick(host.closest, vals)[1] > 1e-12
+                assert np.all(pick_d[decided] == pick_h[decided]) and np.all(np.abs(pick_d - pick_h) <= 1)
                 np.testing.assert_allclose(dev.seed_step(cand, csq, True), host.seed_step(cand, csq, True), rtol=1e-11, atol=1e-9)
-            for k in (1, 3, 8, 13, 16, 17, 40):
+            for k in EDGE_LLOYD_K:
                 if k > n:
                     continue
-                centers = host.fetch(rng.choice(n, k, replace=False)) + 0.01 * rng.standard_normal((k, d))
+                centers = _edge_centres(X, mean, k)           # every label decided: tests/test_cluster_reference_cpu.py
                 dev.reset_labels(), host.reset_labels()
                 for update in (True, False):
                     s_d, c_d, ch_d = dev.lloyd(centers, update)
@@ -208,20 +297,11 @@ def test_row_passes_on_edge_shapes():
                         np.testing.assert_array_equal(c_d, c_h)
                         np.testing.assert_allclose(s_d, s_h, rtol=1e-11, atol=1e-10)
                 np.testing.assert_allclose(dev.own_distance(centers), host.own_distance(centers), rtol=1e-11, atol=1e-12)
-            for k in (1, 2, 5, 12):
-                if k > n or d > 91 and k > 5:
-                    continue
-                means = X[rng.choice(n, k, replace=False)]
-                prec = np.zeros((k, d, d))
-                for c in range(k):
-                    a = rng.standard_normal((d, d)) * 0.3 + np.eye(d) * 2
-                    prec[c] = linalg.solve_triangular(linalg.cholesky(a @ a.T, lower=True), np.eye(d), lower=True).T
-                log_det = np.log(np.einsum("kii->ki", prec)).sum(axis=1)
-                log_w = np.log(np.full(k, 1.0 / k))
+            for k, (prec, means, log_det, log_w) in _edge_mixtures(X):
                 lse_d, lse_h = dev.estep(prec, means, log_det, log_w), host.estep(prec, means, log_det, log_w)
                 assert abs(lse_d - lse_h) <= 1e-10 * max(1.0, abs(lse_h))
-                agree = np.mean(dev.labels() == host.labels())
-                assert agree == 1.0 or (agree > 0.99 and n > 500)
+                np.testing.assert_array_equal(dev.labels(), ref.estep_labels(X, prec, means, log_det, log_w)[0])
+                np.testing.assert_array_equal(host.labels(), dev.labels())
                 shift = X.mean(axis=0)
                 for c in range(k):
                     g_h = host.moments(c, shift)
@@ -240,36 +320,22 @@ def test_mixture_e_step_on_the_matrix_cores():
     'full' / 'tied' factors, the diagonal pieces only for 'diag' / 'spherical' ones; 1 to 3 column blocks, row counts around
     the 16-row blocks of a wave and the 128 rows of a workgroup round; against the NumPy statement -- log-likelihood, labels and
     (through the weighted moments) the responsibilities."""
-    from scipy import linalg
+    import cluster_reference as ref
     from test_clustering_sharded_cpu import HostRows
     from mtflearn_amd.clustering import DeviceRows
-    rng = np.random.default_rng(5)
-    for n, d in [(1, 2), (15, 16), (16, 17), (17, 32), (127, 33), (128, 45), (129, 48), (1000, 45), (4099, 40), (70001, 45)]:
-        X = rng.standard_normal((n, d)) * (1 + rng.random(d)) + rng.standard_normal(d) * 2
+    for n, d in MATRIX_CORE_SHAPES:
+        X = _matrix_core_matrix(n, d)
         host = HostRows(X)
         with DeviceRows(X) as dev:
-            for k in (1, 4, 8):
-                if k > n:
-                    continue
-                for kind in ("full", "diag"):
-                    means = X[rng.choice(n, k, replace=False)] + 0.1 * rng.standard_normal((k, d))
-                    prec = np.zeros((k, d, d))
-                    for c in range(k):
-                        if kind == "full":
-                            a = rng.standard_normal((d, d)) * 0.3 + np.eye(d) * 2
-                            prec[c] = linalg.solve_triangular(linalg.cholesky(a @ a.T, lower=True), np.eye(d), lower=True).T
-                        else:
-                            prec[c] = np.diag(0.5 + rng.random(d))
-                    log_det = np.log(np.einsum("kii->ki", prec)).sum(axis=1)
-                    log_w = np.log(rng.dirichlet(np.ones(k) * 5))
-                    lse_d, lse_h = dev.estep(prec, means, log_det, log_w), host.estep(prec, means, log_det, log_w)
-                    assert abs(lse_d - lse_h) <= 1e-10 * max(1.0, abs(lse_h)), (n, d, k, kind)
-                    agree = np.mean(dev.labels() == host.labels())
-                    assert agree == 1.0 or (agree > 0.999 and n > 500), (n, d, k, kind, agree)
-                    shift = X.mean(axis=0)
-                    for c in range(k):
-                        g_h = host.moments(c, shift)
-                        np.testing.assert_allclose(dev.moments(c, shift), g_h, rtol=1e-10, atol=1e-10 * np.abs(g_h).max())
+            for k, kind, (prec, means, log_det, log_w) in _matrix_core_mixtures(X):
+                lse_d, lse_h = dev.estep(prec, means, log_det, log_w), host.estep(prec, means, log_det, log_w)
+                assert abs(lse_d - lse_h) <= 1e-10 * max(1.0, abs(lse_h)), (n, d, k, kind)
+                np.testing.assert_array_equal(dev.labels(), ref.estep_labels(X, prec, means, log_det, log_w)[0],
+                                              err_msg=str((n, d, k, kind)))
+                shift = X.mean(axis=0)
+                for c in range(k):
+                    g_h = host.moments(c, shift)
+                    np.testing.assert_allclose(dev.moments(c, shift), g_h, rtol=1e-10, atol=1e-10 * np.abs(g_h).max())
 
 
 def test_sharded_control_flow_on_the_device_passes():
