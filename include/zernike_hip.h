@@ -437,6 +437,64 @@ int zk_background_baseline_dev(int device, const void* image_dev, int dtype, int
                                void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Image normalisation and clipping: the device side of the reference's utils/ subpackage (_preprocessing_image.py,
+ * _clip_image.py), the first step of every workflow.  No plan involved.  The image is flat: n elements (1 <= n < 2^31) of
+ * ZK_F32 / ZK_F64 / ZK_U8 / ZK_U16 / ZK_I16, C-contiguous in any shape, each converted to float32 as it is read (round to
+ * nearest, ndarray.astype(np.float32)).  These calls do the passes over the pixels; everything scalar (np.isclose, eps,
+ * NumPy's percentile interpolation, the decision to clip) is the caller's, on the few numbers that come back.
+ *
+ *   zk_image_stats        minmax[2]: min and max over the finite elements (+inf, -inf when there is none); *n_nonfinite: the
+ *                         count of NaN / inf elements; sums[3]: sum x, sum |x|, sum x^2 over the finite elements in float64.
+ *                         mode & ZK_STATS_CENTERED: sums[0] = sum (x - center)^2 instead (the second pass of a two-pass
+ *                         variance), sums[1] = sums[2] = 0.  mode & ZK_STATS_WIDE: the sums (and the finite test) of a ZK_F64
+ *                         image take its elements as they are, not narrowed (np.mean / np.std of a float64 image).
+ *                         An element finite in float64 and past the float32 range is then summed and counted finite, and
+ *                         left out of min / max.
+ *                         Per-lane, per-workgroup and final partial sums are joined in a fixed tree, each carried as an
+ *                         unevaluated pair of doubles: the result is the rounded exact sum to a few 2^-100 of sum |terms| and
+ *                         two runs agree bit for bit (no floating-point atomics).
+ *   zk_image_order_stats  values[i] = element ranks[i] (zero-based, 0 <= rank < n, at most 16 of them, any order, repeats
+ *                         allowed) of the ascending sort of the converted elements (ZK_ORDER_VALUES) or of |x - center|
+ *                         computed in float32 (ZK_ORDER_DEVIATIONS: the second median of a MAD; the deviations are never
+ *                         stored).  Exact: a radix select on the order-preserving uint32 image of the float32 bits, every rank
+ *                         refined in the same four sweeps, counts merged with integer atomics (the same result every run).
+ *                         -0.0 sorts just below +0.0 (they compare equal: either may come back).  NaN elements sort by
+ *                         their bits (after +inf with the sign clear); their place is not pinned.
+ *   zk_image_map          out[i] = f(x[i]), one operation at a time, nothing fused:
+ *                           ZK_MAP_RESCALE      p0 + (x - p1) * p2 / p3  in float32, in that order (vmin, x_min, span, scale):
+ *                                               NumPy's float32 result bit for bit
+ *                           ZK_MAP_CLIP         np.clip(x, p0, p1)       in float32 (NaN stays NaN; p0 > p1 gives p1)
+ *                           ZK_MAP_DIVIDE       x / p0                   in float64, rounded once to float32
+ *                           ZK_MAP_STANDARDIZE  (x - p0) / p1            in float64 on the element as stored, rounded once
+ *                         params: four doubles (the float32 operations take them rounded to float32).  out is float32, except
+ *                         ZK_MAP_STANDARDIZE of a non-ZK_F32 image: float64.  keep_nonfinite: NaN / inf elements are copied
+ *                         to the output as they are.
+ *
+ * The _dev variants take device pointers (image, out) and run on hip_stream; ranks, params and every scalar result are host
+ * memory (stats and order stats synchronise the stream: their results cross to the host).
+ * ------------------------------------------------------------------------------------------------------ */
+#define ZK_STATS_CENTERED 1
+#define ZK_STATS_WIDE 2
+#define ZK_ORDER_VALUES 0
+#define ZK_ORDER_DEVIATIONS 1
+#define ZK_MAP_RESCALE 0
+#define ZK_MAP_DIVIDE 1
+#define ZK_MAP_CLIP 2
+#define ZK_MAP_STANDARDIZE 3
+int zk_image_stats(int device, const void* image_host, int dtype, int64_t n, int mode, double center, float* minmax_host,
+                   int64_t* n_nonfinite_host, double* sums_host);
+int zk_image_stats_dev(int device, const void* image_dev, int dtype, int64_t n, int mode, double center, float* minmax_host,
+                       int64_t* n_nonfinite_host, double* sums_host, void* hip_stream);
+int zk_image_order_stats(int device, const void* image_host, int dtype, int64_t n, int mode, float center,
+                         const int64_t* ranks_host, int n_ranks, float* values_host);
+int zk_image_order_stats_dev(int device, const void* image_dev, int dtype, int64_t n, int mode, float center,
+                             const int64_t* ranks_host, int n_ranks, float* values_host, void* hip_stream);
+int zk_image_map(int device, const void* image_host, int dtype, int64_t n, int op, const double* params_host, int keep_nonfinite,
+                 void* out_host);
+int zk_image_map_dev(int device, const void* image_dev, int dtype, int64_t n, int op, const double* params_host,
+                     int keep_nonfinite, void* out_dev, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Patch-SVD / patch-PCA denoising: the device side of the reference's denoise/ subpackage (_denoise_svd.py,
  * _denoise_svd_memory_view.py), the step ahead of background removal.  No plan involved.
  *

@@ -5,7 +5,8 @@
 (``mtflearn_amd.features``: parameter pickers, ``pca``; ``mtflearn_amd.clustering``: ``kmeans_lbs`` / ``gmm_lbs`` /
 ``sort_lbs``; ``mtflearn_amd.manifold``: ``ForceGraph8``; ``mtflearn_amd.background``: ``estimate_background_*`` /
 ``remove_background_*`` and their parameter picker; ``mtflearn_amd.denoise``: ``denoise_svd`` / ``DenoiseSVD`` /
-``denoise_svd_memory_view``, the reference's other two top-level names); see DESIGN.md.
+``denoise_svd_memory_view``, the reference's other two top-level names; ``mtflearn_amd.utils``: ``normalize_image`` /
+``normalize_image_robust`` / ``standardize_image`` / ``percentile_clip`` / ``value_clip``); see DESIGN.md.
 """
 __version__ = "0.1.0"
 

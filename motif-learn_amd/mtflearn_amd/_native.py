@@ -11,7 +11,7 @@ import os
 import sys
 import threading
 import weakref
-from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
 
 import numpy as np
 
@@ -19,6 +19,9 @@ ZK_F32, ZK_F64 = 0, 1
 ZK_U8, ZK_U16, ZK_I16 = 2, 3, 4   # host-buffer entry points only: widened to float32 on the device (exact)
 PATH_AUTO, PATH_GENERIC, PATH_FOLDED, PATH_SEPARABLE, PATH_STREAM, PATH_DIRECT = 0, 1, 2, 3, 4, 5
 OP_POINTS, OP_MAPS = 1, 2
+STATS_CENTERED, STATS_WIDE = 1, 2                                  # zk_image_stats modes
+ORDER_VALUES, ORDER_DEVIATIONS = 0, 1                              # zk_image_order_stats modes
+MAP_RESCALE, MAP_DIVIDE, MAP_CLIP, MAP_STANDARDIZE = 0, 1, 2, 3    # zk_image_map operations
 XFER_SEND, XFER_RECV, XFER_ALLGATHER, XFER_BCAST = 1, 2, 3, 4
 COMM_AUTO, COMM_P2P, COMM_ALLGATHER, COMM_BCAST = 0, 1, 2, 3
 COMM_ALGOS = {"": COMM_AUTO, "auto": COMM_AUTO, "p2p": COMM_P2P, "allgather": COMM_ALLGATHER, "bcast": COMM_BCAST}
@@ -116,6 +119,12 @@ SYMBOLS = {
                                        c_int, c_void_p, c_void_p]),
     "zk_background_baseline_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                            c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "zk_image_stats": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_double, c_void_p, POINTER(c_int64), c_void_p]),
+    "zk_image_stats_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_double, c_void_p, POINTER(c_int64), c_void_p, c_void_p]),
+    "zk_image_order_stats": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_int, c_void_p]),
+    "zk_image_order_stats_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
+    "zk_image_map": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p]),
+    "zk_image_map_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "zk_windows_apply": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                  c_void_p, c_int64, c_void_p, c_void_p]),
     "zk_windows_apply_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,

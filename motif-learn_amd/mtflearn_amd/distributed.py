@@ -31,7 +31,8 @@ import numpy as np
 from . import _native
 
 __all__ = ["shard_bounds", "one_gpu_rank_env", "RcclComm", "TorchComm", "DeviceCompute", "patch_moments_device",
-           "frame_moments_device", "frame_maps_device", "local_max_device", "points_moments_device", "remove_background_device", "denoise_svd_device",
+           "frame_moments_device", "frame_maps_device", "normalize_image_device", "standardize_image_device",
+           "percentile_clip_device", "local_max_device", "points_moments_device", "remove_background_device", "denoise_svd_device",
            "denoise_svd_memory_view_device", "sharded_patch_moments", "sharded_frame_moments",
            "sharded_frame_maps", "sharded_frames_moments"]
 
@@ -364,6 +365,44 @@ def remove_background_device(image, method, parameter, clip=True, **method_kw):
         _native.check(lib.zk_background_baseline_dev(*args, wy.ctypes.data_as(c_void_p), len(wy) - 1, wx.ctypes.data_as(c_void_p),
                                                      len(wx) - 1, iters, *outs), "zk_background_baseline_dev")
     return residual, background
+
+
+def _device_image(image):
+    """The :class:`mtflearn_amd.utils._Operand` of a device-resident image of any shape, on torch's current stream."""
+    from .utils import _Operand
+    if not image.is_cuda:
+        raise ValueError("image must live on the GPU")
+    if not _is_native(image) and not image.is_contiguous():
+        image = image.contiguous()
+    return _Operand(image, _current_stream_ptr(image))
+
+
+def normalize_image_device(image, mode="minmax", eps=1e-8, vmin=0.0, vmax=1.0):
+    """:func:`mtflearn_amd.utils.normalize_image` of an image resident on the GPU (a torch tensor or a :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` or ``(H, W, C)``
+    of float32 / float64 / uint8 / uint16 / int16).  Returns the float32 result as a device array of the same kind, the same
+    numbers as the host function; only the statistics (two floats, a count, three sums) cross to the host.  Runs on torch's
+    current stream."""
+    from .utils import _check_mode, _normalize_core
+    _check_mode(mode)
+    return _normalize_core(_device_image(image), mode, float(eps), float(vmin), float(vmax), False)
+
+
+def standardize_image_device(image):
+    """:func:`mtflearn_amd.utils.standardize_image` of an image resident on the GPU (as :func:`normalize_image_device`):
+    float32 for a float32 image, float64 otherwise, as a device array of the same kind."""
+    from .utils import _standardize_core
+    return _standardize_core(_device_image(image))
+
+
+def percentile_clip_device(image, low=1.0, high=99.0, method="auto", high_ratio_thresh=5.0, mad_k=8.0, iqr_k=3.0, eps=1e-8):
+    """:func:`mtflearn_amd.utils.percentile_clip` of an image resident on the GPU (as :func:`normalize_image_device`).  Returns
+    ``(out, did_clip, info)`` with ``out`` the float32 image (clipped or not) as a device array of the same kind and ``info``
+    the host function's dictionary; only the order statistics (at most 16 floats per call) cross to the host."""
+    from .utils import _check_method, _check_percentile, _clip_core
+    method = _check_method(method)
+    _check_percentile(high)
+    _check_percentile(low)
+    return _clip_core(_device_image(image), low, high, method, high_ratio_thresh, mad_k, iqr_k, eps)
 
 
 def _device_frame(image, what):
