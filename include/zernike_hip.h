@@ -495,6 +495,41 @@ int zk_image_map_dev(int device, const void* image_dev, int dtype, int64_t n, in
                      int keep_nonfinite, void* out_dev, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Rasterising Gaussian atoms: the device side of the reference's datasets/ subpackage (_tapered_gaussian.py, what
+ * HoneyCombLattice.to_image draws with, and the uncut Gaussians of _zps_test_data.py / _generate_data_gn.py).  No plan
+ * involved.  frame: ZK_F32 / ZK_F64, C-contiguous (batch, height, width), ADDED TO IN PLACE.  points: n_points pairs (x, y)
+ * of float64 in pixel coordinates (x the column, y the row; centres may lie outside the frame and may be negative);
+ * amplitudes: n_points float64.  Both are HOST arrays in either form.
+ *
+ *   r_factor > 0   add_tapered_gaussian, to the letter.  With R = r_factor * sigma, point (x0, y0) touches the pixels of
+ *                  [floor(x0 - R), ceil(x0 + R)] x [floor(y0 - R), ceil(y0 + R)] cut to the frame (nothing left: the point is
+ *                  skipped); with dx = X - x0, dy = Y - y0, r = sqrt(dx * dx + dy * dy), the pixels with r <= R receive
+ *                    taper = 1:  A * exp(-0.5 * (r * r) / sigma^2) * (1 - 3 t^2 + 2 t^3),  t = r / R
+ *                    taper = 0:  A * exp(-0.5 * (r * r) / sigma^2)
+ *                  in float64, one rounding per operation, nothing fused.  At r = R the taper is exactly 0.  The pixels of
+ *                  the box outside the disc, to which the reference adds 0.0, are left alone: the one visible difference
+ *                  is that a -0.0 pixel there stays -0.0.  batch must be 1.
+ *   r_factor <= 0  no cutoff (taper must be 0): every pixel of the frame receives A * exp(-(dx * dx + dy * dy) / (2 sigma^2)),
+ *                  the squared distance as it is, no sqrt.  batch frames of equal shape, frame b taking the points
+ *                  point_offsets[b] .. point_offsets[b + 1] (batch + 1 ascending int64 from 0 to n_points, host memory;
+ *                  NULL with batch = 1: all points).
+ *
+ * Order is part of the contract: every pixel adds its contributions in ascending point index, and a ZK_F32 frame rounds
+ * after every add, acc = (float)((double)acc + w), as the reference's in-place += does.  It is a gather (per-tile point
+ * lists built with integer atomics and sorted), so two runs agree bit for bit; no floating-point atomics.
+ * list_budget: the most list entries (one per point and 16 x 16 pixel tile its box overlaps) built at once, <= 0 for the
+ * default of 2^24; past it the points are rendered as consecutive index ranges, which changes no result.
+ * The _dev variant takes the frame as a device pointer, runs on hip_stream and synchronises it before it returns (its point
+ * and list buffers live for the call).
+ * ------------------------------------------------------------------------------------------------------ */
+int zk_render_gaussians(int device, void* frame_host, int dtype, int64_t height, int64_t width, int64_t batch,
+                        const double* points_host, const double* amplitudes_host, const int64_t* point_offsets_host,
+                        int64_t n_points, double sigma, double r_factor, int taper, int64_t list_budget);
+int zk_render_gaussians_dev(int device, void* frame_dev, int dtype, int64_t height, int64_t width, int64_t batch,
+                            const double* points_host, const double* amplitudes_host, const int64_t* point_offsets_host,
+                            int64_t n_points, double sigma, double r_factor, int taper, int64_t list_budget, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Patch-SVD / patch-PCA denoising: the device side of the reference's denoise/ subpackage (_denoise_svd.py,
  * _denoise_svd_memory_view.py), the step ahead of background removal.  No plan involved.
  *

@@ -3,7 +3,7 @@
 
   notebook 2 (batch):  key points -> patches -> ZPs.fit_transform(patches) -> rotation-invariant |Z_nm| -> rot_maps
   notebook 3 (dense):  ZPs.fit_transform(frame) -> rot_maps / mirror_map / |Z_nm| maps
-  resident chain:      frame on the device -> denoise -> background removal -> local maxima -> moments at them
+  resident chain:      lattice rendered on the device -> denoise -> background removal -> local maxima -> moments at them
 
 Only the import line differs from the reference (`from mtflearn import ZPs`).  Needs an MI355X.
 Run:  python motif-learn_amd/examples/notebook_flows.py
@@ -53,17 +53,23 @@ def main():
 
     # ---- the front of the chain, device-resident: the notebooks' input frame is a denoised one -------------------
     from mtflearn_amd import _native
-    from mtflearn_amd.distributed import (denoise_svd_device, local_max_device, points_moments_device,
+    from mtflearn_amd.datasets import HoneyCombLattice                     # reference: from mtflearn.datasets import ...
+    from mtflearn_amd.distributed import (denoise_svd_device, honeycomb_image_device, local_max_device, points_moments_device,
                                           remove_background_device)
     t = time.perf_counter()
-    dev = _native.DeviceArray.from_numpy(frame)                            # the only trip of the frame over PCIe
+    lattice = HoneyCombLattice(size=1024, l=12, seed=7)
+    dev = honeycomb_image_device(lattice)                                  # born on the device: only the site coordinates go up
     clean = denoise_svd_device(dev, size, n_components=8)                  # reference: denoise_svd(frame, 32, 8)
     residual, _ = remove_background_device(clean, "opening", 3 * size + 1)
     peaks = local_max_device(residual, 5.0)                                # (N, 2) int32 (x, y) on the device
     keep = peaks.numpy()
     keep = keep[(keep.min(axis=1) >= size // 2) & (keep[:, 0] < 1024 - size // 2) & (keep[:, 1] < 1024 - size // 2)]
     moments = points_moments_device(zps._device_plan(), clean, _native.DeviceArray.from_numpy(keep.astype(np.int32)))
-    print(f"chain  : denoise -> background -> local_max -> moments {moments.shape} in {1e3 * (time.perf_counter() - t):.1f} ms")
+    print(f"chain  : render -> denoise -> background -> local_max -> moments {moments.shape} in {1e3 * (time.perf_counter() - t):.1f} ms")
+    sites = np.concatenate(lattice.get_points())                           # the frame's atoms are known: check the peaks
+    inner = keep[(keep.min(axis=1) >= 2 * size) & (keep.max(axis=1) < 1024 - 2 * size)]
+    dist = np.hypot(inner[:, None, 0] - sites[None, :, 0], inner[:, None, 1] - sites[None, :, 1]).min(axis=1)
+    print(f"         {len(inner)} interior peaks, farthest from a lattice site: {dist.max():.2f} px")
 
 
 if __name__ == "__main__":

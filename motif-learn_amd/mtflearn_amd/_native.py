@@ -125,6 +125,10 @@ SYMBOLS = {
     "zk_image_order_stats_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
     "zk_image_map": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p]),
     "zk_image_map_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "zk_render_gaussians": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_double,
+                                    c_double, c_int, c_int64]),
+    "zk_render_gaussians_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                        c_double, c_double, c_int, c_int64, c_void_p]),
     "zk_windows_apply": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                  c_void_p, c_int64, c_void_p, c_void_p]),
     "zk_windows_apply_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,

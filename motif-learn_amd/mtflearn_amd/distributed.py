@@ -405,6 +405,56 @@ def percentile_clip_device(image, low=1.0, high=99.0, method="auto", high_ratio_
     return _clip_core(_device_image(image), low, high, method, high_ratio_thresh, mad_k, iqr_k, eps)
 
 
+def render_gaussians_device(frame_dev, pts, sigma, amplitude=1, r_factor=3.0):
+    """:func:`mtflearn_amd.datasets.add_tapered_gaussian` into a frame resident on the GPU (a torch tensor or a
+    :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` of float32 / float64): the tapered Gaussians at the host points
+    ``pts`` are added in place and the frame is returned, the same numbers as the host function bit for bit.  Only the points
+    cross to the device.  Runs on torch's current stream, which is synchronised before the call returns."""
+    from .datasets import _points_and_amplitudes, _render_device
+    pts, amps = _points_and_amplitudes(len(frame_dev.shape), pts, sigma, amplitude, r_factor)
+    if not frame_dev.is_cuda:
+        raise ValueError("image must live on the GPU")
+    if not frame_dev.is_contiguous():
+        raise ValueError("the frame is added to in place and must be contiguous")
+    _dtype_code(frame_dev)
+    if len(pts) and frame_dev.numel():
+        _render_device(frame_dev, pts, amps, sigma, r_factor, True)
+    return frame_dev
+
+
+def honeycomb_image_device(lattice, like=None, **to_image_kw):
+    """:meth:`mtflearn_amd.datasets.HoneyCombLattice.to_image` with the image left on the GPU: the float32
+    ``(size, size)`` frame as a :class:`~mtflearn_amd._native.DeviceArray` on the default device, or, with ``like`` a torch
+    tensor (or a DeviceArray), as an array of that kind on that device.  ``to_image_kw``: ``sigma``, ``intensity_A``,
+    ``intensity_B``, ``normalize``.  The frame is born on the device and goes on to :func:`remove_background_device`,
+    :func:`local_max_device` and :func:`points_moments_device` without a host copy; only the site coordinates go up."""
+    from .datasets import _render_device
+    from .utils import _Operand, _map, _stats
+    unknown = set(to_image_kw) - {"sigma", "intensity_A", "intensity_B", "normalize"}
+    if unknown:
+        raise TypeError(f"to_image() got an unexpected keyword argument {sorted(unknown)[0]!r}")
+    sigma, pts, amps = lattice._render_lists(to_image_kw.get("sigma"), to_image_kw.get("intensity_A", 1.0),
+                                             to_image_kw.get("intensity_B", 0.5))
+    size = lattice.size
+    if like is None or _is_native(like):
+        _native.load()
+        _native.require_device()
+        device = _native.default_device() if like is None else like.device.index
+        img = _native.DeviceArray.from_numpy(np.zeros((size, size), np.float32), device)
+    else:
+        import torch
+        img = torch.zeros((size, size), dtype=torch.float32, device=like.device)
+    if len(pts) and size:
+        _render_device(img, pts, amps, sigma, 3.0, True)
+    if to_image_kw.get("normalize", False) and size:
+        operand = _Operand(img, _current_stream_ptr(img))
+        vmax = float(_stats(operand)[1])
+        if vmax > 0.0:
+            # x / vmax in float64 rounded once is the float32 quotient: 53 bits are more than 2 * 24 + 2
+            img = _map(operand, _native.MAP_DIVIDE, [vmax])
+    return img
+
+
 def _device_frame(image, what):
     if len(image.shape) != 2:
         raise ValueError(f"{what} needs a 2D image, not {len(image.shape)}-D")
