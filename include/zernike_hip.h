@@ -530,6 +530,45 @@ int zk_render_gaussians_dev(int device, void* frame_dev, int dtype, int64_t heig
                             int64_t n_points, double sigma, double r_factor, int taper, int64_t list_budget, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Faces of a planar lattice graph: the device side of the reference's graph/ subpackage (find_regions.py, and the centres,
+ * ring sizes and region adjacency that planar_graph.py derives from its result).  No plan involved.
+ * points: n_points pairs (x, y) of float64; edges: n_edges directed pairs (i, j) of int64 with values in [0, n_points) and
+ * i != j (anything else: ZK_E_BADARG; the host variant checks before anything is launched, the _dev variant on the device).
+ * Duplicated pairs collapse; pairs are NOT symmetrised: a pair given in one direction is a neighbour in one direction.
+ * Needs n_points + n_edges + 4 < 2^31.
+ *
+ * What is computed, in the reference's terms: a node is grown at (x - 1, y) of the first point of smallest x, joined to it in
+ * both directions; every node's neighbours are sorted by theta = fmod(atan2(dy, dx) + 2 pi, 2 pi) ascending (float64, ties by
+ * ascending j) into js[0 .. d); rows ("wedges") (js[t - 1], i, js[t]) for d >= 2, (js[0], -1, js[0]) for d == 1 and
+ * (i, -1, -1) for d == 0 are sorted by column 0, then column 1; the successor of (a, b, c) with b != -1 is the row starting
+ * (b, c), a row without one is a dead end.  Every cycle of the successor map is one polygon; polygons are ordered by their
+ * smallest sorted row, and polygon entry t is column 0 of the cycle's t-th row counted from that smallest row.
+ *
+ * The output sizes are not known beforehand, so a call has two phases, told apart by *state:
+ *   count   *state == NULL.  Runs the whole computation, keeps the results on the device behind *state, and writes
+ *           counts_host[0 .. 3) = {F polygons, V vertices of all polygons together, A adjacency pairs}.  The five output
+ *           pointers are not touched.  Both phases synchronise the stream (the counts cross to the host; the state is freed).
+ *   fill    *state != NULL.  Copies to the non-NULL outputs, frees the state and sets *state = NULL (call it with five NULL
+ *           outputs to just free).  points / edges / counts_host are not read.
+ *             offsets    int64 (F + 1)  polygon f is vertices[offsets[f] .. offsets[f + 1])
+ *             vertices   int64 (V)
+ *             ks         int64 (F)      offsets[f + 1] - offsets[f]
+ *             centers    float64 (F, 2) the polygon's points added one after the other in vertex order, divided by k:
+ *                                       bit-equal to NumPy's nodes[region].mean(axis=0)
+ *             adjacency  int64 (A, 2)   for every bond a < b whose half-edges a -> b and b -> a both lie on polygons, the
+ *                                       pair (polygon of a -> b, polygon of b -> a), equal entries included, in ascending
+ *                                       order of the sorted row (a, b, .)
+ * Integer work apart from the angles and the centres, no floating-point atomics: two runs agree byte for byte.
+ * zk_find_regions takes and fills host arrays; zk_find_regions_dev takes and fills device arrays on hip_stream.
+ * ------------------------------------------------------------------------------------------------------ */
+int zk_find_regions(int device, const double* points_host, int64_t n_points, const int64_t* edges_host, int64_t n_edges,
+                    void** state, int64_t* counts_host, int64_t* offsets_host, int64_t* vertices_host, int64_t* ks_host,
+                    double* centers_host, int64_t* adjacency_host);
+int zk_find_regions_dev(int device, const double* points_dev, int64_t n_points, const int64_t* edges_dev, int64_t n_edges,
+                        void** state, int64_t* counts_host, int64_t* offsets_dev, int64_t* vertices_dev, int64_t* ks_dev,
+                        double* centers_dev, int64_t* adjacency_dev, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Patch-SVD / patch-PCA denoising: the device side of the reference's denoise/ subpackage (_denoise_svd.py,
  * _denoise_svd_memory_view.py), the step ahead of background removal.  No plan involved.
  *

@@ -129,6 +129,10 @@ SYMBOLS = {
                                     c_double, c_int, c_int64]),
     "zk_render_gaussians_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                         c_double, c_double, c_int, c_int64, c_void_p]),
+    "zk_find_regions": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, POINTER(c_void_p), POINTER(c_int64), c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p]),
+    "zk_find_regions_dev": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, POINTER(c_void_p), POINTER(c_int64), c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "zk_windows_apply": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                  c_void_p, c_int64, c_void_p, c_void_p]),
     "zk_windows_apply_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,

@@ -33,7 +33,7 @@ from . import _native
 __all__ = ["shard_bounds", "one_gpu_rank_env", "RcclComm", "TorchComm", "DeviceCompute", "patch_moments_device",
            "frame_moments_device", "frame_maps_device", "normalize_image_device", "standardize_image_device",
            "percentile_clip_device", "local_max_device", "points_moments_device", "remove_background_device", "denoise_svd_device",
-           "denoise_svd_memory_view_device", "sharded_patch_moments", "sharded_frame_moments",
+           "denoise_svd_memory_view_device", "find_regions_device", "sharded_patch_moments", "sharded_frame_moments",
            "sharded_frame_maps", "sharded_frames_moments"]
 
 
@@ -453,6 +453,65 @@ def honeycomb_image_device(lattice, like=None, **to_image_kw):
             # x / vmax in float64 rounded once is the float32 quotient: 53 bits are more than 2 * 24 + 2
             img = _map(operand, _native.MAP_DIVIDE, [vmax])
     return img
+
+
+def _as_dtype_device(array, np_dtype, what):
+    """``array`` as a contiguous device array of ``np_dtype``: a torch tensor is converted on the device, a DeviceArray must
+    already have the type."""
+    if not array.is_cuda:
+        raise ValueError(f"{what} must live on the GPU")
+    if _is_native(array):
+        if array.dtype != np_dtype:
+            raise TypeError(f"{what} must be a {np.dtype(np_dtype).name} DeviceArray, not {array.dtype}")
+        return array
+    import torch
+    return array.to({np.float64: torch.float64, np.int64: torch.int64}[np_dtype]).contiguous()
+
+
+def find_regions_device(points, edges):
+    """:func:`mtflearn_amd.graph.find_regions` of points and bonds resident on the GPU: ``points`` ``(N, 2)`` (torch tensor of
+    any real type, e.g. what :func:`local_max_device` returns, converted to float64 on the device; or a float64
+    :class:`~mtflearn_amd._native.DeviceArray`), ``edges`` ``(E, 2)`` directed index pairs (torch integer tensor, or an int64
+    DeviceArray) on the same device.  Returns ``(offsets, vertices, ks, centers, adjacency)`` as device arrays of the same kind:
+    polygon ``f`` is ``vertices[offsets[f]:offsets[f + 1]]`` (int64), ``ks`` its size (int64), ``centers`` ``(F, 2)`` float64
+    bit-equal to ``nodes[region].mean(axis=0)``, ``adjacency`` ``(A, 2)`` int64 pairs of polygons that share a bond.  Only the
+    three counts cross to the host.  The edge values cannot be checked before the launch here: the device checks them, and
+    a pair outside ``[0, N)`` or a self-loop raises ``RuntimeError`` (``ZK_E_BADARG``) with nothing computed.  Runs on torch's
+    current stream, which is synchronised before the call returns."""
+    if len(points.shape) != 2 or points.shape[1] != 2:
+        raise ValueError(f"points must have shape (N, 2), not {tuple(points.shape)}")
+    if len(edges.shape) != 2 or edges.shape[1] != 2:
+        raise ValueError(f"edges must have shape (E, 2), not {tuple(edges.shape)}")
+    if not _is_native(edges) and (edges.dtype.is_floating_point or edges.dtype.is_complex or str(edges.dtype) == "torch.bool"):
+        raise ValueError(f"edges must be of an integer type, not {edges.dtype}")
+    points = _as_dtype_device(points, np.float64, "points")
+    edges = _as_dtype_device(edges, np.int64, "edges")
+    if points.device.index != edges.device.index:
+        raise ValueError("points and edges must live on the same device")
+    n, e = int(points.shape[0]), int(edges.shape[0])
+    if n + e + 4 >= 2 ** 31:
+        raise ValueError("find_regions_device needs len(points) + len(edges) + 4 < 2^31")
+    if n == 0 and e:
+        raise ValueError("edges without points")
+
+    def empty(shape, dtype):
+        if _is_native(points):
+            return _native.DeviceArray(shape, dtype, points.device.index)
+        import torch
+        return torch.empty(shape, dtype=torch.int64 if dtype == np.int64 else torch.float64, device=points.device)
+
+    lib = _native.load()
+    device, stream = points.device.index, c_void_p(_current_stream_ptr(points))
+    state, counts = c_void_p(), (c_int64 * 3)()
+    _native.check(lib.zk_find_regions_dev(device, c_void_p(points.data_ptr()), n, c_void_p(edges.data_ptr()), e, byref(state), counts,
+                                          None, None, None, None, None, stream), "zk_find_regions_dev")
+    f, v, a = (int(c) for c in counts)
+    offsets, vertices, ks = empty((f + 1,), np.int64), empty((v,), np.int64), empty((f,), np.int64)
+    centers, adjacency = empty((f, 2), np.float64), empty((a, 2), np.int64)
+    _native.check(lib.zk_find_regions_dev(device, None, 0, None, 0, byref(state), counts, c_void_p(offsets.data_ptr()),
+                                          c_void_p(vertices.data_ptr()), c_void_p(ks.data_ptr()), c_void_p(centers.data_ptr()),
+                                          c_void_p(adjacency.data_ptr()), stream), "zk_find_regions_dev")
+    return offsets, vertices, ks, centers, adjacency
 
 
 def _device_frame(image, what):

@@ -1,0 +1,451 @@
+"""mtflearn_amd.graph -- the reference's ``mtflearn.graph``: polygons ("regions": the 5-, 6-, 7-rings) of a planar lattice
+graph, their centres and ring sizes, and the graph of neighbouring polygons.
+
+``find_regions`` is the hot path.  The reference walks the faces wedge by wedge on the host, quadratic in the size of the graph;
+here the whole computation is one launch sequence on the GPU (``csrc/zk_regions.hip``: radix sorts, a successor permutation over
+the wedges, cycle labelling and ranking by pointer doubling, scans), with exact integer parity to the reference and centres
+bit-equal to ``nodes[region].mean(axis=0)``.  There is no CPU fallback: without a device ``find_regions`` and everything of
+:class:`LatticeGraph` that needs regions raises ``RuntimeError``.  The classes and the sparse-matrix helpers around it are the
+host-side bookkeeping of the reference, with its names and argument order.
+
+Deviations from the reference in ``find_regions``:
+
+* ``pts`` is converted to float64.  (The reference would compute float32 angles for float32 points.)
+* ``ijs`` must be of an integer type with values in ``[0, N)`` and no self-loops; anything else raises ``ValueError``.
+* ``N == 0`` returns the empty object array.
+* A node with out-neighbours but no in-neighbour (possible only with one-directional pairs) makes the reference index its wedge
+  groups by position instead of by node; here the successor of ``(a, b, c)`` is always the wedge that starts ``(b, c)``.
+
+Elsewhere: ``PlanarGraph.is_symmetric`` reduces the sparse difference with ``max`` (the reference's ``np.all`` of a sparse
+comparison fails on current SciPy), and ``decompose`` / ``remove_nodes`` hand the node labels on as ``lbs`` (the reference passes
+them in the ``img`` slot).
+
+Not provided: ``vnn_graph`` / ``estimate_d`` / ``vnn_distance`` (qhull Voronoi and scikit-image thresholds),
+``get_polygon_masks`` (scikit-image ``polygon2mask``), the ``show*`` and ``save`` mixins (matplotlib, h5py).  Bonds are the
+caller's, e.g. ``scipy.spatial.cKDTree(pts).query_pairs(r, output_type="ndarray")``.
+"""
+from __future__ import annotations
+
+from ctypes import byref, c_int64, c_void_p
+
+import numpy as np
+
+from . import _native
+
+__all__ = ["find_regions", "PlanarGraph", "LatticeGraph", "LatticeGraph1", "Motif", "MotifsGraph", "sort_lbs", "symmetric_edges",
+           "cantor_pairing", "construct_motif", "find_n_nodes", "matrix2edges", "matrix2ijs", "matrix2lil", "matrix2inds",
+           "edges2matrix", "ijs2matrix", "is_symmetric", "make_symmetric", "make_symmetric_more", "make_symmetric_less",
+           "get_num_faces"]
+
+
+# ---------------------------------------------------------------------------------------------------------
+# sparse-matrix helpers (reference graph/utils.py)
+# ---------------------------------------------------------------------------------------------------------
+def matrix2edges(matrix):
+    from scipy.sparse import coo_matrix
+    coo = coo_matrix(matrix)
+    return np.array([coo.row, coo.col]).T
+
+
+matrix2ijs = matrix2edges
+
+
+def matrix2lil(matrix):
+    from scipy.sparse import lil_matrix
+    return lil_matrix(matrix).rows
+
+
+matrix2inds = matrix2lil
+
+
+def edges2matrix(ijs, shape=None, fmt="coo"):
+    from scipy.sparse import coo_matrix
+    rows, cols = np.asarray(ijs).T
+    if shape is None:
+        side = int(np.max(ijs) + 1)
+        shape = (side, side)
+    matrix = coo_matrix((np.ones_like(rows), (rows, cols)), shape=shape)
+    if fmt in ("csr", "csc", "lil"):
+        matrix = matrix.asformat(fmt)
+    elif fmt == "dense":
+        matrix = np.array(matrix.todense())
+    return matrix
+
+
+def ijs2matrix(ijs, shape=None):
+    return edges2matrix(ijs, shape)
+
+
+def is_symmetric(matrix):
+    from scipy.sparse import issparse
+    if issparse(matrix):
+        from scipy.sparse.linalg import norm
+        return norm(matrix - matrix.T) == 0
+    return (matrix == matrix.T).all()
+
+
+def make_symmetric(matrix):
+    from scipy.sparse import csr_matrix, issparse, lil_matrix
+    if not issparse(matrix):
+        return np.maximum(matrix.T, matrix)
+    matrix = lil_matrix(matrix)
+    i, j = matrix.nonzero()
+    matrix[j, i] = matrix[i, j]
+    return csr_matrix(matrix)
+
+
+def make_symmetric_more(matrix):
+    """0 / 1 matrix with an entry wherever ``matrix`` or its transpose has a positive one."""
+    matrix = (matrix > 0) * 1
+    return ((matrix + matrix.T) / 2 > 0) * 1
+
+
+def make_symmetric_less(matrix):
+    """0 / 1 matrix with an entry wherever ``matrix`` and its transpose both have a positive one."""
+    matrix = (matrix > 0) * 1
+    return ((matrix + matrix.T) / 2 > 0.5) * 1
+
+
+def _num_faces_connected(matrix):
+    matrix = make_symmetric(matrix)
+    return len(matrix2ijs(matrix)) // 2 - matrix.shape[0] + 1
+
+
+def get_num_faces(matrix):
+    """Euler's count ``e - v + 1`` of bounded faces, summed over the connected components."""
+    from scipy.sparse.csgraph import connected_components
+    n_components, lbs = connected_components(matrix, directed=False)
+    if n_components == 1:
+        return _num_faces_connected(matrix)
+    faces = []
+    for e in np.unique(lbs):
+        inds = np.where(lbs == e)[0]
+        faces.append(_num_faces_connected(matrix[:, inds][inds, :]))
+    return np.sum(faces)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# label / edge helpers (reference graph/planar_graph.py)
+# ---------------------------------------------------------------------------------------------------------
+def sort_lbs(lbs):
+    """Relabel so that 0 is the most frequent label, 1 the next, ..."""
+    unique_lbs, counts = np.unique(lbs, return_counts=True)
+    unique_lbs = unique_lbs[np.argsort(counts)[::-1]]
+    order = dict(zip(unique_lbs, range(len(unique_lbs))))
+    return np.vectorize(order.get)(lbs)
+
+
+def symmetric_edges(edges):
+    return np.unique(np.vstack([edges, np.fliplr(edges)]), axis=0)
+
+
+def cantor_pairing(ij, symmetric=True):
+    ij = np.array(ij).reshape(-1, 2)
+    i, j = (ij.min(axis=1), ij.max(axis=1)) if symmetric else (ij[:, 0], ij[:, 1])
+    return (i + j) * (i + j + 1) // 2 + j
+
+
+def construct_motif(pts):
+    """The closed ring through ``pts`` in their order, as a :class:`Motif`."""
+    n = len(pts)
+    i, j = np.arange(n), np.roll(np.arange(n), 1)
+    return Motif(pts, np.vstack([np.array([i, j]).T, np.array([j, i]).T]))
+
+
+def _expand_nodes(nodes, lil):
+    grown = [nodes.tolist() + [e] for e in lil[nodes[-1]] if e not in nodes]
+    return np.array(grown if grown else [nodes.tolist() + [-1]])
+
+
+def find_n_nodes(ijs, n=2):
+    """All simple paths of ``n`` nodes along the edges ``ijs``, one per row."""
+    matrix = edges2matrix(ijs)
+    ijs = matrix2edges(matrix)
+    lil = matrix2lil(matrix)
+    for _ in range(n - 2):
+        ijs = np.vstack([_expand_nodes(row, lil) for row in ijs])
+        ijs = ijs[ijs[:, -1] != -1]
+    _, idx = np.unique(ijs, axis=0, return_index=True)
+    return ijs[idx]
+
+
+def get_connected_components(matrix):
+    from scipy.sparse.csgraph import connected_components
+    n_components, lbs = connected_components(matrix, directed=False, return_labels=True)
+    return n_components, sort_lbs(lbs)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# find_regions: the device call
+# ---------------------------------------------------------------------------------------------------------
+def _check_graph(pts, ijs):
+    """``(pts float64 (N, 2), ijs int64 (E, 2))`` C-contiguous, or ValueError; nothing is launched before this returns."""
+    pts = np.asarray(pts)
+    if pts.ndim != 2 or pts.shape[1] != 2:
+        raise ValueError(f"pts must have shape (N, 2), not {pts.shape}")
+    if pts.dtype.kind not in "fiu":
+        raise ValueError(f"pts must be real numbers, not {pts.dtype}")
+    pts = np.ascontiguousarray(pts, dtype=np.float64)
+    ijs = np.asarray(ijs)
+    if ijs.size == 0 and ijs.ndim <= 2:
+        ijs = np.empty((0, 2), np.int64)
+    if ijs.ndim != 2 or ijs.shape[1] != 2:
+        raise ValueError(f"ijs must have shape (E, 2), not {ijs.shape}")
+    if ijs.dtype.kind not in "iu":
+        raise ValueError(f"ijs must be of an integer type, not {ijs.dtype}")
+    if ijs.dtype == np.uint64 and ijs.size and ijs.max() >= len(pts):
+        raise ValueError(f"ijs must index the {len(pts)} points")
+    ijs = np.ascontiguousarray(ijs, dtype=np.int64)
+    if ijs.size:
+        if ijs.min() < 0 or ijs.max() >= len(pts):
+            raise ValueError(f"ijs must index the {len(pts)} points: values in [0, {len(pts)})")
+        if (ijs[:, 0] == ijs[:, 1]).any():
+            raise ValueError("ijs must not join a node to itself")
+    if len(pts) + len(ijs) + 4 >= 2 ** 31:
+        raise ValueError("find_regions needs len(pts) + len(ijs) + 4 < 2^31")
+    return pts, ijs
+
+
+def _regions_arrays(pts, ijs):
+    """``(offsets, vertices, ks, centers, adjacency)`` of checked host arrays, from one device call."""
+    if len(pts) == 0:
+        return (np.zeros(1, np.int64), np.empty(0, np.int64), np.empty(0, np.int64), np.empty((0, 2)), np.empty((0, 2), np.int64))
+    lib = _native.load()
+    _native.require_device()
+    device = _native.default_device()
+    state, counts = c_void_p(), (c_int64 * 3)()
+    ptr = lambda a: a.ctypes.data_as(c_void_p)
+    _native.check(lib.zk_find_regions(device, ptr(pts), len(pts), ptr(ijs), len(ijs), byref(state), counts, None, None, None, None, None),
+                  "zk_find_regions")
+    f, v, a = (int(c) for c in counts)
+    offsets, vertices, ks = np.empty(f + 1, np.int64), np.empty(v, np.int64), np.empty(f, np.int64)
+    centers, adjacency = np.empty((f, 2), np.float64), np.empty((a, 2), np.int64)
+    _native.check(lib.zk_find_regions(device, None, 0, None, 0, byref(state), counts, ptr(offsets), ptr(vertices), ptr(ks), ptr(centers),
+                                      ptr(adjacency)), "zk_find_regions")
+    return offsets, vertices, ks, centers, adjacency
+
+
+def _polygons(offsets, vertices, return_dict=False):
+    """The reference's return value from the CSR form: the same ``np.array(list, dtype=object)`` call, so polygons of one
+    common length come as a 2-D object array, as they do there."""
+    polys = np.array([vertices[offsets[f]:offsets[f + 1]] for f in range(len(offsets) - 1)], dtype=object)
+    if not return_dict:
+        return polys
+    ks = np.array([len(e) for e in polys])
+    return {str(e): np.vstack(polys[ks == e]) for e in np.unique(ks)}
+
+
+def find_regions(pts, ijs, return_dict=False):
+    """The polygons of the planar graph with nodes ``pts`` ``(N, 2)`` and directed index pairs ``ijs`` ``(E, 2)``: an object
+    array of int64 vertex arrays in the reference's order, or with ``return_dict`` a dict ``{str(k): (n_k, k) array}``.
+    Pairs are taken as given (duplicates collapse, nothing is symmetrised); a face is found when it can be walked all the way
+    round, so dangling bonds and one-directional pairs kill the faces they touch, and the outer face of the component that
+    holds the leftmost point is dropped.  Computed on the GPU (see the module docstring for the deviations)."""
+    pts, ijs = _check_graph(pts, ijs)
+    offsets, vertices = _regions_arrays(pts, ijs)[:2]
+    return _polygons(offsets, vertices, return_dict)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# graph classes (reference graph/planar_graph.py, graph/_lattice_graph.py)
+# ---------------------------------------------------------------------------------------------------------
+class PlanarGraphBase:
+    """Attribute aliases shared by the graph classes: ``pts`` / ``vertices`` are ``nodes``, ``ijs`` is ``edges``,
+    ``polys`` / ``faces`` / ``polygons`` are ``regions``.  A subclass sets ``nodes`` and ``edges``."""
+
+    aliases = {"polys": "regions", "faces": "regions", "polygons": "regions", "pts": "nodes", "vertices": "nodes", "ijs": "edges"}
+
+    def __post_init__(self):
+        for attr in ("nodes", "edges"):
+            if not hasattr(self, attr):
+                raise AttributeError(f"Missing attribute: '{attr}'")
+
+    def __setattr__(self, name, value):
+        object.__setattr__(self, self.aliases.get(name, name), value)
+
+    def __getattr__(self, name):
+        if name == "aliases":
+            raise AttributeError(name)
+        return object.__getattribute__(self, self.aliases.get(name, name))
+
+
+class PlanarGraph(PlanarGraphBase):
+    """Nodes ``(N, 2)`` and edges, the edges made symmetric (``symmetric_edges``); ``matrix`` (sparse adjacency), ``lil``
+    (neighbour lists) and ``degs`` are derived on first use."""
+
+    def __init__(self, nodes, edges):
+        self.nodes = nodes
+        self.edges = symmetric_edges(edges)
+        self._matrix = None
+        self._lil = None
+        self._degs = None
+        super().__post_init__()
+
+    @property
+    def matrix(self):
+        if self._matrix is None:
+            self._matrix = edges2matrix(self.edges, shape=(len(self.nodes), len(self.nodes)))
+        return self._matrix
+
+    @property
+    def lil(self):
+        if self._lil is None:
+            self._lil = matrix2lil(self.matrix)
+        return self._lil
+
+    @property
+    def degs(self):
+        if self._degs is None:
+            self._degs = np.array(np.sum(self.matrix, axis=1)).ravel()
+        return self._degs
+
+    def is_symmetric(self, tol=1e-8):
+        diff = abs((self.matrix - self.matrix.T).tocsr())
+        return bool(diff.nnz == 0 or diff.max() < tol)
+
+
+class LatticeGraph(PlanarGraph):
+    """A lattice of atoms and bonds.  ``regions``, ``centers`` and ``ks`` (and the region adjacency ``to_motifs_graph`` uses)
+    come from ONE device call, made on first use of any of them and cached."""
+
+    def __init__(self, nodes, edges, img=None, lbs=None):
+        super().__init__(nodes, edges)
+        self.img = img
+        self.lbs = self.degs if lbs is None else lbs
+        self._regions = None
+        self._centers = None
+        self._ks = None
+        self._adjacency = None
+        super().__post_init__()
+
+    def _compute(self):
+        if self._regions is None:
+            pts, ijs = _check_graph(self.nodes, self.edges)
+            offsets, vertices, ks, centers, adjacency = _regions_arrays(pts, ijs)
+            self._regions, self._centers, self._ks, self._adjacency = _polygons(offsets, vertices), centers, ks, adjacency
+
+    @property
+    def regions(self):
+        self._compute()
+        return self._regions
+
+    @property
+    def centers(self):
+        self._compute()
+        return self._centers
+
+    @property
+    def ks(self):
+        self._compute()
+        return self._ks
+
+    @property
+    def is_loop(self):
+        return np.all(self.degs == 2)
+
+    @property
+    def is_chain(self):
+        return sum(self.degs) == 2 * (len(self.degs) - 1)
+
+    def get_node_motifs(self):
+        """Per node, the sizes of the regions it is a vertex of (in region order)."""
+        out = [[] for _ in range(len(self.nodes))]
+        for region in self.regions:
+            for i in np.unique(np.asarray(region).astype(int)):
+                out[i].append(len(region))
+        return out
+
+    def to_motifs_graph(self):
+        motifs = np.array([construct_motif(np.asarray(self.pts)[np.asarray(region).astype(int)]) for region in self.regions], dtype=object)
+        self._compute()
+        return MotifsGraph(motifs, self.centers, self._adjacency)
+
+    def get_level1(self):
+        return self.lbs
+
+    def get_level2(self):
+        return [self.lbs[row] for row in self.lil]
+
+    def _subgraph(self, mask):
+        from scipy.sparse import lil_matrix
+        ijs = matrix2edges(lil_matrix(self.matrix)[mask, :][:, mask])
+        return LatticeGraph(self.nodes[mask], ijs, lbs=None if self.lbs is None else self.lbs[mask])
+
+    def decompose(self, min_nodes=4):
+        """One :class:`LatticeGraph` per connected component of at least ``min_nodes`` nodes."""
+        from scipy.sparse.csgraph import connected_components
+        n_components, lbs = connected_components(self.matrix, directed=False)
+        return [self._subgraph(lbs == e) for e in range(n_components) if (lbs == e).sum() >= min_nodes]
+
+    def remove_nodes(self, mask):
+        """The graph of the nodes ``mask`` keeps."""
+        return self._subgraph(mask)
+
+
+LatticeGraph1 = LatticeGraph
+
+
+class Motif(PlanarGraphBase):
+    """One ring: its points and its (symmetric) edges.  ``a + b`` merges two motifs on their shared points."""
+
+    def __init__(self, nodes, edges):
+        self.nodes = nodes
+        self.edges = symmetric_edges(edges)
+        super().__post_init__()
+
+    def __add__(self, other):
+        edge_pts = np.vstack([self.pts[self.edges].reshape(-1, 2), other.pts[other.edges].reshape(-1, 2)])
+        pts = np.unique(np.vstack([self.pts, other.pts]), axis=0)
+        ijs = np.empty(len(edge_pts))
+        for i, p in enumerate(pts):
+            ijs[(edge_pts == p).all(axis=1).nonzero()[0]] = i
+        return Motif(pts, np.unique(ijs.reshape(-1, 2).astype(int), axis=0))
+
+
+class MotifsGraph(PlanarGraphBase):
+    """The graph whose nodes are regions (``nodes``: their centres, ``motifs``: their rings, ``ks``: their sizes) and whose
+    edges join regions that share a bond."""
+
+    def __init__(self, motifs, nodes, edges, lbs=None):
+        from scipy.stats import mode
+        self.nodes = nodes
+        edges = np.asarray(edges).reshape(-1, 2).astype(np.int64)
+        self.edges = symmetric_edges(edges)
+        self.motifs = motifs
+        self.matrix = edges2matrix(self.edges, shape=(len(self.nodes), len(self.nodes)))
+        self.degs = np.array(np.sum(self.matrix, axis=1)).ravel()
+        self.ks = np.array([len(motif.pts) for motif in self.motifs])
+        self.major_k = mode(self.ks)[0]
+        self.n_components, self.component_lbs = get_connected_components(self.matrix)
+        self.lbs = lbs
+        super().__post_init__()
+
+    def _masked(self, mask, lbs=None):
+        from scipy.sparse import lil_matrix
+        ijs = matrix2edges(lil_matrix(self.matrix)[mask, :][:, mask])
+        return MotifsGraph(self.motifs[mask], self.pts[mask], ijs, lbs)
+
+    def _k_mask(self, k):
+        if k is None:
+            k = [self.major_k]
+        elif not np.iterable(k):
+            k = [k]
+        return np.isin(self.ks, k)
+
+    def select(self, k=None):
+        return self._masked(self._k_mask(k))
+
+    def select_nodes(self, mask=None, k=None):
+        if mask is None:
+            mask = self._k_mask(k)
+        return self._masked(mask, None if self.lbs is None else self.lbs[mask])
+
+    def find_n_nodes(self, n=3):
+        return find_n_nodes(self.edges, n=n)
+
+    def select_connections(self, k1k2):
+        mask = np.isin(cantor_pairing(self.ks[self.ijs]), cantor_pairing(k1k2))
+        return MotifsGraph(self.motifs, self.pts, self.ijs[mask])
+
+    def remove_edges(self, mask):
+        return MotifsGraph(self.motifs, self.pts, self.ijs[mask])
