@@ -60,7 +60,9 @@ def main():
     import regions_cases as rc
     find_regions = import_reference()["find_regions"].find_regions
     out = {}
-    for name, (pts, ijs) in rc.cases().items():
+    inputs = dict(rc.cases())
+    inputs.update({name: rc.kernel_cases()[name] for name in rc.GOLDEN_KERNEL_NAMES})     # the kernel-level cases it can reach
+    for name, (pts, ijs) in inputs.items():
         t0 = time.perf_counter()
         polys = find_regions(pts, ijs)
         seconds = time.perf_counter() - t0

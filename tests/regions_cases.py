@@ -140,3 +140,66 @@ NAMES = ["01_point", "02_triangle", "03_square_dangling", "04_two_triangles", "0
 # polygon counts worked out by hand from the rules (dead ends, the grown edge, one face per orientation of a free component)
 EXPECTED_FACES = {"01_point": 0, "02_triangle": 1, "03_square_dangling": 0, "04_two_triangles": 3, "06_one_way_triangle": 0,
                   "08_grid": 49}
+
+
+# ------------------------------------------------------------------------------------------------ kernel-level cases
+# (tests/test_gpu_regions_kernels.py; the reference is tests/regions_oracle.py, itself held to the reference's goldens on
+# GOLDEN_KERNEL_NAMES by tests/test_regions_cpu.py)
+RING_SIZES = (1021, 1022, 1023, 1024, 4093)
+TIED_NODES = (2500, 1030, 2047)                            # strides 2, 1, 1 and lanes 452, 6, 1023 of a 1024-lane sweep
+TIED_TRIANGLE_NODES = (2500, 1030, 2047, 2054)             # 2054 = 1030 + 1024: the same lane one stride later
+FAR_LEFT_TRIANGLE = [[-2000.0, 0.0], [-1990.0, 3.0], [-1995.0, 9.0]]
+
+
+def _build_kernel_cases():
+    out = {}
+    # cycles on both sides of 2^10 and 2^12 wedges; the triangle further left takes the grown edge, the ring keeps both faces
+    for n in RING_SIZES:
+        out[f"ring_{n}"] = (np.vstack([polygon(n, 1000.0, (0.0, 0.0), 0.1), FAR_LEFT_TRIANGLE]), np.vstack([ring_edges(n), ring_edges(3, n)]))
+    # a dead-end path far longer than any cycle: out along the chain and back, 10 000 wedges that must not be taken for a face
+    square = np.array([[0.0, 0.0], [4.0, 0.2], [4.1, 4.0], [0.3, 4.2]]) - [50.0, 0.0]
+    links = 5000
+    chain = np.column_stack([100.0 + np.arange(links), np.random.default_rng(3).normal(0.0, 0.2, links)])
+    hang = np.array([[1, 4]] + [(4 + k, 5 + k) for k in range(links - 1)])
+    out["chain_5000"] = (np.vstack([square, chain]), np.vstack([ring_edges(4), both_ways(hang)]))
+    # a hub with 700 neighbours: the angular sort counts a row of 700 for each of its entries
+    spokes = 700
+    out["wheel_700"] = (np.vstack([polygon(spokes, 100.0, (0.0, 0.0), 0.003), [[0.2, -0.1]]]),
+                        np.vstack([ring_edges(spokes), both_ways([(k, spokes) for k in range(spokes)])]))
+    # the same wheel with its nodes renumbered at random: the order by neighbour index has nothing to do with the order by angle
+    perm = np.random.default_rng(7).permutation(spokes + 1)
+    pts, ijs = out["wheel_700"]
+    relabelled = np.empty_like(pts)
+    relabelled[perm] = pts
+    out["wheel_700_shuffled"] = (relabelled, perm[ijs])
+    # the minimum x three times, in different lanes and strides of the argmin sweep; np.argmin takes node 1030
+    from scipy.spatial import Delaunay
+    cloud = np.random.default_rng(5).random((3000, 2)) * 100 + 1
+    cloud[list(TIED_NODES), 0] = 0.5
+    tri = Delaunay(cloud).simplices
+    out["tied_min_3000"] = (cloud, both_ways(np.vstack([tri[:, [0, 1]], tri[:, [1, 2]], tri[:, [2, 0]]])))
+    # the same tie where the choice SHOWS: 1000 separate triangles (nodes 3c, 3c + 1, 3c + 2).  A free triangle keeps two faces,
+    # one per orientation; the one that takes the grown edge loses its outer face.  That must be the triangle of node 1030.
+    rng = np.random.default_rng(6)
+    tris = np.vstack([polygon(3, 2.0, (5.0, 10.0 * c), rng.uniform(0, TWO_PI)) for c in range(1000)])
+    tris[list(TIED_TRIANGLE_NODES), 0] = 0.5
+    out["tied_min_triangles"] = (tris, np.vstack([ring_edges(3, 3 * c) for c in range(1000)]))
+    return {name: _checked(name, pts, ijs) for name, (pts, ijs) in out.items()}
+
+
+_KERNEL_CASES = None
+
+
+def kernel_cases():
+    global _KERNEL_CASES
+    if _KERNEL_CASES is None:
+        _KERNEL_CASES = _build_kernel_cases()
+    return _KERNEL_CASES
+
+
+KERNEL_NAMES = [f"ring_{n}" for n in RING_SIZES] + ["chain_5000", "wheel_700", "wheel_700_shuffled", "tied_min_3000", "tied_min_triangles"]
+GOLDEN_KERNEL_NAMES = ["ring_1024", "wheel_700"]          # the sizes the reference's quadratic walk finishes in under a minute
+
+# name -> {polygon size: count}, from the rules (and the oracle, on the CPU)
+KERNEL_EXPECTED_KS = {**{f"ring_{n}": {3: 1, n: 2} for n in RING_SIZES}, "chain_5000": {4: 1}, "wheel_700": {3: 700}, "wheel_700_shuffled": {3: 700},
+                      "tied_min_3000": {3: 5978}, "tied_min_triangles": {3: 1999}}

@@ -58,6 +58,82 @@ def test_oracle_patches_equal_the_reference(golden, name):
         np.testing.assert_array_equal(got / got.max(), golden[f"patches/{name}"][b])
 
 
+# ------------------------------------------------------------------------------------------------ the kernel-level inputs
+def _oracle(case, dtype=np.float32):
+    return oracle.render(dc.case_frame(case, dtype), case["pts"], case["amps"], case["sigma"], case["r_factor"])[0]
+
+
+@pytest.mark.parametrize("layout", ["consecutive", "spread"])
+@pytest.mark.parametrize("L", dc.SEAM_LENGTHS)
+def test_order_probes_read_as_stated_and_flip_when_swapped(L, layout):
+    """What tests/test_gpu_datasets_kernels.py asserts of the device, in the oracle's float32 model: every probed pixel is 1.0
+    (the 1 last) or 0.0 (the 1 second), nothing else is touched, and exchanging the last two points of each triple flips it."""
+    case, expect = dc.order_probe_case(L, layout)
+    assert len(expect) <= L // 3 and (L >= 3) == bool(expect) and len(case["pts"]) == L
+    if L >= 3 * (dc.TILE - 2) ** 2:
+        assert len(expect) > 180                                         # nearly every pixel the tile offers
+    values = set(v.item() for v in expect.values())
+    assert values <= {0.0, 1.0} and (len(expect) < 2 or values == {0.0, 1.0})
+    pts = case["pts"]
+    assert (pts == np.round(pts)).all() and pts.min() >= dc.TILE + 1 and pts.max() <= 2 * dc.TILE - 2     # boxes stay in the tile
+    got = _oracle(case)
+    flipped = _oracle(dc.swapped_last_two(case, L, layout))
+    rest = np.ones(case["shape"], bool)
+    for pixel, value in expect.items():
+        assert got[pixel].tobytes() == value.tobytes() and flipped[pixel] == np.float32(1.0) - value, (L, layout, pixel)
+        rest[pixel] = False
+    assert not got[rest].any() and not flipped[rest].any()
+    # the triples reach every window seam of the list
+    idx = np.flatnonzero(case["amps"])
+    assert all(((idx // 256) == w).any() for w in range(-(-L // 256))) or L < 3
+
+
+def test_seam_lists_have_exactly_L_entries():
+    R = 3.0
+    for L in dc.SEAM_LENGTHS:
+        pts = dc.seam_random_case(L)["pts"]
+        assert len(pts) == L and np.floor(pts - R).min() >= dc.TILE and np.ceil(pts + R).max() <= 2 * dc.TILE - 1
+
+
+def test_uncut_probe_reads_as_stated():
+    case, expect = dc.uncut_probe_case()
+    assert case["counts"] == [257, 257, 601, 601, 256, 256] and [e.item() for e in expect] == [1.0, 0.0] * 3
+    got, _ = oracle.render_batch(np.zeros(case["shape"], np.float32), case["pts"], case["amps"], case["counts"], case["sigma"])
+    assert [got[b][dc.UNCUT_PROBE_PIXEL].tobytes() for b in range(6)] == [e.tobytes() for e in expect]
+    swapped = case["amps"].copy()
+    for start, idx in zip(np.cumsum([0] + case["counts"][:-1]), [i for i in dc.UNCUT_PROBE_INDICES for _ in range(2)]):
+        swapped[start + idx[1]], swapped[start + idx[2]] = swapped[start + idx[2]], swapped[start + idx[1]]
+    got, _ = oracle.render_batch(np.zeros(case["shape"], np.float32), case["pts"], swapped, case["counts"], case["sigma"])
+    assert [got[b][dc.UNCUT_PROBE_PIXEL].item() for b in range(6)] == [0.0, 1.0] * 3
+    # a window walked backwards shows where a whole triple lies inside it: (1e8, -1e8, 1) reads 0.0 from the back
+    backwards = case["amps"][-512:-256][::-1]
+    got, _ = oracle.render_batch(np.zeros((1, 19, 23), np.float32), case["pts"][:256], backwards, [256], case["sigma"])
+    assert got[0][dc.UNCUT_PROBE_PIXEL].item() == 0.0
+
+
+def test_many_tile_frames_cover_the_scan():
+    for shape in dc.MANY_TILES_SHAPES:
+        case = dc.many_tiles_case(shape)
+        h, w = shape
+        tiles_x, tiles_y = -(-w // dc.TILE), -(-h // dc.TILE)
+        assert 1024 < tiles_x * tiles_y <= 2048 and len(case["pts"]) == 60
+        inside = case["pts"][(case["pts"][:, 0] >= 0) & (case["pts"][:, 0] < w) & (case["pts"][:, 1] >= 0) & (case["pts"][:, 1] < h)]
+        tile = (inside[:, 1] // dc.TILE).astype(int) * tiles_x + (inside[:, 0] // dc.TILE).astype(int)
+        assert {0, tiles_x * tiles_y - 1, tiles_x - 3, tiles_x - 2, tiles_x - 1} <= set(tile.tolist())
+        assert len(set((tile // 2).tolist())) > 25                       # scan lanes with something to add
+    assert dc.many_tiles_case((33, 8200))["pts"][:, 0].max() > 8192      # the remainder columns
+
+
+def test_cut_edge_case_is_exact_at_r_equal_R():
+    case = dc.cut_edge_case()
+    plain = oracle.render(dc.case_frame(case, np.float64), case["pts"], case["amps"], case["sigma"], case["r_factor"], taper=False)[0]
+    tapered = _oracle(case, np.float64)
+    (x, y), a = case["pts"][0].astype(int), case["amps"][0]
+    for pixel in [(y, x + 3), (y, x - 3), (y + 3, x), (y - 3, x)]:
+        assert plain[pixel] == a * np.exp(-4.5) and tapered[pixel].tobytes() == np.float64(0.0).tobytes()
+    assert np.count_nonzero(plain) == 29 and np.count_nonzero(tapered) == 25
+
+
 # ------------------------------------------------------------------------------------------------ host parts of the package
 @pytest.mark.parametrize("name", sorted(dc.LATTICES))
 def test_lattice_coordinates_equal_the_reference(golden, name):

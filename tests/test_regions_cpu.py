@@ -61,6 +61,55 @@ def test_golden_shapes_say_what_the_cases_are_for(golden):
     assert set(golden["09_wheel/ks"]) == {3} and len(golden["09_wheel/ks"]) == 20
 
 
+# ------------------------------------------------------------------------------------------------ the kernel-level cases
+@pytest.fixture(scope="module")
+def kernel_oracles():
+    return {name: oracle.regions(*case) for name, case in rc.kernel_cases().items()}
+
+
+def test_kernel_cases_are_conditioned_and_say_what_they_are_for(kernel_oracles):
+    """What tests/test_gpu_regions_kernels.py hands to the device, proven here first."""
+    cases = rc.kernel_cases()
+    assert list(cases) == rc.KERNEL_NAMES and not set(cases) & set(rc.NAMES)
+    for name, (pts, ijs) in cases.items():
+        gap, edge = rc.conditioning(pts, ijs)
+        assert gap >= rc.MIN_GAP and edge >= rc.MIN_GAP, (name, gap, edge)
+        assert pts.dtype == np.float64 and ijs.dtype == np.int64 and ijs.shape[1] == 2
+        sizes, counts = np.unique(kernel_oracles[name][2], return_counts=True)
+        assert dict(zip(sizes.tolist(), counts.tolist())) == rc.KERNEL_EXPECTED_KS[name], name
+    assert [len(cases[f"ring_{n}"][0]) - 3 for n in rc.RING_SIZES] == [1021, 1022, 1023, 1024, 4093]
+    pts, ijs = cases["chain_5000"]
+    degree = np.bincount(ijs[:, 0], minlength=len(pts))
+    assert len(pts) == 5004 and degree[1] == 3 and degree[-1] == 1 and (degree[4:-1] == 2).all()      # 2 x 5000 wedges out and back
+    assert np.bincount(cases["wheel_700"][1][:, 0]).max() == 700 == np.bincount(cases["wheel_700_shuffled"][1][:, 0]).max()
+    pts, ijs = cases["wheel_700_shuffled"]
+    hub = int(np.argmax(np.bincount(ijs[:, 0])))
+    rim = np.sort(ijs[ijs[:, 0] == hub, 1])                              # by index: not by angle
+    turn = np.diff(np.arctan2(*(pts[rim] - pts[hub]).T[::-1]))
+    assert (turn < 0).sum() > 300 and (turn > 0).sum() > 300
+    for name, tied in (("tied_min_3000", rc.TIED_NODES), ("tied_min_triangles", rc.TIED_TRIANGLE_NODES)):
+        x = cases[name][0][:, 0]
+        assert sorted(np.flatnonzero(x == x.min())) == sorted(tied) and int(np.argmin(x)) == 1030 == min(tied)
+        assert len({t // 1024 for t in tied}) > 1                                # more than one stride of a 1024-lane sweep
+    assert sorted(t % 1024 for t in rc.TIED_TRIANGLE_NODES) == [6, 6, 452, 1023]
+    # the triangle that takes the grown edge keeps one face, every other one two
+    offsets, vertices, ks, _, adjacency = kernel_oracles["tied_min_triangles"]
+    faces_of = np.bincount(vertices[offsets[:-1]] // 3, minlength=1000)
+    assert np.array_equal(np.flatnonzero(faces_of != 2), [1030 // 3]) and faces_of[1030 // 3] == 1 and len(adjacency) == 3 * 999
+
+
+@pytest.mark.parametrize("name", rc.GOLDEN_KERNEL_NAMES)
+def test_oracle_equals_reference_on_kernel_cases(golden, kernel_oracles, name):
+    """The kernel-level cases the reference's quadratic walk can reach: the yardstick of the GPU tests is the reference there."""
+    offsets, vertices, ks, centers, adjacency = kernel_oracles[name]
+    for key, got in (("offsets", offsets), ("vertices", vertices), ("ks", ks)):
+        ref = golden[f"{name}/{key}"]
+        assert got.dtype == ref.dtype == np.int64 and np.array_equal(got, ref), (name, key)
+    ref = golden[f"{name}/centers"]
+    assert centers.shape == ref.shape and centers.tobytes() == ref.tobytes(), name
+    assert oracle.symmetrised(adjacency) == oracle.symmetrised(golden[f"{name}/adjacency"]), name
+
+
 # ------------------------------------------------------------------------------------------------ host-side classes
 def test_polygons_reproduce_the_object_array_quirk(golden):
     same = graph._polygons(golden["08_grid/offsets"], golden["08_grid/vertices"])
