@@ -50,6 +50,7 @@ extern "C" {
 #define ZK_U8  2
 #define ZK_U16 3
 #define ZK_I16 4
+#define ZK_I32 5  /* int32 key points, what zk_local_max writes: accepted by zk_voronoi_cells only */
 
 /* argument-error codes (runtime failures are -hipError_t, i.e. -1 .. -1999) */
 #define ZK_E_BADARG   (-10001)
@@ -567,6 +568,51 @@ int zk_find_regions(int device, const double* points_host, int64_t n_points, con
 int zk_find_regions_dev(int device, const double* points_dev, int64_t n_points, const int64_t* edges_dev, int64_t n_edges,
                         void** state, int64_t* counts_host, int64_t* offsets_dev, int64_t* vertices_dev, int64_t* ks_dev,
                         double* centers_dev, int64_t* adjacency_dev, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Voronoi neighbours of a point set and the bonds the reference's graph/vnn.py (vnn_graph) keeps of them: the step between key
+ * points and zk_find_regions.  No plan involved.
+ * points: n_points pairs of ZK_F64, or of ZK_I32 (the (x, y) pairs zk_local_max writes, widened exactly on the device); the
+ * result does not depend on which column is x.  Needs n_points < 2^26 - 4 and pad > 0.
+ *
+ * The diagram is that of the points plus four corner points centre + (-+v, -+v) in the order (-,-) (+,-) (+,+) (-,+), with
+ * centre = mean of the points and v = max |p - centre| (1 + pad) over both coordinates (the reference's add_corner_points;
+ * centre and v are reduced on the device in float64 in a fixed order, so they may differ from NumPy's by rounding).  Every
+ * point clips its own cell, a convex polygon of at most 32 vertices, against the corners and then against the points of a
+ * uniform grid of bins in rings of growing distance, until no point farther away can reach the cell.
+ *
+ *   mode ZK_VORONOI_NEIGHBOURS  rows (i, j) for every point i and every point j whose cells share a ridge of positive length,
+ *                               with ridge[m] = that length as computed in the cell of i and edge[m] = hypot(p_j - p_i).
+ *                               dmax and threshold are ignored.
+ *   mode ZK_VORONOI_GRAPH       vnn_graph: with R_i the neighbours of i (corner points included) at less than dmax, the entry
+ *                               (i, j) is kept when j is a point of R_i and L_ij / sum over R_i of L_ik >= threshold; the rows
+ *                               are the pairs kept in either direction, in both directions.  Needs dmax > 0, threshold > 0;
+ *                               ridge / edge are not written.
+ * Rows are sorted by i, then j.
+ *
+ * Errors (ZK_E_BADARG, nothing returned, the library stays usable): a non-finite coordinate (the host variant checks before
+ * anything is launched, the _dev variant on the device; finite coordinates so large that their sum or the starting square of a
+ * cell overflows, near 1e307, count as non-finite), two coincident points, a cell that needs more than 32 vertices (a point
+ * with more than 32 Voronoi neighbours, or with nearly as many: cells are clipped in bin order and may pass their final size
+ * on the way), a cell that is convex only up to rounding (nearly coincident points).
+ * Memory: the count phase stages 32 rows per point on the device, 128 B a point in graph mode and 640 B in neighbour mode
+ * (43 GB at the limit on n_points), freed when it returns.
+ *
+ * The number of rows is not known beforehand, so a call has two phases, told apart by *state, as zk_find_regions:
+ *   count   *state == NULL.  Runs the whole computation, keeps the rows on the device behind *state and writes
+ *           counts_host[0] = M rows.  The three output pointers are not touched.  Both phases synchronise the stream.
+ *   fill    *state != NULL.  Copies to the non-NULL outputs ijs int64 (M, 2), ridge float64 (M), edge float64 (M), frees the
+ *           state and sets *state = NULL.  The other arguments are not read.
+ * No floating-point atomics, every sum in a fixed order: two runs agree byte for byte.
+ * zk_voronoi_cells takes and fills host arrays; zk_voronoi_cells_dev takes and fills device arrays on hip_stream.
+ * ------------------------------------------------------------------------------------------------------ */
+#define ZK_VORONOI_NEIGHBOURS 0
+#define ZK_VORONOI_GRAPH      1
+int zk_voronoi_cells(int device, const void* points_host, int points_dtype, int64_t n_points, double pad, int mode, double dmax,
+                     double threshold, void** state, int64_t* counts_host, int64_t* ijs_host, double* ridge_host, double* edge_host);
+int zk_voronoi_cells_dev(int device, const void* points_dev, int points_dtype, int64_t n_points, double pad, int mode, double dmax,
+                         double threshold, void** state, int64_t* counts_host, int64_t* ijs_dev, double* ridge_dev, double* edge_dev,
+                         void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Patch-SVD / patch-PCA denoising: the device side of the reference's denoise/ subpackage (_denoise_svd.py,

@@ -33,7 +33,7 @@ from . import _native
 __all__ = ["shard_bounds", "one_gpu_rank_env", "RcclComm", "TorchComm", "DeviceCompute", "patch_moments_device",
            "frame_moments_device", "frame_maps_device", "normalize_image_device", "standardize_image_device",
            "percentile_clip_device", "local_max_device", "points_moments_device", "remove_background_device", "denoise_svd_device",
-           "denoise_svd_memory_view_device", "find_regions_device", "sharded_patch_moments", "sharded_frame_moments",
+           "denoise_svd_memory_view_device", "find_regions_device", "voronoi_neighbours_device", "vnn_graph_device", "sharded_patch_moments", "sharded_frame_moments",
            "sharded_frame_maps", "sharded_frames_moments"]
 
 
@@ -512,6 +512,81 @@ def find_regions_device(points, edges):
                                           c_void_p(vertices.data_ptr()), c_void_p(ks.data_ptr()), c_void_p(centers.data_ptr()),
                                           c_void_p(adjacency.data_ptr()), stream), "zk_find_regions_dev")
     return offsets, vertices, ks, centers, adjacency
+
+
+def _voronoi_device(points, pad, mode, dmax, threshold, stream, what):
+    """Both phases of ``zk_voronoi_cells_dev`` on resident points; returns ``(ijs, ridge, edge)`` of the points' kind."""
+    if len(points.shape) != 2 or points.shape[1] != 2:
+        raise ValueError(f"points must have shape (N, 2), not {tuple(points.shape)}")
+    if not points.is_cuda:
+        raise ValueError("points must live on the GPU")
+    if not (np.isfinite(pad) and pad > 0):
+        raise ValueError(f"pad must be positive and finite, not {pad}")
+    if _is_native(points):
+        if points.dtype not in (np.float64, np.int32):
+            raise TypeError(f"points must be a float64 or int32 DeviceArray, not {points.dtype}")
+        code = _native.ZK_F64 if points.dtype == np.float64 else _native.ZK_I32
+    else:
+        import torch
+        if points.dtype.is_complex or points.dtype == torch.bool:
+            raise ValueError(f"points must be real numbers, not {points.dtype}")
+        if points.dtype not in (torch.float64, torch.int32):
+            points = points.to(torch.float64)
+        points = points.contiguous()
+        code = _native.ZK_F64 if points.dtype == torch.float64 else _native.ZK_I32
+    n = int(points.shape[0])
+    if n + 4 >= 2 ** 26:
+        raise ValueError(f"{what} needs len(points) < 2^26 - 4")
+
+    def empty(shape, dtype):
+        if _is_native(points):
+            return _native.DeviceArray(shape, dtype, points.device.index)
+        import torch
+        return torch.empty(shape, dtype=torch.int64 if dtype == np.int64 else torch.float64, device=points.device)
+
+    lengths = mode == _native.VORONOI_NEIGHBOURS
+    if n == 0:
+        return empty((0, 2), np.int64), empty((0,), np.float64), empty((0,), np.float64)
+    lib = _native.load()
+    device = points.device.index
+    if stream is None:
+        stream = _current_stream_ptr(points)
+    stream = c_void_p(int(getattr(stream, "cuda_stream", stream)))
+    state, counts = c_void_p(), (c_int64 * 1)()
+    _native.check(lib.zk_voronoi_cells_dev(device, c_void_p(points.data_ptr()), code, n, pad, mode, dmax, threshold, byref(state), counts,
+                                           None, None, None, stream), "zk_voronoi_cells_dev")
+    m = int(counts[0])
+    ijs = empty((m, 2), np.int64)
+    ridge, edge = (empty((m,), np.float64), empty((m,), np.float64)) if lengths else (None, None)
+    _native.check(lib.zk_voronoi_cells_dev(device, None, code, 0, pad, mode, dmax, threshold, byref(state), counts, c_void_p(ijs.data_ptr()),
+                                           c_void_p(ridge.data_ptr()) if lengths else None, c_void_p(edge.data_ptr()) if lengths else None,
+                                           stream), "zk_voronoi_cells_dev")
+    return ijs, ridge, edge
+
+
+def voronoi_neighbours_device(points, pad=0.05, stream=None):
+    """:func:`mtflearn_amd.graph.voronoi_neighbours` of points resident on the GPU: ``points`` ``(N, 2)``, a torch tensor of
+    any real type or a float64 / int32 :class:`~mtflearn_amd._native.DeviceArray`.  What :func:`local_max_device` returns --
+    ``(N, 2)`` int32, column 0 is x, column 1 is y -- is taken as it is and widened on the device; the neighbours do not depend
+    on which column is x.  Returns ``(ijs, ridge_lengths, edge_lengths)`` as device arrays of the same kind (int64 ``(M, 2)``,
+    float64 ``(M)``, float64 ``(M)``).  Only the row count crosses to the host.  The values cannot be checked before the launch
+    here: the device checks them, and a non-finite coordinate, two coincident points or a cell of more than 32 vertices (a point
+    with more than 32 Voronoi neighbours, or nearly as many: cells are clipped in bin order) raise ``RuntimeError``
+    (``ZK_E_BADARG``) with nothing computed.  Runs on ``stream`` (default: torch's current stream for tensors, the default
+    stream for a DeviceArray), which is synchronised before the call returns."""
+    return _voronoi_device(points, float(pad), _native.VORONOI_NEIGHBOURS, 0.0, 0.0, stream, "voronoi_neighbours_device")
+
+
+def vnn_graph_device(points, dmax, threshold=0.1, pad=0.05, stream=None):
+    """:func:`mtflearn_amd.graph.vnn_graph` of points resident on the GPU (see :func:`voronoi_neighbours_device` for the
+    operands, the errors and the stream): the int64 ``(E, 2)`` sorted, symmetrised bonds as a device array of the points'
+    kind, ready for :func:`find_regions_device` -- key points go from :func:`local_max_device` to polygons without a host copy."""
+    dmax, threshold = float(dmax), float(threshold)
+    if not dmax > 0:
+        raise ValueError(f"dmax must be positive, not {dmax}")
+    if not threshold > 0:
+        raise ValueError(f"threshold must be > 0, not {threshold}")
+    return _voronoi_device(points, float(pad), _native.VORONOI_GRAPH, dmax, threshold, stream, "vnn_graph_device")[0]
 
 
 def _device_frame(image, what):

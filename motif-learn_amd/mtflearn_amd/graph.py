@@ -20,9 +20,17 @@ Elsewhere: ``PlanarGraph.is_symmetric`` reduces the sparse difference with ``max
 comparison fails on current SciPy), and ``decompose`` / ``remove_nodes`` hand the node labels on as ``lbs`` (the reference passes
 them in the ``img`` slot).
 
-Not provided: ``vnn_graph`` / ``estimate_d`` / ``vnn_distance`` (qhull Voronoi and scikit-image thresholds),
-``get_polygon_masks`` (scikit-image ``polygon2mask``), the ``show*`` and ``save`` mixins (matplotlib, h5py).  Bonds are the
-caller's, e.g. ``scipy.spatial.cKDTree(pts).query_pairs(r, output_type="ndarray")``.
+Bonds come from ``vnn_graph`` (reference ``graph/vnn.py``): the Voronoi neighbours of the points plus four far corner points
+(``add_corner_points``), cut at ``dmax`` and at a share ``threshold`` of each row's summed ridge lengths, symmetrised by OR.
+The diagram is not qhull's: every point clips its own cell on the GPU (``csrc/zk_voronoi.hip``), and ``voronoi_neighbours``
+returns what the graph is made of.  Deviations, each a ``ValueError`` before any launch: ``dmax`` must be given (the reference's
+default goes through ``estimate_d`` and scikit-image's thresholds), ``threshold`` must be ``> 0`` (at ``<= 0`` the reference's
+sparse comparison densifies), ``pts`` must be finite and free of coincident points (qhull drops duplicates silently and the
+reference's indexing then shifts); a cell may have at most 32 vertices (``RuntimeError`` from the device for a point with more
+Voronoi neighbours, or with nearly as many: cells are clipped in bin order and may pass their final size on the way).
+
+Not provided: ``estimate_d`` / ``vnn_distance`` (scikit-image thresholds; Delaunay edges of the unpadded hull),
+``get_polygon_masks`` (scikit-image ``polygon2mask``), the ``show*`` and ``save`` mixins (matplotlib, h5py).
 """
 from __future__ import annotations
 
@@ -32,7 +40,7 @@ import numpy as np
 
 from . import _native
 
-__all__ = ["find_regions", "PlanarGraph", "LatticeGraph", "LatticeGraph1", "Motif", "MotifsGraph", "sort_lbs", "symmetric_edges",
+__all__ = ["add_corner_points", "voronoi_neighbours", "vnn_graph", "find_regions", "PlanarGraph", "LatticeGraph", "LatticeGraph1", "Motif", "MotifsGraph", "sort_lbs", "symmetric_edges",
            "cantor_pairing", "construct_motif", "find_n_nodes", "matrix2edges", "matrix2ijs", "matrix2lil", "matrix2inds",
            "edges2matrix", "ijs2matrix", "is_symmetric", "make_symmetric", "make_symmetric_more", "make_symmetric_less",
            "get_num_faces"]
@@ -244,6 +252,95 @@ def find_regions(pts, ijs, return_dict=False):
     pts, ijs = _check_graph(pts, ijs)
     offsets, vertices = _regions_arrays(pts, ijs)[:2]
     return _polygons(offsets, vertices, return_dict)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# vnn_graph: Voronoi-neighbour bonds (reference graph/vnn.py)
+# ---------------------------------------------------------------------------------------------------------
+def add_corner_points(pts, pad=0.05):
+    """``pts`` with four points appended, ``centre + (-+v, -+v)`` in the order ``(-,-) (+,-) (+,+) (-,+)``, where
+    ``centre = pts.mean(axis=0)`` and ``v = max|pts - centre| * (1 + pad)``: they close every Voronoi cell.  Host NumPy."""
+    pts = np.asarray(pts)
+    center = pts.mean(axis=0)
+    v = np.abs(pts - center).max() * (1 + pad)
+    return np.vstack([pts, np.array([(-v, -v), (+v, -v), (+v, +v), (-v, +v)]) + center])
+
+
+def _check_points(pts, pad):
+    """``pts`` float64 ``(N, 2)`` C-contiguous, finite and without coincident points, or ValueError; nothing is launched
+    before this returns."""
+    pts = np.asarray(pts)
+    if pts.ndim != 2 or pts.shape[1] != 2:
+        raise ValueError(f"pts must have shape (N, 2), not {pts.shape}")
+    if pts.dtype.kind not in "fiu":
+        raise ValueError(f"pts must be real numbers, not {pts.dtype}")
+    pts = np.ascontiguousarray(pts, dtype=np.float64)
+    if not np.isfinite(pts).all():
+        raise ValueError("pts must be finite")
+    if len(pts) + 4 >= 2 ** 26:
+        raise ValueError("the Voronoi neighbours need len(pts) < 2^26 - 4")
+    if len(pts) > 1 and len(np.unique(pts, axis=0)) != len(pts):
+        raise ValueError("pts holds coincident points")
+    if not (np.isfinite(pad) and pad > 0):
+        raise ValueError(f"pad must be positive and finite, not {pad}")
+    return pts
+
+
+def _voronoi_rows(pts, pad, mode, dmax, threshold):
+    """``(ijs, ridge, edge)`` of checked host points, from one device call (``ridge`` / ``edge`` only in neighbour mode)."""
+    lengths = mode == _native.VORONOI_NEIGHBOURS
+    if len(pts) == 0:
+        return np.empty((0, 2), np.int64), np.empty(0), np.empty(0)
+    lib = _native.load()
+    _native.require_device()
+    device = _native.default_device()
+    state, counts = c_void_p(), (c_int64 * 1)()
+    ptr = lambda a: a.ctypes.data_as(c_void_p)
+    _native.check(lib.zk_voronoi_cells(device, ptr(pts), _native.ZK_F64, len(pts), pad, mode, dmax, threshold, byref(state), counts,
+                                       None, None, None), "zk_voronoi_cells")
+    m = int(counts[0])
+    ijs, ridge, edge = np.empty((m, 2), np.int64), np.empty(m if lengths else 0), np.empty(m if lengths else 0)
+    _native.check(lib.zk_voronoi_cells(device, None, _native.ZK_F64, 0, pad, mode, dmax, threshold, byref(state), counts, ptr(ijs),
+                                       ptr(ridge) if lengths else None, ptr(edge) if lengths else None), "zk_voronoi_cells")
+    return ijs, ridge, edge
+
+
+def voronoi_neighbours(pts, pad=0.05):
+    """``(ijs, ridge_lengths, edge_lengths)``: for every point ``i`` every point ``j`` whose Voronoi cells share a ridge of
+    positive length in the diagram of ``add_corner_points(pts, pad)``.  ``ijs`` is int64 ``(M, 2)``, sorted lexicographically,
+    every pair in both directions; ``ridge_lengths[m]`` is the float64 length of the ridge as computed in the cell of ``i``,
+    ``edge_lengths[m]`` is ``hypot(dx, dy)``.  Not a reference function: it is what ``vnn_graph`` is made of, and a source of
+    ``dmax`` (a multiple of ``np.median(edge_lengths)``).  Computed on the GPU; centre and ``v`` of the corner points are
+    reduced there and may differ from NumPy's by rounding."""
+    pts = _check_points(pts, pad)
+    return _voronoi_rows(pts, float(pad), _native.VORONOI_NEIGHBOURS, 0.0, 0.0)
+
+
+def vnn_graph(pts, threshold=0.1, dmax=None, threshold_method=None, return_ijs=True):
+    """The reference's ``vnn_graph``: bonds between Voronoi neighbours.  With ``R_i`` the Voronoi neighbours of point ``i``
+    (the four corner points included) closer than ``dmax``, the entry ``(i, j)`` is kept when ``j`` is a point of ``R_i`` and its
+    ridge is at least ``threshold`` of the summed ridge lengths of ``R_i``; the result is every pair kept in either direction, in
+    both directions: int64 ``(E, 2)`` sorted lexicographically, or with ``return_ijs=False`` the SciPy CSR matrix of ones of
+    shape ``(N, N)``.  Computed on the GPU.
+
+    Deviations from the reference, each a ``ValueError`` before any launch: ``dmax=None`` is refused (the reference estimates
+    it with scikit-image's Li / Otsu thresholds) -- pass a distance, e.g. 1.3 times the median of
+    ``voronoi_neighbours(pts)[2]``; ``threshold_method`` is accepted and ignored; ``threshold`` must be ``> 0``; ``pts`` must
+    be finite ``(N, 2)`` (converted to float64) without coincident points; ``N == 0`` returns the empty ``(0, 2)`` array."""
+    if dmax is None:
+        raise ValueError("vnn_graph needs dmax: the reference's estimate (estimate_d, scikit-image thresholds) is not provided; "
+                         "pass a distance, e.g. 1.3 * np.median(voronoi_neighbours(pts)[2])")
+    dmax, threshold = float(dmax), float(threshold)
+    if not dmax > 0:
+        raise ValueError(f"dmax must be positive, not {dmax}")
+    if not threshold > 0:
+        raise ValueError(f"threshold must be > 0, not {threshold}")
+    pts = _check_points(pts, 0.05)
+    ijs = _voronoi_rows(pts, 0.05, _native.VORONOI_GRAPH, dmax, threshold)[0]
+    if return_ijs:
+        return ijs
+    from scipy.sparse import csr_matrix
+    return csr_matrix((np.ones(len(ijs), np.int64), (ijs[:, 0], ijs[:, 1])), shape=(len(pts), len(pts)))
 
 
 # ---------------------------------------------------------------------------------------------------------
