@@ -50,7 +50,7 @@ extern "C" {
 #define ZK_U8  2
 #define ZK_U16 3
 #define ZK_I16 4
-#define ZK_I32 5  /* int32 key points, what zk_local_max writes: accepted by zk_voronoi_cells only */
+#define ZK_I32 5  /* int32 key points, what zk_local_max writes: accepted by zk_voronoi_cells and zk_knn_distances only */
 
 /* argument-error codes (runtime failures are -hipError_t, i.e. -1 .. -1999) */
 #define ZK_E_BADARG   (-10001)
@@ -613,6 +613,67 @@ int zk_voronoi_cells(int device, const void* points_host, int points_dtype, int6
 int zk_voronoi_cells_dev(int device, const void* points_dev, int points_dtype, int64_t n_points, double pad, int mode, double dmax,
                          double threshold, void** state, int64_t* counts_host, int64_t* ijs_dev, double* ridge_dev, double* edge_dev,
                          void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Sub-pixel refinement of key points: the reference's center_of_mass_refine (features/_keypoint.py:12-23), the step between
+ * zk_local_max and zk_voronoi_cells.  No plan involved.
+ * image: (H, W) of ZK_F32 or ZK_F64.  points: n_points int32 pairs (x, y), what zk_local_max writes.  out: float64 (n_points, 2),
+ * rows (x, y).  mode: ZK_REFINE_BOX (the (2 size + 1)^2 box) or ZK_REFINE_DISK (its pixels with dx^2 + dy^2 <= size^2).
+ *
+ * What is computed: the regions are painted in point order into one label image, so a pixel belongs to the LAST point whose box
+ * covers it; in disk mode the corners of that last box paint 0 and such a pixel belongs to nobody, even where an earlier disk
+ * covered it.  Per point three float64 sums over its pixels in raveled (row-major) order -- value, value * (double)row,
+ * value * (double)col, each product rounded once -- and x = sum(value * col) / sum(value), y = sum(value * row) / sum(value):
+ * bit-equal to scipy.ndimage.center_of_mass on that label image.  A point left with no pixels gives NaN, NaN (0 / 0).
+ *
+ * Errors (ZK_E_BADARG, nothing returned): a dtype other than the two float types, n_points >= 2^24 (the reference's label image
+ * has the frame's type), size outside [0, 64], a box that leaves the frame (every point needs size <= x < W - size and
+ * size <= y < H - size; the host variant checks before anything is launched, the _dev variant on the device, where such a point
+ * paints and reads nothing).
+ * Memory: an int32 owner image of H x W, freed when the call returns.  Integer atomics only: two runs agree byte for byte.
+ * zk_refine_points takes and fills host arrays; zk_refine_points_dev takes and fills device arrays on hip_stream, which is
+ * synchronised before it returns (the error flag crosses to the host).
+ * ------------------------------------------------------------------------------------------------------ */
+#define ZK_REFINE_BOX  0
+#define ZK_REFINE_DISK 1
+int zk_refine_points(int device, const void* image_host, int image_dtype, int64_t H, int64_t W, const int32_t* points_host,
+                     int64_t n_points, int64_t size, int mode, double* out_host);
+int zk_refine_points_dev(int device, const void* image_dev, int image_dtype, int64_t H, int64_t W, const int32_t* points_dev,
+                         int64_t n_points, int64_t size, int mode, double* out_dev, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * The device passes of the reference's estimate_d (graph/vnn.py:18-40): the bond length vnn_graph cuts at when no dmax is given.
+ * No plan involved.
+ *
+ * zk_knn_distances: out float64 (n_points, k), the k smallest Euclidean distances sqrt(dx * dx + dy * dy) (float64, not fused) of
+ * every point to the points of the set, itself included (column 0 is 0; a coincident point adds another 0), ascending.
+ * points as for zk_voronoi_cells (ZK_F64 or ZK_I32 pairs).  Needs 1 <= k <= 12, k <= n_points < 2^26, finite points
+ * (ZK_E_BADARG otherwise).  Points are binned on a uniform grid and every point searches rings of bins until its k-th best is
+ * no farther than anything an unvisited ring can hold.
+ *
+ * zk_knn_stats: one reduction over dd, the (n_points, 12) matrix zk_knn_distances writes at k = 12, for the eleven nested
+ * samples d_k = dd[:, 1:k], k = 2 .. 12 (index c = k - 2 below).  params_host / counts_host / sums_host are HOST arrays:
+ *   ZK_KNN_RANGES  sums[0] = min of column 1, sums[j] = max of column j, j = 1 .. 11: d_k spans [sums[0], sums[k - 1]].
+ *   ZK_KNN_HIST    params = {first, last[11], edges[11][257]}; counts[c][256] = np.histogram(d_k, bins=256)[0] under NumPy's own
+ *                  rule: index (v - first) / (last_c - first) * 256 truncated, 256 folded into 255, one down when
+ *                  v < edges[index], one up when v >= edges[index + 1] outside the last bin.  Needs last_c > first.
+ *   ZK_KNN_SIDES   params = {shift, t[11]}; with w = v - shift: counts[c] = number of w > t_c in d_k, sums[2 c] = their sum,
+ *                  sums[2 c + 1] = the sum of the others.  Fixed summation tree, no floating-point atomics.
+ *   ZK_KNN_GAPS    params = {shift}, shift <= every value; sums[c] = the smallest positive difference between two values
+ *                  w = v - shift of d_k (a radix sort of the bit patterns and adjacent differences), +inf when all are equal.
+ * Both calls synchronise the stream.  The _dev variants take device arrays (points, out, dd) on hip_stream.
+ * ------------------------------------------------------------------------------------------------------ */
+#define ZK_KNN_RANGES 0
+#define ZK_KNN_HIST   1
+#define ZK_KNN_SIDES  2
+#define ZK_KNN_GAPS   3
+int zk_knn_distances(int device, const void* points_host, int points_dtype, int64_t n_points, int k, double* out_host);
+int zk_knn_distances_dev(int device, const void* points_dev, int points_dtype, int64_t n_points, int k, double* out_dev,
+                         void* hip_stream);
+int zk_knn_stats(int device, const double* dd_host, int64_t n_points, int op, const double* params_host, int64_t* counts_host,
+                 double* sums_host);
+int zk_knn_stats_dev(int device, const double* dd_dev, int64_t n_points, int op, const double* params_host, int64_t* counts_host,
+                     double* sums_host, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Patch-SVD / patch-PCA denoising: the device side of the reference's denoise/ subpackage (_denoise_svd.py,

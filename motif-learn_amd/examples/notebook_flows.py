@@ -4,6 +4,7 @@
   notebook 2 (batch):  key points -> patches -> ZPs.fit_transform(patches) -> rotation-invariant |Z_nm| -> rot_maps
   notebook 3 (dense):  ZPs.fit_transform(frame) -> rot_maps / mirror_map / |Z_nm| maps
   resident chain:      lattice rendered on the device -> denoise -> background removal -> local maxima -> moments at them
+  refined chain:       the same key points -> sub-pixel centroids -> bond length -> Voronoi bonds -> polygons, all resident
 
 Only the import line differs from the reference (`from mtflearn import ZPs`).  Needs an MI355X.
 Run:  python motif-learn_amd/examples/notebook_flows.py
@@ -70,6 +71,19 @@ def main():
     inner = keep[(keep.min(axis=1) >= 2 * size) & (keep.max(axis=1) < 1024 - 2 * size)]
     dist = np.hypot(inner[:, None, 0] - sites[None, :, 0], inner[:, None, 1] - sites[None, :, 1]).min(axis=1)
     print(f"         {len(inner)} interior peaks, farthest from a lattice site: {dist.max():.2f} px")
+
+    # ---- the refined chain: key points -> centroids -> estimate_d -> bonds -> polygons, nothing but scalars on the host ------
+    from mtflearn_amd.distributed import estimate_d_device, find_regions_device, refine_points_device, vnn_graph_device
+    t = time.perf_counter()
+    d_keep = _native.DeviceArray.from_numpy(keep.astype(np.int32))
+    atoms = refine_points_device(clean, d_keep, size=3)                    # reference: KeyPoints.refine(r=3); (N, 2) float64 (x, y)
+    dmax = estimate_d_device(atoms, threshold="otsu")                      # reference: estimate_d(pts)
+    bonds = vnn_graph_device(atoms, dmax)                                  # vnn_graph_device(atoms) alone estimates with Li, as the reference
+    offsets, vertices, ks, centers, adjacency = find_regions_device(atoms, bonds)
+    print(f"refined: refine -> estimate_d ({dmax:.2f} px) -> vnn_graph {bonds.shape} -> find_regions in {1e3 * (time.perf_counter() - t):.1f} ms;"
+          f" {int((ks.numpy() == 6).sum())} hexagons of {len(ks)} polygons")
+    moved = atoms.numpy() - keep
+    print(f"         centroids moved the key points by at most {np.abs(moved).max():.2f} px")
 
 
 if __name__ == "__main__":

@@ -17,8 +17,11 @@ import numpy as np
 
 ZK_F32, ZK_F64 = 0, 1
 ZK_U8, ZK_U16, ZK_I16 = 2, 3, 4   # host-buffer entry points only: widened to float32 on the device (exact)
-ZK_I32 = 5                         # int32 key points (local_max): zk_voronoi_cells only
+ZK_E_BADARG = -10001                # zernike_hip.h: a refused argument
+ZK_I32 = 5                         # int32 key points (local_max): zk_voronoi_cells and zk_knn_distances only
 VORONOI_NEIGHBOURS, VORONOI_GRAPH = 0, 1                           # zk_voronoi_cells modes
+REFINE_BOX, REFINE_DISK = 0, 1                                     # zk_refine_points modes
+KNN_RANGES, KNN_HIST, KNN_SIDES, KNN_GAPS = 0, 1, 2, 3             # zk_knn_stats ops
 PATH_AUTO, PATH_GENERIC, PATH_FOLDED, PATH_SEPARABLE, PATH_STREAM, PATH_DIRECT = 0, 1, 2, 3, 4, 5
 OP_POINTS, OP_MAPS = 1, 2
 STATS_CENTERED, STATS_WIDE = 1, 2                                  # zk_image_stats modes
@@ -139,6 +142,12 @@ SYMBOLS = {
                                  c_void_p, c_void_p, c_void_p]),
     "zk_voronoi_cells_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_double, c_int, c_double, c_double, POINTER(c_void_p),
                                      POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "zk_refine_points": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p]),
+    "zk_refine_points_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "zk_knn_distances": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_void_p]),
+    "zk_knn_distances_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p]),
+    "zk_knn_stats": (c_int, [c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "zk_knn_stats_dev": (c_int, [c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "zk_windows_apply": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                  c_void_p, c_int64, c_void_p, c_void_p]),
     "zk_windows_apply_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,

@@ -33,7 +33,8 @@ from . import _native
 __all__ = ["shard_bounds", "one_gpu_rank_env", "RcclComm", "TorchComm", "DeviceCompute", "patch_moments_device",
            "frame_moments_device", "frame_maps_device", "normalize_image_device", "standardize_image_device",
            "percentile_clip_device", "local_max_device", "points_moments_device", "remove_background_device", "denoise_svd_device",
-           "denoise_svd_memory_view_device", "find_regions_device", "voronoi_neighbours_device", "vnn_graph_device", "sharded_patch_moments", "sharded_frame_moments",
+           "denoise_svd_memory_view_device", "find_regions_device", "voronoi_neighbours_device", "vnn_graph_device", "refine_points_device",
+           "estimate_d_device", "sharded_patch_moments", "sharded_frame_moments",
            "sharded_frame_maps", "sharded_frames_moments"]
 
 
@@ -577,10 +578,97 @@ def voronoi_neighbours_device(points, pad=0.05, stream=None):
     return _voronoi_device(points, float(pad), _native.VORONOI_NEIGHBOURS, 0.0, 0.0, stream, "voronoi_neighbours_device")
 
 
-def vnn_graph_device(points, dmax, threshold=0.1, pad=0.05, stream=None):
+def _knn_points(points, what):
+    """``(points, ZK_* code)`` of resident ``(N, 2)`` points for ``zk_knn_distances_dev``: float64 or int32 as they are, any
+    other real torch type converted to float64 on the device."""
+    if len(points.shape) != 2 or points.shape[1] != 2:
+        raise ValueError(f"points must have shape (N, 2), not {tuple(points.shape)}")
+    if not points.is_cuda:
+        raise ValueError("points must live on the GPU")
+    if _is_native(points):
+        if points.dtype not in (np.float64, np.int32):
+            raise TypeError(f"points must be a float64 or int32 DeviceArray, not {points.dtype}")
+        return points, _native.ZK_F64 if points.dtype == np.float64 else _native.ZK_I32
+    import torch
+    if points.dtype.is_complex or points.dtype == torch.bool:
+        raise ValueError(f"points must be real numbers, not {points.dtype}")
+    if points.dtype not in (torch.float64, torch.int32):
+        points = points.to(torch.float64)
+    points = points.contiguous()
+    n = int(points.shape[0])
+    if n >= 2 ** 26:
+        raise ValueError(f"{what} needs len(points) < 2^26")
+    return points, _native.ZK_F64 if points.dtype == torch.float64 else _native.ZK_I32
+
+
+def estimate_d_device(points, threshold='otsu', return_k=False):
+    """:func:`mtflearn_amd.graph.estimate_d` of points resident on the GPU: ``points`` ``(N, 2)``, a torch tensor of any real
+    type or a float64 / int32 :class:`~mtflearn_amd._native.DeviceArray` -- what :func:`local_max_device` or
+    :func:`refine_points_device` return.  The points and their distance matrix stay on the device; a few hundred numbers per
+    pass (ranges, histograms, side sums) cross to the host, where the scalar rules run.  ``N < 12`` raises ``ValueError``;
+    a non-finite coordinate raises ``RuntimeError`` from the device.  Runs on torch's current stream."""
+    from . import graph
+    points, code = _knn_points(points, "estimate_d_device")
+    n = int(points.shape[0])
+    if n < graph.KNN:
+        raise ValueError(f"Expected n_neighbors <= n_samples_fit, but n_neighbors = {graph.KNN}, n_samples_fit = {n}")
+    device, stream = points.device.index, _current_stream_ptr(points)
+    dd = _empty_like((n, graph.KNN), points)
+    _native.check(_native.load().zk_knn_distances_dev(device, c_void_p(points.data_ptr()), code, n, graph.KNN, c_void_p(dd.data_ptr()),
+                                                      c_void_p(stream)), "zk_knn_distances_dev")
+    parts = graph._estimate_from_distances(device, dd.data_ptr(), n, stream, threshold)
+    return (parts["t"], parts["k"]) if return_k else parts["t"]
+
+
+def refine_points_device(image, points, size=3, mode=None):
+    """:func:`mtflearn_amd.features.refine_points` of a frame and key points resident on the GPU: ``image`` ``(H, W)`` float32 /
+    float64, ``points`` ``(N, 2)`` int32 ``(x, y)`` (what :func:`local_max_device` returns), both torch tensors or both
+    :class:`~mtflearn_amd._native.DeviceArray`.  Returns the ``(N, 2)`` float64 ``(x, y)`` centroids on the device, of the same
+    kind -- what :func:`vnn_graph_device`, :func:`estimate_d_device` and :func:`find_regions_device` accept; round them to
+    int32 for :func:`points_moments_device`.  The numbers are those of the host ``center_of_mass_refine``, bit for bit.  A
+    frame that is not float, ``N >= 2^24`` or a box that leaves the frame raise ``ValueError`` (the boxes are checked on the
+    device: nothing is written for such a point, and only the flag crosses to the host).  Runs on torch's current stream."""
+    if len(image.shape) != 2:
+        raise ValueError(f"refine_points_device needs a 2D image, not {len(image.shape)}-D")
+    if not image.is_cuda or not points.is_cuda:
+        raise ValueError("image and points must live on the GPU")
+    if _is_native(image) != _is_native(points) or image.device.index != points.device.index:
+        raise ValueError("image and points must be of one kind and on one device")
+    try:
+        code = _dtype_code(image)
+    except TypeError as e:
+        raise ValueError(f"refine_points_device needs a float frame: {e}") from None
+    if len(points.shape) != 2 or points.shape[1] != 2 or not (
+            points.dtype == np.int32 if _is_native(points) else str(points.dtype) == "torch.int32"):
+        raise TypeError("points must be an (N, 2) int32 array of (x, y)")
+    if not _is_native(image):
+        image, points = image.contiguous(), points.contiguous()
+    size = int(size)
+    if not 0 <= size <= 64:
+        raise ValueError(f"size must be in [0, 64], not {size}")
+    n = int(points.shape[0])
+    if n >= 2 ** 24:
+        raise ValueError("refine_points_device needs len(points) < 2^24 (the reference's label image has the frame's type)")
+    h, w = (int(v) for v in image.shape)
+    out = _empty_like((n, 2), image)
+    if n:
+        lib = _native.load()
+        rc = lib.zk_refine_points_dev(image.device.index, c_void_p(image.data_ptr()), code, h, w, c_void_p(points.data_ptr()), n, size,
+                                      _native.REFINE_DISK if mode == 'disk' else _native.REFINE_BOX, c_void_p(out.data_ptr()),
+                                      c_void_p(_current_stream_ptr(image)))
+        if rc == _native.ZK_E_BADARG:
+            raise ValueError(_native.last_error())
+        _native.check(rc, "zk_refine_points_dev")
+    return out
+
+
+def vnn_graph_device(points, dmax=None, threshold=0.1, pad=0.05, stream=None, threshold_method=None):
     """:func:`mtflearn_amd.graph.vnn_graph` of points resident on the GPU (see :func:`voronoi_neighbours_device` for the
     operands, the errors and the stream): the int64 ``(E, 2)`` sorted, symmetrised bonds as a device array of the points'
-    kind, ready for :func:`find_regions_device` -- key points go from :func:`local_max_device` to polygons without a host copy."""
+    kind, ready for :func:`find_regions_device` -- key points go from :func:`local_max_device` to polygons without a host copy.
+    Without ``dmax`` it is ``estimate_d_device(points, threshold=threshold_method)``, as in the reference."""
+    if dmax is None:
+        dmax = estimate_d_device(points, threshold=threshold_method)
     dmax, threshold = float(dmax), float(threshold)
     if not dmax > 0:
         raise ValueError(f"dmax must be positive, not {dmax}")

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["disk_patch", "center_of_mass_refine", "com_refine", "clear_border", "KeyPoints"]
+__all__ = ["disk_patch", "center_of_mass_refine", "refine_points", "com_refine", "clear_border", "KeyPoints"]
 
 
 def _interior(pts, x_limit, y_limit, size):
@@ -46,6 +46,43 @@ def center_of_mass_refine(data, pts, size=3, mode=None):
         owner[py - size:py + size + 1, px - size:px + size + 1] = label * stamp
     yx = np.array(ndimage.center_of_mass(data, owner, list(range(1, len(pts) + 1))))
     return yx[:, ::-1]
+
+
+def refine_points(data, pts, size=3, mode=None):
+    """``center_of_mass_refine(data, pts, size, mode)`` on the GPU (``zk_refine_points``): NumPy in, NumPy out, the same float64
+    ``(N, 2)`` rows ``(x, y)`` bit for bit -- the last point whose box covers a pixel owns it, a disk's box corners belong to
+    nobody, a point left with no pixels gives ``nan, nan``.  What the kernel does not take raises ``ValueError`` naming the
+    condition, and the host function remains for those cases: ``data`` must be a 2-D float32 / float64 frame, ``pts`` integer
+    ``(N, 2)`` with ``N < 2^24``, and every box must lie inside the frame (``KeyPoints`` guarantees it by border clearing)."""
+    from ctypes import c_void_p
+    from .. import _native
+    data, pts = np.asarray(data), np.asarray(pts)
+    if data.ndim != 2 or data.dtype not in (np.float32, np.float64):
+        raise ValueError(f"refine_points needs a 2-D float32 or float64 frame, not {data.ndim}-D {data.dtype}")
+    if pts.size == 0:
+        pts = pts.reshape(0, 2).astype(np.int32)
+    if pts.ndim != 2 or pts.shape[1] != 2 or pts.dtype.kind not in "iu":
+        raise ValueError(f"refine_points needs integer points of shape (N, 2), not {pts.dtype} {pts.shape}")
+    if len(pts) >= 2 ** 24:
+        raise ValueError("refine_points needs len(pts) < 2^24 (the reference's label image has the frame's type)")
+    size = int(size)
+    if not 0 <= size <= 64:
+        raise ValueError(f"size must be in [0, 64], not {size}")
+    height, width = data.shape
+    if len(pts) and not ((pts[:, 0] >= size).all() and (pts[:, 0] < width - size).all() and (pts[:, 1] >= size).all()
+                         and (pts[:, 1] < height - size).all()):
+        raise ValueError("refine_points needs every box inside the frame: size <= x < W - size and size <= y < H - size")
+    out = np.empty((len(pts), 2), np.float64)
+    if len(pts) == 0:
+        return out
+    data, pts = np.ascontiguousarray(data), np.ascontiguousarray(pts, dtype=np.int32)
+    lib = _native.load()
+    _native.require_device()
+    _native.check(lib.zk_refine_points(_native.default_device(), data.ctypes.data_as(c_void_p), _native.dtype_code(data.dtype), height, width,
+                                       pts.ctypes.data_as(c_void_p), len(pts), size,
+                                       _native.REFINE_DISK if mode == 'disk' else _native.REFINE_BOX, out.ctypes.data_as(c_void_p)),
+                  "zk_refine_points")
+    return out
 
 
 def com_refine(pts, img, size, threshold=None):
@@ -99,3 +136,8 @@ class KeyPoints:
     def refine(self, data=None, r=3, mode=None):
         """Replace the points by the intensity centroids around their integer parts (``center_of_mass_refine``)."""
         self.pts = center_of_mass_refine(self.img if data is None else data, self.pts.astype(int), size=r, mode=mode)
+
+    def refine_gpu(self, data=None, r=3, mode=None):
+        """:meth:`refine` on the GPU (extension, in the spirit of :meth:`moments`): the same truncation ``pts.astype(int)``, the
+        same numbers (:func:`refine_points`)."""
+        self.pts = refine_points(self.img if data is None else data, self.pts.astype(int), size=r, mode=mode)

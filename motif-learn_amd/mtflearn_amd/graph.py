@@ -23,13 +23,26 @@ them in the ``img`` slot).
 Bonds come from ``vnn_graph`` (reference ``graph/vnn.py``): the Voronoi neighbours of the points plus four far corner points
 (``add_corner_points``), cut at ``dmax`` and at a share ``threshold`` of each row's summed ridge lengths, symmetrised by OR.
 The diagram is not qhull's: every point clips its own cell on the GPU (``csrc/zk_voronoi.hip``), and ``voronoi_neighbours``
-returns what the graph is made of.  Deviations, each a ``ValueError`` before any launch: ``dmax`` must be given (the reference's
-default goes through ``estimate_d`` and scikit-image's thresholds), ``threshold`` must be ``> 0`` (at ``<= 0`` the reference's
+returns what the graph is made of.  Without ``dmax`` the bond length comes from ``estimate_d``, as in the reference (below).
+Deviations, each a ``ValueError`` before any launch: ``threshold`` must be ``> 0`` (at ``<= 0`` the reference's
 sparse comparison densifies), ``pts`` must be finite and free of coincident points (qhull drops duplicates silently and the
 reference's indexing then shifts); a cell may have at most 32 vertices (``RuntimeError`` from the device for a point with more
 Voronoi neighbours, or with nearly as many: cells are clipped in bin order and may pass their final size on the way).
 
-Not provided: ``estimate_d`` / ``vnn_distance`` (scikit-image thresholds; Delaunay edges of the unpadded hull),
+``estimate_d`` (reference ``graph/vnn.py:18-40``) keeps the reference's signature and rule: for ``k = 2 .. 12`` the distances to
+the nearest ``k - 1`` neighbours are thresholded (Otsu, or Li's minimum cross-entropy for anything but ``'otsu'``) and the
+threshold that splits its sample most evenly wins.  The device does every pass over the data (``csrc/zk_refine.hip``: the
+12-neighbour distance matrix on a grid of bins, one pass for the eleven ranges, one for the eleven 256-bin histograms under
+NumPy's own binning rule, one fixed-tree reduction per Li iteration, a radix sort for Li's tolerance); the host applies the
+scalar rules to a few hundred numbers with NumPy.  The two thresholds are this project's statements of the published
+algorithms (Otsu 1979; Li and Tam 1998 as scikit-image iterates it): scikit-image is not installed where this is tested, so
+parity with ``skimage.filters.threshold_otsu`` / ``threshold_li`` is UNPINNED; what is pinned is tests/thresholds_reference.py,
+an independent NumPy / scikit-learn statement of the same definitions.  Li's loop ends when two iterates differ by no more
+than half the smallest gap between distinct values; on a perfect lattice those gaps are rounding noise and the published loop
+need not end (``estimate_d`` raises ``RuntimeError`` after 1000 iterations) -- measured points, or a few per cent of jitter, end
+it in a handful.
+
+Not provided: ``vnn_distance`` (Delaunay edges of the unpadded hull),
 ``get_polygon_masks`` (scikit-image ``polygon2mask``), the ``show*`` and ``save`` mixins (matplotlib, h5py).
 """
 from __future__ import annotations
@@ -40,7 +53,7 @@ import numpy as np
 
 from . import _native
 
-__all__ = ["add_corner_points", "voronoi_neighbours", "vnn_graph", "find_regions", "PlanarGraph", "LatticeGraph", "LatticeGraph1", "Motif", "MotifsGraph", "sort_lbs", "symmetric_edges",
+__all__ = ["add_corner_points", "voronoi_neighbours", "vnn_graph", "knn_distances", "estimate_d", "find_regions", "PlanarGraph", "LatticeGraph", "LatticeGraph1", "Motif", "MotifsGraph", "sort_lbs", "symmetric_edges",
            "cantor_pairing", "construct_motif", "find_n_nodes", "matrix2edges", "matrix2ijs", "matrix2lil", "matrix2inds",
            "edges2matrix", "ijs2matrix", "is_symmetric", "make_symmetric", "make_symmetric_more", "make_symmetric_less",
            "get_num_faces"]
@@ -316,20 +329,160 @@ def voronoi_neighbours(pts, pad=0.05):
     return _voronoi_rows(pts, float(pad), _native.VORONOI_NEIGHBOURS, 0.0, 0.0)
 
 
+# ---------------------------------------------------------------------------------------------------------
+# estimate_d: the bond length (reference graph/vnn.py:18-40)
+# ---------------------------------------------------------------------------------------------------------
+KNN = 12                                             # columns of the distance matrix: self and eleven neighbours
+KS = tuple(range(2, KNN + 1))                        # the reference's ks
+LI_MAX_ITERATIONS = 1000
+
+
+def _check_knn_points(pts, k):
+    """``pts`` float64 ``(N, 2)`` C-contiguous and finite with ``N >= k``, or ValueError; nothing is launched before this."""
+    pts = np.asarray(pts)
+    if pts.ndim != 2 or pts.shape[1] != 2:
+        raise ValueError(f"pts must have shape (N, 2), not {pts.shape}")
+    if pts.dtype.kind not in "fiu":
+        raise ValueError(f"pts must be real numbers, not {pts.dtype}")
+    pts = np.ascontiguousarray(pts, dtype=np.float64)
+    if not np.isfinite(pts).all():
+        raise ValueError("pts must be finite")
+    if not 1 <= k <= KNN:
+        raise ValueError(f"k must be in [1, {KNN}], not {k}")
+    if len(pts) < k:                                 # scikit-learn's kneighbors raises the same way
+        raise ValueError(f"Expected n_neighbors <= n_samples_fit, but n_neighbors = {k}, n_samples_fit = {len(pts)}")
+    if len(pts) >= 2 ** 26:
+        raise ValueError("the neighbour distances need len(pts) < 2^26")
+    return pts
+
+
+def knn_distances(pts, k=12):
+    """float64 ``(N, k)``: the ``k <= 12`` smallest Euclidean distances of every point to the points of ``pts``, itself included
+    (column 0 is 0), ascending -- ``NearestNeighbors(k).fit(pts).kneighbors(pts)[0]``.  Computed on the GPU on a uniform grid
+    of bins (``zk_knn_distances``); ``N < k`` raises ``ValueError`` as scikit-learn does."""
+    k = int(k)
+    pts = _check_knn_points(pts, k)
+    lib = _native.load()
+    _native.require_device()
+    out = np.empty((len(pts), k), np.float64)
+    _native.check(lib.zk_knn_distances(_native.default_device(), pts.ctypes.data_as(c_void_p), _native.ZK_F64, len(pts), k,
+                                       out.ctypes.data_as(c_void_p)), "zk_knn_distances")
+    return out
+
+
+def _knn_stats(device, dd_ptr, n, op, params, stream):
+    """``(counts int64 (11 * 256), sums float64 (22))`` of one ``zk_knn_stats_dev`` call on a resident distance matrix."""
+    counts, sums = np.zeros(len(KS) * 256, np.int64), np.zeros(2 * len(KS), np.float64)
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    _native.check(_native.load().zk_knn_stats_dev(device, c_void_p(dd_ptr), n, op, params.ctypes.data_as(c_void_p),
+                                                  counts.ctypes.data_as(c_void_p), sums.ctypes.data_as(c_void_p), c_void_p(stream)),
+                  "zk_knn_stats_dev")
+    return counts, sums
+
+
+def _otsu_from_counts(counts, edges):
+    """Otsu's threshold of a histogram: the centre of the bin that maximises the between-class variance."""
+    centers = (edges[:-1] + edges[1:]) / 2
+    w1 = np.cumsum(counts)
+    w2 = np.cumsum(counts[::-1])[::-1]
+    m1 = np.cumsum(counts * centers) / w1
+    m2 = (np.cumsum((counts * centers)[::-1]) / w2[::-1])[::-1]
+    return centers[np.argmax(w1[:-1] * w2[1:] * (m1[:-1] - m2[1:]) ** 2)]
+
+
+def _otsu_thresholds(stats, first, lasts, parts):
+    edges = [np.linspace(first, last if last > first else first + 1.0, 257) for last in lasts]
+    params = np.concatenate([[first], [e[-1] for e in edges]] + edges)
+    counts = stats(_native.KNN_HIST, params)[0].reshape(len(KS), 256)
+    parts["counts"] = counts
+    return [first if last == first else _otsu_from_counts(counts[c], edges[c]) for c, last in enumerate(lasts)]
+
+
+def _li_thresholds(stats, n, first, lasts, parts):
+    lens = np.array([n * (k - 1) for k in KS], np.float64)
+    tol = stats(_native.KNN_GAPS, [first])[1][:len(KS)] / 2
+    flat = np.array([last == first for last in lasts])                 # all values equal: that value is the threshold
+    total = stats(_native.KNN_SIDES, [first] + [np.inf] * len(KS))[1][1::2]
+    t_next, t_curr = total / lens, -2 * tol
+    active, iterations = ~flat, np.zeros(len(KS), np.int64)
+    with np.errstate(all="ignore"):
+        while True:
+            active &= np.abs(t_next - t_curr) > tol
+            if not active.any():
+                break
+            if iterations.max() >= LI_MAX_ITERATIONS:
+                raise RuntimeError(f"estimate_d: Li's iteration has not ended after {LI_MAX_ITERATIONS} steps (on a perfect lattice the "
+                                   "gaps between distinct distances are rounding noise: jitter the points or use threshold='otsu')")
+            t_curr = np.where(active, t_next, t_curr)
+            counts, sums = stats(_native.KNN_SIDES, np.concatenate([[first], t_curr]))
+            above = counts[:len(KS)].astype(np.float64)
+            mean_fore, mean_back = sums[0::2] / above, sums[1::2] / (lens - above)
+            iterations += active
+            active &= mean_back != 0
+            step = (mean_back - mean_fore) / (np.log(mean_back) - np.log(mean_fore))
+            t_next = np.where(active, step, t_next)
+    parts["iterations"], parts["tolerance"] = iterations, tol
+    return [first if flat[c] else t_next[c] + first for c in range(len(KS))]
+
+
+def _estimate_from_distances(device, dd_ptr, n, stream, threshold):
+    """The reference's rule on a resident ``(n, 12)`` distance matrix; returns the parts ``estimate_d`` is made of."""
+    stats = lambda op, params: _knn_stats(device, dd_ptr, n, op, params, stream)
+    ranges = stats(_native.KNN_RANGES, [0.0])[1]
+    first, lasts = ranges[0], ranges[1:KNN]
+    parts = {"first": first, "lasts": lasts}
+    ts = _otsu_thresholds(stats, first, lasts, parts) if threshold == 'otsu' else _li_thresholds(stats, n, first, lasts, parts)
+    ts = np.array(ts, np.float64)
+    above = stats(_native.KNN_SIDES, np.concatenate([[0.0], ts]))[0][:len(KS)]
+    lens = np.array([n * (k - 1) for k in KS])
+    scores = (above / lens) * ((lens - above) / lens)
+    best = int(np.argmax(scores))
+    parts.update(ts=ts, above=above, scores=scores, t=float(ts[best]), k=KS[best])
+    return parts
+
+
+def _estimate_d_parts(pts, threshold='otsu'):
+    """``estimate_d`` with everything it is made of (``ts``, ``scores``, ``counts`` or ``iterations``, ``dd``): what the tests
+    and tools/time_refine.py read."""
+    pts = _check_knn_points(pts, KNN)
+    _native.require_device()
+    device = _native.default_device()
+    d_pts = _native.DeviceArray.from_numpy(pts, device)
+    dd = _native.DeviceArray((len(pts), KNN), np.float64, device)
+    _native.check(_native.load().zk_knn_distances_dev(device, c_void_p(d_pts.data_ptr()), _native.ZK_F64, len(pts), KNN,
+                                                      c_void_p(dd.data_ptr()), c_void_p(0)), "zk_knn_distances_dev")
+    parts = _estimate_from_distances(device, dd.data_ptr(), len(pts), 0, threshold)
+    parts["dd"] = dd
+    return parts
+
+
+def estimate_d(pts, threshold='otsu', return_k=False):
+    """The reference's ``estimate_d``: the bond length of a point set.  For every ``k = 2 .. 12`` the distances of all points
+    to their ``k - 1`` nearest neighbours are thresholded -- ``threshold='otsu'``: Otsu on a 256-bin histogram; anything else:
+    Li's minimum cross-entropy, as in the reference -- and the threshold whose two sides are most even
+    (``count(d > t) count(d <= t) / len(d)^2``, first maximum) is returned, with ``return_k`` together with its ``k``.
+    Computed on the GPU (see the module docstring: which passes, and that parity with scikit-image is unpinned).  ``N < 12``
+    raises ``ValueError`` as scikit-learn's query does.  Li needs points that are not a perfect lattice."""
+    parts = _estimate_d_parts(pts, threshold)
+    return (parts["t"], parts["k"]) if return_k else parts["t"]
+
+
 def vnn_graph(pts, threshold=0.1, dmax=None, threshold_method=None, return_ijs=True):
     """The reference's ``vnn_graph``: bonds between Voronoi neighbours.  With ``R_i`` the Voronoi neighbours of point ``i``
     (the four corner points included) closer than ``dmax``, the entry ``(i, j)`` is kept when ``j`` is a point of ``R_i`` and its
     ridge is at least ``threshold`` of the summed ridge lengths of ``R_i``; the result is every pair kept in either direction, in
     both directions: int64 ``(E, 2)`` sorted lexicographically, or with ``return_ijs=False`` the SciPy CSR matrix of ones of
-    shape ``(N, N)``.  Computed on the GPU.
+    shape ``(N, N)``.  Computed on the GPU.  Without ``dmax`` it is ``estimate_d(pts, threshold=threshold_method)``, as in the
+    reference (``None`` means Li there, and here).
 
-    Deviations from the reference, each a ``ValueError`` before any launch: ``dmax=None`` is refused (the reference estimates
-    it with scikit-image's Li / Otsu thresholds) -- pass a distance, e.g. 1.3 times the median of
-    ``voronoi_neighbours(pts)[2]``; ``threshold_method`` is accepted and ignored; ``threshold`` must be ``> 0``; ``pts`` must
+    Deviations from the reference, each a ``ValueError`` before any launch: ``threshold`` must be ``> 0``; ``pts`` must
     be finite ``(N, 2)`` (converted to float64) without coincident points; ``N == 0`` returns the empty ``(0, 2)`` array."""
     if dmax is None:
-        raise ValueError("vnn_graph needs dmax: the reference's estimate (estimate_d, scikit-image thresholds) is not provided; "
-                         "pass a distance, e.g. 1.3 * np.median(voronoi_neighbours(pts)[2])")
+        if np.ndim(pts) == 2 and len(pts) < KNN:     # scikit-learn's refusal, with the way out
+            raise ValueError(f"vnn_graph without dmax estimates it from the {KNN} nearest neighbours (estimate_d): Expected n_neighbors <= "
+                             f"n_samples_fit, but n_neighbors = {KNN}, n_samples_fit = {len(pts)}; pass dmax, e.g. "
+                             "1.3 * np.median(voronoi_neighbours(pts)[2])")
+        dmax = estimate_d(pts, threshold=threshold_method)
     dmax, threshold = float(dmax), float(threshold)
     if not dmax > 0:
         raise ValueError(f"dmax must be positive, not {dmax}")
