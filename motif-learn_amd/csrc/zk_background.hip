@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "zk_internal.h"
+#include "zk_scratch.h"
 
 namespace {
 
@@ -37,23 +38,6 @@ constexpr int RB_TY = 4;                 // output rows per wave
 constexpr int RB_WAVES = 4;
 constexpr int RB_TW = 64 * RB_NX, RB_TH = RB_WAVES * RB_TY;
 constexpr int RB_MAX_R = 1536;           // two staged rows of (RB_TW + 2 R) float64 stay within 64 KiB of LDS
-
-struct dev_buf {
-  void* p = nullptr;
-  ~dev_buf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    ZK_HIP(hipMalloc(&p, bytes ? bytes : 16));
-    return 0;
-  }
-  template <typename T>
-  T* as() const {
-    return (T*)p;
-  }
-};
-
-inline unsigned blocks_of(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 size_t element_size(int dtype) { return dtype == ZK_F64 ? 8 : dtype == ZK_F32 ? 4 : dtype == ZK_U8 ? 1 : 2; }
 

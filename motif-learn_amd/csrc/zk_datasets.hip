@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "zk_internal.h"
+#include "zk_scratch.h"
 
 namespace {
 
@@ -36,21 +37,6 @@ constexpr int SORT_CAP = 1024;            // list entries sorted in LDS; longer 
 constexpr int64_t DEFAULT_BUDGET = (int64_t)1 << 24;   // list entries (int32) per point range: 64 MiB
 
 enum { MODE_UNCUT = 0, MODE_CUT = 1, MODE_TAPER = 2 };
-
-struct dev_buf {
-  void* p = nullptr;
-  ~dev_buf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    ZK_HIP(hipMalloc(&p, bytes ? bytes : 16));
-    return 0;
-  }
-  template <typename T>
-  T* as() const {
-    return (T*)p;
-  }
-};
 
 struct point {
   double x, y, a;

@@ -28,29 +28,13 @@
 #include <vector>
 
 #include "zk_internal.h"
+#include "zk_scratch.h"
 
 namespace {
 
 constexpr int ZK_DN_LC = 16;        // columns of Q / Y per pass of apply and apply_t
 constexpr int ZK_DN_CHUNKS = 512;   // most window chunks of apply_t
 constexpr int ZK_DN_MAX_P = 48;     // largest patch edge of the moments kernel (its border tables stay within 64 KiB of LDS)
-
-struct dev_buf {
-  void* p = nullptr;
-  ~dev_buf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    ZK_HIP(hipMalloc(&p, bytes ? bytes : 16));
-    return 0;
-  }
-  template <typename T>
-  T* as() const {
-    return (T*)p;
-  }
-};
-
-inline unsigned blocks_of(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 size_t element_size(int dtype) { return dtype == ZK_F64 ? 8 : dtype == ZK_F32 ? 4 : dtype == ZK_U8 ? 1 : 2; }
 

@@ -29,6 +29,7 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 
 #include "zk_internal.h"
+#include "zk_scratch.h"
 
 namespace {
 
@@ -40,21 +41,6 @@ constexpr size_t TILE_LDS_MAX = 60 * 1024;  // + 4 KiB of static LDS: within the
 constexpr int ROUNDS_PER_CHECK = 4;  // suppression launches between two reads of the undecided counter
 
 thread_local int64_t g_last_launches = 0;
-
-struct dev_buf {
-  void* p = nullptr;
-  ~dev_buf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    ZK_HIP(hipMalloc(&p, bytes ? bytes : 16));
-    return 0;
-  }
-  template <typename T>
-  T* as() const {
-    return (T*)p;
-  }
-};
 
 // order-preserving unsigned images of the value bits (-0.0 folded onto +0.0, which compares equal to it)
 __device__ __forceinline__ unsigned long long ordered64(double v) {
@@ -263,8 +249,6 @@ __global__ __launch_bounds__(256) void points_kernel(const int32_t* __restrict__
   out[2 * j + 1] = p / W;
 }
 
-inline unsigned blocks_of(long long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
-
 template <typename T>
 int launch_front(const void* img, int H, int W, unsigned long long* mm, int has_threshold, double threshold, uint8_t* flag,
                  hipStream_t s) {
@@ -295,8 +279,10 @@ int sort_candidates(const void* img, const int32_t* pix, int n, int32_t* pix_sor
 template <typename K>
 size_t sort_temp_bytes(int n) {
   size_t bytes = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, bytes, (K*)nullptr, (K*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, n, 0,
-                                  8 * (unsigned)sizeof(K), (hipStream_t)0);
+  (void)zk_prim_bytes(&bytes, [&](void* p, size_t& b) {
+    return rocprim::radix_sort_pairs(p, b, (K*)nullptr, (K*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, n, 0, 8 * (unsigned)sizeof(K),
+                                     (hipStream_t)0);
+  });
   return bytes;
 }
 
@@ -305,7 +291,8 @@ int local_max_core(const void* img, int dtype, int H, int W, double r, int has_t
                    int64_t capacity, int64_t* n_found, hipStream_t s) {
   g_last_launches = 0;
   const long long npx = (long long)H * W;
-  dev_buf d_mm, d_flag, d_count, d_temp;
+  dev_buf d_mm, d_flag, d_count;
+  temp_store tmp;
   int rc;
   if ((rc = d_mm.alloc(16)) || (rc = d_flag.alloc((size_t)npx)) || (rc = d_count.alloc(8))) return rc;
   switch (dtype) {
@@ -320,12 +307,11 @@ int local_max_core(const void* img, int dtype, int H, int W, double r, int has_t
   // raster-ordered candidate list (the count crosses to the host: it sizes everything after)
   dev_buf d_pix;
   if ((rc = d_pix.alloc((size_t)npx * 4))) return rc;
-  size_t sel_bytes = 0;
-  ZK_HIP(rocprim::select(nullptr, sel_bytes, rocprim::counting_iterator<int32_t>(0), d_flag.as<uint8_t>(), d_pix.as<int32_t>(),
-                         d_count.as<unsigned int>(), (size_t)npx, s));
-  if ((rc = d_temp.alloc(sel_bytes))) return rc;
-  ZK_HIP(rocprim::select(d_temp.p, sel_bytes, rocprim::counting_iterator<int32_t>(0), d_flag.as<uint8_t>(), d_pix.as<int32_t>(),
-                         d_count.as<unsigned int>(), (size_t)npx, s));
+  if ((rc = zk_prim(tmp, [&](void* p, size_t& b) {
+         return rocprim::select(p, b, rocprim::counting_iterator<int32_t>(0), d_flag.as<uint8_t>(), d_pix.as<int32_t>(),
+                                d_count.as<unsigned int>(), (size_t)npx, s);
+       })))
+    return rc;
   unsigned int n_cand = 0;
   ZK_HIP(hipMemcpyAsync(&n_cand, d_count.p, 4, hipMemcpyDeviceToHost, s));
   ZK_HIP(hipStreamSynchronize(s));
@@ -338,9 +324,12 @@ int local_max_core(const void* img, int dtype, int H, int W, double r, int has_t
   const size_t key_size = wide ? 8 : 4;
   dev_buf d_keys, d_sorted, d_rank, d_state, d_temp2;
   const size_t sort_bytes = wide ? sort_temp_bytes<unsigned long long>(n) : sort_temp_bytes<unsigned int>(n);
+  // the kept candidates in priority order (run after the suppression); one allocation serves the sort and this select
+  const auto select_kept = [&](void* p, size_t& b) {
+    return rocprim::select(p, b, d_sorted.as<int32_t>(), d_state.as<uint8_t>(), d_pix.as<int32_t>(), d_count.as<unsigned int>(), (size_t)n, s);
+  };
   size_t kept_bytes = 0;
-  ZK_HIP(rocprim::select(nullptr, kept_bytes, d_sorted.as<int32_t>(), d_state.as<uint8_t>(), d_pix.as<int32_t>(),
-                         d_count.as<unsigned int>(), (size_t)n, s));
+  if ((rc = zk_prim_bytes(&kept_bytes, select_kept))) return rc;
   size_t temp2_bytes = std::max(sort_bytes, kept_bytes);
   if ((rc = d_keys.alloc((size_t)n * 2 * key_size)) || (rc = d_sorted.alloc((size_t)n * 4)) || (rc = d_rank.alloc((size_t)npx * 4)) ||
       (rc = d_state.alloc((size_t)n)) || (rc = d_temp2.alloc(temp2_bytes)))
@@ -405,9 +394,7 @@ int local_max_core(const void* img, int dtype, int H, int W, double r, int has_t
     if (launch > (long long)n + N_COUNTERS) return zk_fail(ZK_E_BADARG, "local_max: suppression made no progress");
   }
 
-  // kept candidates in priority order
-  ZK_HIP(rocprim::select(d_temp2.p, temp2_bytes, d_sorted.as<int32_t>(), d_state.as<uint8_t>(), d_pix.as<int32_t>(),
-                         d_count.as<unsigned int>(), (size_t)n, s));
+  ZK_HIP(select_kept(d_temp2.p, temp2_bytes));
   unsigned int n_kept = 0;
   ZK_HIP(hipMemcpyAsync(&n_kept, d_count.p, 4, hipMemcpyDeviceToHost, s));
   ZK_HIP(hipStreamSynchronize(s));

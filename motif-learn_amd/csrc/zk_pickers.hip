@@ -20,6 +20,7 @@
 #include <hipfft/hipfft.h>  // types and prototypes only; nothing here links against libhipfft
 
 #include "zk_internal.h"
+#include "zk_scratch.h"
 
 namespace {
 
@@ -122,21 +123,6 @@ struct fft_plan {
     key = fft_cached{device, ny, nx, batch, h};
     live = true;
     return 0;
-  }
-};
-
-struct dev_buf {
-  void* p = nullptr;
-  ~dev_buf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    ZK_HIP(hipMalloc(&p, bytes ? bytes : 16));
-    return 0;
-  }
-  template <typename T>
-  T* as() const {
-    return (T*)p;
   }
 };
 
@@ -341,8 +327,6 @@ __global__ __launch_bounds__(256) void to_complex_kernel(const T* __restrict__ i
     out[t].y = 0.0;
   }
 }
-
-inline unsigned blocks_of(long long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
 // Bit pattern of the k-th largest (k >= 1) of n non-negative doubles v[0], v[stride], ... and the number of strictly
 // larger ones: radix select, four passes of 16-bit histograms (`d_hist`: 65536 counters on the device).

@@ -19,9 +19,8 @@
 //
 // B. zk_knn_distances.  The k <= 12 smallest Euclidean distances of every point to the points of the set, itself included
 //   (column 0 is 0), ascending.
-//   frame        one workgroup: the bounding box of the points (min / max are order-free); a G x G grid of square bins over it,
-//                G = ceil(sqrt(N / 2)), as zk_voronoi.hip bins its points (about two a bin on a uniform set).
-//   bins         points radix-sorted by bin (rocPRIM), bin starts by lower bounds in the sorted keys.
+//   frame        one workgroup: the bounding box of the points (min / max are order-free), with square bins over it.
+//   bins         the point grid of zk_point_grid.h over that box.
 //   search       one lane per point in bin order.  The running list of 12 distances lives in registers (an insertion network
 //                unrolled over the 12 slots, no run-time index).  Bins are visited in rings of growing Chebyshev distance r
 //                around the point's own bin; every point not yet seen lies outside the box of the rings searched, so the
@@ -50,6 +49,8 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "zk_internal.h"
+#include "zk_point_grid.h"
+#include "zk_scratch.h"
 
 namespace {
 
@@ -58,30 +59,12 @@ typedef unsigned long long u64;
 constexpr int KNN = 12;                              // columns of the distance matrix
 constexpr int NK = 11;                               // the samples d_2 .. d_12
 constexpr int BINS = 256;                            // np.histogram(bins=256)
-constexpr int MAX_GRID = 4096;                       // bins per axis at most
 constexpr int MAX_SIZE = 64;                         // half-width of a refinement box at most
 constexpr int RED_BLOCKS = 512;                      // workgroups of a reduction at most
 constexpr double SLACK = 1e-9;
 constexpr double DBL_BIG = 1.7976931348623157e308;
 
-enum { ERR_BOX = 1, ERR_NONFINITE = 2 };
-
-struct dev_buf {
-  void* p = nullptr;
-  ~dev_buf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    ZK_HIP(hipMalloc(&p, bytes ? bytes : 16));
-    return 0;
-  }
-  template <typename T>
-  T* as() const {
-    return (T*)p;
-  }
-};
-
-inline unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256); }
+enum { ERR_BOX = 1 };                                // the flag of refine_points (knn_distances has ERR_NONFINITE in a flag of its own)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // A. centroid refinement
@@ -174,34 +157,8 @@ int refine_call(const void* img, int dtype, int64_t H, int64_t W, const int* pts
 // B. nearest-neighbour distances
 // ---------------------------------------------------------------------------------------------------------------------
 
-struct knn_frame {
-  double x0, y0, h;                                  // grid origin and bin side
-  int g;
-};
-
-__device__ inline int bin_of(double u, int g) {
-  const double f = floor(u);
-  return f >= (double)(g - 1) ? g - 1 : (f > 0 ? (int)f : 0);      // NaN goes to 0
-}
-
-__global__ __launch_bounds__(256) void load_points_kernel(const void* __restrict__ in, int dtype, long long n, double2* __restrict__ pts,
-                                                          int* __restrict__ flag) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  double x, y;
-  if (dtype == ZK_I32) {
-    x = (double)((const int*)in)[2 * i];
-    y = (double)((const int*)in)[2 * i + 1];
-  } else {
-    x = ((const double*)in)[2 * i];
-    y = ((const double*)in)[2 * i + 1];
-  }
-  if (!(fabs(x) <= DBL_BIG) || !(fabs(y) <= DBL_BIG)) atomicOr(flag, ERR_NONFINITE);
-  pts[i] = make_double2(x, y);
-}
-
 // one workgroup: the bounding box and the grid over it
-__global__ __launch_bounds__(1024) void knn_frame_kernel(const double2* __restrict__ pts, long long n, int g, knn_frame* __restrict__ out) {
+__global__ __launch_bounds__(1024) void knn_frame_kernel(const double2* __restrict__ pts, long long n, int g, zk_grid_frame* __restrict__ out) {
   __shared__ double s[4][1024];
   const int t = threadIdx.x;
   double xlo = DBL_BIG, xhi = -DBL_BIG, ylo = DBL_BIG, yhi = -DBL_BIG;
@@ -226,7 +183,7 @@ __global__ __launch_bounds__(1024) void knn_frame_kernel(const double2* __restri
     __syncthreads();
   }
   if (t == 0) {
-    knn_frame f;
+    zk_grid_frame f;
     const double span = fmax(s[1][0] - s[0][0], s[3][0] - s[2][0]);
     f.x0 = s[0][0];
     f.y0 = s[2][0];
@@ -234,32 +191,6 @@ __global__ __launch_bounds__(1024) void knn_frame_kernel(const double2* __restri
     f.g = g;
     *out = f;
   }
-}
-
-__global__ __launch_bounds__(256) void bin_key_kernel(const double2* __restrict__ pts, long long n, const knn_frame* __restrict__ fi,
-                                                      unsigned* __restrict__ keys, int* __restrict__ idx) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const knn_frame f = *fi;
-  keys[i] = (unsigned)(bin_of((pts[i].y - f.y0) / f.h, f.g) * f.g + bin_of((pts[i].x - f.x0) / f.h, f.g));
-  idx[i] = (int)i;
-}
-
-// bin_start[b] = first sorted point of bin b, b in [0, bins]; spts = the points in sorted order
-__global__ __launch_bounds__(256) void bin_start_kernel(const unsigned* __restrict__ skeys, const int* __restrict__ sidx,
-                                                        const double2* __restrict__ pts, long long n, long long bins,
-                                                        int* __restrict__ bin_start, double2* __restrict__ spts) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i <= bins) {
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-      const long long mid = (lo + hi) >> 1;
-      if ((long long)skeys[mid] < i) lo = mid + 1;
-      else hi = mid;
-    }
-    bin_start[i] = (int)lo;
-  }
-  if (i < n) spts[i] = pts[sidx[i]];
 }
 
 // the running list: best[0] <= ... <= best[11]; d takes its place and the largest falls out (no run-time index: registers)
@@ -280,17 +211,17 @@ __device__ inline void scan_range(const double2* __restrict__ spts, int lo, int 
 }
 
 __global__ __launch_bounds__(64) void knn_kernel(const double2* __restrict__ spts, const int* __restrict__ sidx,
-                                                 const int* __restrict__ bin_start, long long n, const knn_frame* __restrict__ fi, int k,
+                                                 const int* __restrict__ bin_start, long long n, const zk_grid_frame* __restrict__ fi, int k,
                                                  const int* __restrict__ flag, double* __restrict__ out) {
   const long long t = (long long)blockIdx.x * 64 + threadIdx.x;
   if (t >= n || (*flag & ERR_NONFINITE)) return;     // set before this launch; with a NaN no search would ever stop
-  const knn_frame f = *fi;
+  const zk_grid_frame f = *fi;
   const int g = f.g;
   const double px = spts[t].x, py = spts[t].y;
   double best[KNN];
 #pragma unroll
   for (int j = 0; j < KNN; ++j) best[j] = INFINITY;
-  const int bx = bin_of((px - f.x0) / f.h, g), by = bin_of((py - f.y0) / f.h, g);
+  const int bx = f.bin_x(px), by = f.bin_y(py);
   int reach = bx > g - 1 - bx ? bx : g - 1 - bx;
   reach = by > reach ? by : reach;
   reach = g - 1 - by > reach ? g - 1 - by : reach;
@@ -333,32 +264,17 @@ int check_knn(const void* pts, int dtype, int64_t n, int k, const void* out) {
 
 int knn_call(const void* points, int dtype, int64_t n, int k, double* out, hipStream_t s) {
   int rc;
-  int g = (int)ceil(sqrt((double)n / 2));
-  g = g < 1 ? 1 : (g > MAX_GRID ? MAX_GRID : g);
-  const long long bins = (long long)g * g;
-  int key_bits = 1;
-  while (((long long)1 << key_bits) < bins) ++key_bits;
-  dev_buf d_pts, d_flag, d_frame, d_keys, d_idx, d_bin, d_spts, d_tmp;
-  if ((rc = d_pts.alloc(sizeof(double2) * (size_t)n)) || (rc = d_flag.alloc(16)) || (rc = d_frame.alloc(sizeof(knn_frame))) ||
-      (rc = d_keys.alloc(sizeof(unsigned) * 2 * (size_t)n)) || (rc = d_idx.alloc(sizeof(int) * 2 * (size_t)n)) ||
-      (rc = d_bin.alloc(sizeof(int) * (size_t)(bins + 1))) || (rc = d_spts.alloc(sizeof(double2) * (size_t)n)))
-    return rc;
+  const int g = grid_side(n);
+  temp_store tmp;
+  point_grid grid;
+  dev_buf d_pts, d_flag, d_frame;
+  if ((rc = d_pts.alloc(sizeof(double2) * (size_t)n)) || (rc = d_flag.alloc(16)) || (rc = d_frame.alloc(sizeof(zk_grid_frame)))) return rc;
   ZK_HIP(hipMemsetAsync(d_flag.p, 0, 16, s));
   hipLaunchKernelGGL(load_points_kernel, dim3(blocks_of(n)), dim3(256), 0, s, points, dtype, (long long)n, d_pts.as<double2>(), d_flag.as<int>());
-  hipLaunchKernelGGL(knn_frame_kernel, dim3(1), dim3(1024), 0, s, d_pts.as<double2>(), (long long)n, g, d_frame.as<knn_frame>());
-  unsigned *k_in = d_keys.as<unsigned>(), *k_out = k_in + n;
-  int *i_in = d_idx.as<int>(), *i_out = i_in + n;
-  hipLaunchKernelGGL(bin_key_kernel, dim3(blocks_of(n)), dim3(256), 0, s, d_pts.as<double2>(), (long long)n, d_frame.as<knn_frame>(), k_in, i_in);
-  ZK_HIP(hipGetLastError());
-  size_t bytes = 0;
-  ZK_HIP(rocprim::radix_sort_pairs(nullptr, bytes, k_in, k_out, i_in, i_out, (size_t)n, 0, key_bits, s));
-  if ((rc = d_tmp.alloc(bytes))) return rc;
-  ZK_HIP(rocprim::radix_sort_pairs(d_tmp.p, bytes, k_in, k_out, i_in, i_out, (size_t)n, 0, key_bits, s));
-  const long long span = bins + 1 > n ? bins + 1 : n;
-  hipLaunchKernelGGL(bin_start_kernel, dim3(blocks_of(span)), dim3(256), 0, s, k_out, i_out, d_pts.as<double2>(), (long long)n, bins,
-                     d_bin.as<int>(), d_spts.as<double2>());
-  hipLaunchKernelGGL(knn_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, d_spts.as<double2>(), i_out, d_bin.as<int>(), (long long)n,
-                     d_frame.as<knn_frame>(), k, d_flag.as<int>(), out);
+  hipLaunchKernelGGL(knn_frame_kernel, dim3(1), dim3(1024), 0, s, d_pts.as<double2>(), (long long)n, g, d_frame.as<zk_grid_frame>());
+  if ((rc = build_point_grid(&grid, tmp, d_pts.as<double2>(), n, g, d_frame.as<zk_grid_frame>(), s))) return rc;
+  hipLaunchKernelGGL(knn_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, grid.spts, grid.sidx, grid.bin_start, (long long)n,
+                     d_frame.as<zk_grid_frame>(), k, d_flag.as<int>(), out);
   ZK_HIP(hipGetLastError());
   int flags = 0;
   ZK_HIP(hipMemcpyAsync(&flags, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -558,21 +474,19 @@ int stats_call(const double* dd, int64_t n, int op, const double* params, int64_
     return 0;
   }
   // ZK_KNN_GAPS: one sort per sample
-  dev_buf d_keys, d_tmp;
+  dev_buf d_keys;
+  temp_store tmp;
   const size_t most = (size_t)n * NK;
   if ((rc = d_keys.alloc(sizeof(u64) * 2 * most)) || (rc = d_out.alloc(sizeof(u64) * NK))) return rc;
   ZK_HIP(hipMemsetAsync(d_out.p, 0xff, sizeof(u64) * NK, s));
-  size_t bytes = 0;
   u64 *k_in = d_keys.as<u64>(), *k_out = k_in + most;
-  ZK_HIP(rocprim::radix_sort_keys(nullptr, bytes, k_in, k_out, most, 0, 64, s));
-  if ((rc = d_tmp.alloc(bytes))) return rc;
+  const auto sort = [&](size_t m) { return [=](void* p, size_t& b) { return rocprim::radix_sort_keys(p, b, k_in, k_out, m, 0, 64, s); }; };
+  size_t bytes = 0;                                  // one allocation, sized by the largest sample, serves the eleven sorts
+  if ((rc = zk_prim_bytes(&bytes, sort(most))) || (rc = tmp.ensure(bytes))) return rc;
   for (int c = 0; c < NK; ++c) {
     const long long m = (long long)n * (c + 1);
-    size_t need = 0;
-    ZK_HIP(rocprim::radix_sort_keys(nullptr, need, k_in, k_out, (size_t)m, 0, 64, s));
-    if (need > bytes) return zk_fail(ZK_E_BADARG, "knn_stats: the sort of a smaller sample asks for more temporary storage than the largest");
     hipLaunchKernelGGL(gap_keys_kernel, dim3(blocks_of(m)), dim3(256), 0, s, dd, (long long)n, c + 1, params[0], k_in);
-    ZK_HIP(rocprim::radix_sort_keys(d_tmp.p, need, k_in, k_out, (size_t)m, 0, 64, s));
+    if ((rc = zk_prim(tmp, sort((size_t)m)))) return rc;
     hipLaunchKernelGGL(gap_min_kernel, dim3(blocks_of(m)), dim3(256), 0, s, k_out, m, d_out.as<u64>() + c);
     ZK_HIP(hipGetLastError());
   }

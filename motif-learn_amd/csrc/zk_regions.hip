@@ -36,10 +36,10 @@
 #include <new>
 
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 
 #include "zk_internal.h"
+#include "zk_scratch.h"
 
 namespace {
 
@@ -48,29 +48,12 @@ typedef unsigned long long u64;
 constexpr u64 PAD_KEY = ~0ull;                       // unused wedge slots and rejected edges: sorts last, matches nothing
 constexpr double TWO_PI = 2 * 3.141592653589793;     // the reference's 2 * np.pi
 
-struct dev_buf {
-  void* p = nullptr;
-  ~dev_buf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    ZK_HIP(hipMalloc(&p, bytes ? bytes : 16));
-    return 0;
-  }
-  template <typename T>
-  T* as() const {
-    return (T*)p;
-  }
-};
-
 // what the count phase leaves for the fill phase
 struct regions_state {
   int device = 0;
   int64_t F = 0, V = 0, A = 0;
   dev_buf offsets, vertices, ks, centers, adjacency;   // int64 (F + 1), int64 (V), int64 (F), float64 (F, 2), int64 (A, 2)
 };
-
-inline unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256); }
 
 // doubling rounds that cover any path or cycle of up to w wedges: the smallest r with 2^r >= w
 inline int rounds_for(long long w) {
@@ -337,26 +320,6 @@ __global__ __launch_bounds__(256) void centers_kernel(const double2* __restrict_
 // the launch sequence
 // ---------------------------------------------------------------------------------------------------------------------
 
-// rocPRIM's temporary storage, grown to the largest request of the call
-struct temp_store {
-  void* p = nullptr;
-  size_t have = 0;
-  ~temp_store() {
-    if (p) (void)hipFree(p);
-  }
-  int ensure(size_t need) { return zk_ensure(&p, &have, need ? need : 16); }
-};
-
-template <typename T>
-int exclusive_sum(temp_store& tmp, const T* in, T* out, size_t n, hipStream_t s) {
-  size_t bytes = 0;
-  ZK_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, (T)0, n, rocprim::plus<T>(), s));
-  int rc = tmp.ensure(bytes);
-  if (rc) return rc;
-  ZK_HIP(rocprim::exclusive_scan(tmp.p, bytes, in, out, (T)0, n, rocprim::plus<T>(), s));
-  return 0;
-}
-
 int regions_count(regions_state* st, const double* pts, int64_t n, const long long* ijs, int64_t e, hipStream_t s) {
   if (n == 0) return 0;
   int rc;
@@ -375,14 +338,11 @@ int regions_count(regions_state* st, const double* pts, int64_t n, const long lo
   u64 *k_in = d_keys.as<u64>(), *k_out = k_in + e2;
   hipLaunchKernelGGL(edge_key_kernel, dim3(blocks_of(e2)), dim3(256), 0, s, ijs, (long long)e, (long long)n, d_i0, k_in, d_i0 + 1);
   ZK_HIP(hipGetLastError());
-  size_t bytes = 0;
-  ZK_HIP(rocprim::radix_sort_keys(nullptr, bytes, k_in, k_out, (size_t)e2, 0, 64, s));
-  if ((rc = tmp.ensure(bytes))) return rc;
-  ZK_HIP(rocprim::radix_sort_keys(tmp.p, bytes, k_in, k_out, (size_t)e2, 0, 64, s));
-  bytes = 0;
-  ZK_HIP(rocprim::unique(nullptr, bytes, k_out, d_ukeys.as<u64>(), (unsigned int*)(d_i0 + 2), (size_t)e2, rocprim::equal_to<u64>(), s));
-  if ((rc = tmp.ensure(bytes))) return rc;
-  ZK_HIP(rocprim::unique(tmp.p, bytes, k_out, d_ukeys.as<u64>(), (unsigned int*)(d_i0 + 2), (size_t)e2, rocprim::equal_to<u64>(), s));
+  if ((rc = zk_prim(tmp, [&](void* p, size_t& b) { return rocprim::radix_sort_keys(p, b, k_in, k_out, (size_t)e2, 0, 64, s); })) ||
+      (rc = zk_prim(tmp, [&](void* p, size_t& b) {
+         return rocprim::unique(p, b, k_out, d_ukeys.as<u64>(), (unsigned int*)(d_i0 + 2), (size_t)e2, rocprim::equal_to<u64>(), s);
+       })))
+    return rc;
   int small[3] = {0, 0, 0};
   ZK_HIP(hipMemcpyAsync(small, d_small.p, sizeof(small), hipMemcpyDeviceToHost, s));
   ZK_HIP(hipStreamSynchronize(s));
@@ -405,10 +365,8 @@ int regions_count(regions_state* st, const double* pts, int64_t n, const long lo
   int *wl_in = d_wlast.as<int>(), *wl = wl_in + w_n;
   hipLaunchKernelGGL(wedge_kernel, dim3(blocks_of(w_n)), dim3(256), 0, s, uk, m, nodes, d_row.as<int>(), d_sorted.as<int>(), wk_in, wl_in);
   ZK_HIP(hipGetLastError());
-  bytes = 0;
-  ZK_HIP(rocprim::radix_sort_pairs(nullptr, bytes, wk_in, wk, wl_in, wl, (size_t)w_n, 0, 64, s));
-  if ((rc = tmp.ensure(bytes))) return rc;
-  ZK_HIP(rocprim::radix_sort_pairs(tmp.p, bytes, wk_in, wk, wl_in, wl, (size_t)w_n, 0, 64, s));
+  if ((rc = zk_prim(tmp, [&](void* p, size_t& b) { return rocprim::radix_sort_pairs(p, b, wk_in, wk, wl_in, wl, (size_t)w_n, 0, 64, s); })))
+    return rc;
 
   // successor, cycle labels, ranks
   dev_buf d_succ, d_ptr, d_mn, d_nxt, d_dist;

@@ -27,26 +27,12 @@
 #include <type_traits>
 
 #include "zk_internal.h"
+#include "zk_scratch.h"
 
 namespace {
 
 constexpr int MAX_RANKS = 16;
 constexpr int SWEEP_BLOCKS = 1024;  // 4 workgroups per CU; a workgroup's share of a 2048^2 frame is 4096 elements
-
-struct dev_buf {
-  void* p = nullptr;
-  ~dev_buf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    ZK_HIP(hipMalloc(&p, bytes ? bytes : 16));
-    return 0;
-  }
-  template <typename T>
-  T* as() const {
-    return (T*)p;
-  }
-};
 
 size_t element_size(int dtype) { return dtype == ZK_F64 ? 8 : dtype == ZK_F32 ? 4 : dtype == ZK_U8 ? 1 : 2; }
 

@@ -8,8 +8,7 @@
 //                sequential sum / max per lane and a fixed tree over the 1024 lanes (no floating-point atomics).  The four
 //                corner points are centre + (-+v, -+v), v = v0 (1 + pad), with the indices N .. N + 3, as add_corner_points
 //                appends them.
-//   bins         a G x G grid over the square centre -+ v0, G = ceil(sqrt(N / 2)) (about two points a bin on a uniform set);
-//                points are radix-sorted by bin (rocPRIM), bin starts are lower bounds in the sorted keys.
+//   bins         the point grid of zk_point_grid.h over the square centre -+ v0.
 //   cells        one lane per point, in bin order.  The cell is a convex polygon in coordinates RELATIVE to the point, each
 //                vertex with the index of the neighbour whose bisector made the edge that leaves it.  It starts as a square
 //                that contains the cell (below), is clipped by the four corners, then by the points of the bins in rings of
@@ -53,10 +52,11 @@
 #include <new>
 
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 
 #include "zk_internal.h"
+#include "zk_point_grid.h"
+#include "zk_scratch.h"
 
 namespace {
 
@@ -64,25 +64,9 @@ typedef unsigned long long u64;
 
 constexpr int CAP = 32;                              // vertices of one cell
 constexpr int CELL_LANES = 64;                       // one wave per workgroup of the cell kernel
-constexpr int MAX_GRID = 4096;                       // bins per axis at most (bin keys fit 24 bits)
 constexpr double SLACK = 1e-9;                       // relative margin of the search's stopping test, far past any rounding in it
 
-enum { ERR_NONFINITE = 1, ERR_COINCIDENT = 2, ERR_CAP = 4, ERR_OPEN = 8, ERR_ROUNDING = 16 };
-
-struct dev_buf {
-  void* p = nullptr;
-  ~dev_buf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    ZK_HIP(hipMalloc(&p, bytes ? bytes : 16));
-    return 0;
-  }
-  template <typename T>
-  T* as() const {
-    return (T*)p;
-  }
-};
+enum { ERR_COINCIDENT = 2, ERR_CAP = 4, ERR_OPEN = 8, ERR_ROUNDING = 16 };
 
 // what the count phase leaves for the fill phase
 struct voronoi_state {
@@ -95,12 +79,9 @@ struct voronoi_state {
 struct frame_info {
   double cx, cy;                                     // centre
   double v0, v;                                      // max |p - centre|, v0 (1 + pad)
-  double x0, y0, h;                                  // grid origin and bin side
+  zk_grid_frame grid;                                // the bins, over centre -+ v0
   double half;                                       // half-side of the starting square
-  int g;                                             // bins per axis
 };
-
-inline unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256); }
 
 // one cell's polygon: vertex t at x[t * stride], y[t * stride], id[t * stride]
 struct poly_ref {
@@ -110,17 +91,12 @@ struct poly_ref {
   int stride;
 };
 
-__host__ __device__ inline int bin_of(double u, int g) {
-  const double f = floor(u);
-  return f >= (double)(g - 1) ? g - 1 : (f > 0 ? (int)f : 0);      // NaN goes to 0
-}
-
 // Clips the polygon of n vertices with x . q <= |q|^2 / 2 in place (Sutherland-Hodgman; the write index never passes
 // the vertex read next, which is held in registers).  Returns the new vertex count, -1 when it would pass CAP, -2 when
 // nothing is left, -3 when the vertices outside the half-plane are not one run around the polygon: it is then convex only up
 // to rounding (three nearly collinear vertices, as nearly coincident points make them), and neither the count nor the
 // in-place order would hold.  Every store is guarded by the cap as well.
-__host__ __device__ inline int clip_cell(poly_ref p, int n, double qx, double qy, int qid) {
+__device__ inline int clip_cell(poly_ref p, int n, double qx, double qy, int qid) {
   const double hq = 0.5 * (qx * qx + qy * qy);
   const int s = p.stride;
   int outside = 0, runs = 0;
@@ -178,7 +154,7 @@ struct search_box {
 // circle around v through the cell's own point (|q - v| < |v|), so the search is over when, for every vertex, the part of
 // that circle inside the grid's rectangle lies in the box.  The part is bounded by its extent in y over the rectangle's x
 // range and its extent in x over the rectangle's y range; radii are taken SLACK larger.
-__host__ __device__ inline bool can_be_cut(poly_ref p, int nv, const search_box& b) {
+__device__ inline bool can_be_cut(poly_ref p, int nv, const search_box& b) {
   for (int t = 0; t < nv; ++t) {
     const double vx = p.x[t * p.stride], vy = p.y[t * p.stride], r2 = (vx * vx + vy * vy) * (1 + SLACK);
     const double dx = fmax(fmax(b.gxlo - vx, vx - b.gxhi), 0.0), dy = fmax(fmax(b.gylo - vy, vy - b.gyhi), 0.0);
@@ -201,7 +177,7 @@ struct cell_input {
 };
 
 // position of neighbour `id` relative to (px, py): a point, or corner id - n in the order (-,-) (+,-) (+,+) (-,+)
-__host__ __device__ inline void relative_of(const cell_input& in, const frame_info& f, int id, double px, double py, double* qx,
+__device__ inline void relative_of(const cell_input& in, const frame_info& f, int id, double px, double py, double* qx,
                                             double* qy) {
   if (id < in.n) {
     *qx = in.pts[id].x - px;
@@ -214,7 +190,7 @@ __host__ __device__ inline void relative_of(const cell_input& in, const frame_in
 }
 
 // clips with the points of the sorted range [lo, hi); returns the vertex count or a negative code
-__host__ __device__ inline int clip_range(const cell_input& in, poly_ref p, int nv, int lo, int hi, int self, double px, double py,
+__device__ inline int clip_range(const cell_input& in, poly_ref p, int nv, int lo, int hi, int self, double px, double py,
                                           int* err) {
   for (int m = lo; m < hi && nv > 0; ++m) {
     const int j = in.sidx[m];
@@ -230,8 +206,9 @@ __host__ __device__ inline int clip_range(const cell_input& in, poly_ref p, int 
 }
 
 // The cell of sorted point k in p; returns its vertex count, or 0 with bits set in *err.
-__host__ __device__ inline int build_cell(const cell_input& in, const frame_info& f, long long k, poly_ref p, int* err) {
-  const int s = p.stride, self = in.sidx[k], g = f.g;
+__device__ inline int build_cell(const cell_input& in, const frame_info& f, long long k, poly_ref p, int* err) {
+  const zk_grid_frame& gf = f.grid;
+  const int s = p.stride, self = in.sidx[k], g = gf.g;
   const double px = in.spts[k].x, py = in.spts[k].y;
   // the starting square, counter-clockwise, no neighbour behind its edges
   const double mx = f.cx - px, my = f.cy - py;
@@ -246,16 +223,16 @@ __host__ __device__ inline int build_cell(const cell_input& in, const frame_info
     relative_of(in, f, (int)in.n + c, px, py, &qx, &qy);
     nv = clip_cell(p, nv, qx, qy, (int)in.n + c);
   }
-  const int bx = bin_of((px - f.x0) / f.h, g), by = bin_of((py - f.y0) / f.h, g);
+  const int bx = gf.bin_x(px), by = gf.bin_y(py);
   int reach = bx > g - 1 - bx ? bx : g - 1 - bx;
   reach = by > reach ? by : reach;
   reach = g - 1 - by > reach ? g - 1 - by : reach;
   for (int r = 0; r <= reach && nv > 0; ++r) {
     if (r > 0) {                                     // the points not yet seen lie outside the box of the rings before r
-      const double e = SLACK * f.h * g;
-      const search_box b = {f.x0 - px - e, f.x0 + f.h * g - px + e, f.y0 - py - e, f.y0 + f.h * g - py + e,
-                            f.x0 + f.h * (bx - r + 1) - px + e, f.x0 + f.h * (bx + r) - px - e,
-                            f.y0 + f.h * (by - r + 1) - py + e, f.y0 + f.h * (by + r) - py - e};
+      const double e = SLACK * gf.h * g;
+      const search_box b = {gf.x0 - px - e, gf.x0 + gf.h * g - px + e, gf.y0 - py - e, gf.y0 + gf.h * g - py + e,
+                            gf.x0 + gf.h * (bx - r + 1) - px + e, gf.x0 + gf.h * (bx + r) - px - e,
+                            gf.y0 + gf.h * (by - r + 1) - py + e, gf.y0 + gf.h * (by + r) - py - e};
       if (!can_be_cut(p, nv, b)) break;
     }
     const int xlo = bx - r > 0 ? bx - r : 0, xhi = bx + r < g - 1 ? bx + r : g - 1;
@@ -298,7 +275,7 @@ __host__ __device__ inline int build_cell(const cell_input& in, const frame_info
 // The rows of a finished cell: for vertex t the neighbour id[t], its ridge length and its edge length.  Returns the number of
 // rows kept by `mode` and writes them through put(row, j, L, L1).
 template <class Put>
-__host__ __device__ inline int cell_rows(const cell_input& in, const frame_info& f, long long k, poly_ref p, int nv, int mode, double dmax,
+__device__ inline int cell_rows(const cell_input& in, const frame_info& f, long long k, poly_ref p, int nv, int mode, double dmax,
                                          double threshold, Put put) {
   const int s = p.stride;
   const double px = in.spts[k].x, py = in.spts[k].y;
@@ -328,22 +305,6 @@ __host__ __device__ inline int cell_rows(const cell_input& in, const frame_info&
 // ---------------------------------------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------------------------------------
-
-__global__ __launch_bounds__(256) void load_points_kernel(const void* __restrict__ in, int dtype, long long n, double2* __restrict__ pts,
-                                                          int* __restrict__ flag) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  double x, y;
-  if (dtype == ZK_I32) {
-    x = (double)((const int*)in)[2 * i];
-    y = (double)((const int*)in)[2 * i + 1];
-  } else {
-    x = ((const double*)in)[2 * i];
-    y = ((const double*)in)[2 * i + 1];
-  }
-  if (!(fabs(x) <= 1.7976931348623157e308) || !(fabs(y) <= 1.7976931348623157e308)) atomicOr(flag, ERR_NONFINITE);
-  pts[i] = make_double2(x, y);
-}
 
 // one workgroup: centre, v0, corners' v, grid and starting square
 __global__ __launch_bounds__(1024) void frame_kernel(const double2* __restrict__ pts, long long n, double pad, int g,
@@ -383,41 +344,15 @@ __global__ __launch_bounds__(1024) void frame_kernel(const double2* __restrict__
     f.cy = cy;
     f.v0 = sa[0];
     f.v = f.v0 * s;
-    f.x0 = cx - f.v0;
-    f.y0 = cy - f.v0;
-    f.h = f.v0 > 0 ? 2 * f.v0 / (double)g : 1.0;
+    f.grid.x0 = cx - f.v0;
+    f.grid.y0 = cy - f.v0;
+    f.grid.h = f.v0 > 0 ? 2 * f.v0 / (double)g : 1.0;
+    f.grid.g = g;
     f.half = f.v * ((2 * s * s - 1) / (2 * pad * s)) * (17.0 / 16.0);
-    f.g = g;
     *out = f;
     // finite points whose sum or whose starting square overflows (coordinates near 1e308) are refused like non-finite ones
     if (!(fabs(cx) + fabs(cy) + f.half <= 1.7976931348623157e308)) atomicOr(flag, ERR_NONFINITE);
   }
-}
-
-__global__ __launch_bounds__(256) void bin_key_kernel(const double2* __restrict__ pts, long long n, const frame_info* __restrict__ fi,
-                                                      unsigned* __restrict__ keys, int* __restrict__ idx) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const frame_info f = *fi;
-  keys[i] = (unsigned)(bin_of((pts[i].y - f.y0) / f.h, f.g) * f.g + bin_of((pts[i].x - f.x0) / f.h, f.g));
-  idx[i] = (int)i;
-}
-
-// bin_start[b] = first sorted point of bin b, b in [0, bins]; spts = the points in sorted order
-__global__ __launch_bounds__(256) void bin_start_kernel(const unsigned* __restrict__ skeys, const int* __restrict__ sidx,
-                                                        const double2* __restrict__ pts, long long n, long long bins,
-                                                        int* __restrict__ bin_start, double2* __restrict__ spts) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i <= bins) {
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-      const long long mid = (lo + hi) >> 1;
-      if ((long long)skeys[mid] < i) lo = mid + 1;
-      else hi = mid;
-    }
-    bin_start[i] = (int)lo;
-  }
-  if (i < n) spts[i] = pts[sidx[i]];
 }
 
 // One lane per sorted point.  Its rows go to stage_*[row * n + k] (coalesced over the lanes), their number to cnt[k];
@@ -489,21 +424,6 @@ __global__ __launch_bounds__(256) void unpack_kernel(const u64* __restrict__ key
 // the launch sequence
 // ---------------------------------------------------------------------------------------------------------------------
 
-// rocPRIM's temporary storage, grown to the largest request of the call
-struct temp_store {
-  void* p = nullptr;
-  size_t have = 0;
-  ~temp_store() {
-    if (p) (void)hipFree(p);
-  }
-  int ensure(size_t need) { return zk_ensure(&p, &have, need ? need : 16); }
-};
-
-int grid_side(int64_t n) {
-  int g = (int)ceil(sqrt((double)n / 2));
-  return g < 1 ? 1 : (g > MAX_GRID ? MAX_GRID : g);
-}
-
 int fail_flags(int flags) {
   if (flags & ERR_NONFINITE)
     return zk_fail(ZK_E_BADARG, "voronoi_cells: a point is not finite (or the coordinates are so large that their sum or the corner points overflow)");
@@ -522,15 +442,11 @@ int voronoi_count(voronoi_state* st, const void* points, int dtype, int64_t n, d
   int rc;
   temp_store tmp;
   const int g = grid_side(n);
-  const long long bins = (long long)g * g;
-  int key_bits = 1;
-  while (((long long)1 << key_bits) < bins) ++key_bits;
   const bool lengths = mode == ZK_VORONOI_NEIGHBOURS;
 
-  dev_buf d_pts, d_small, d_frame, d_keys, d_idx, d_bin, d_spts, d_cnt, d_off, d_sj, d_sl, d_sl1;
+  point_grid grid;
+  dev_buf d_pts, d_small, d_frame, d_cnt, d_off, d_sj, d_sl, d_sl1;
   if ((rc = d_pts.alloc(sizeof(double2) * (size_t)n)) || (rc = d_small.alloc(64)) || (rc = d_frame.alloc(sizeof(frame_info))) ||
-      (rc = d_keys.alloc(sizeof(unsigned) * 2 * (size_t)n)) || (rc = d_idx.alloc(sizeof(int) * 2 * (size_t)n)) ||
-      (rc = d_bin.alloc(sizeof(int) * (size_t)(bins + 1))) || (rc = d_spts.alloc(sizeof(double2) * (size_t)n)) ||
       (rc = d_cnt.alloc(sizeof(int) * (size_t)(n + 1))) || (rc = d_off.alloc(sizeof(int) * (size_t)(n + 1))) ||
       (rc = d_sj.alloc(sizeof(int) * CAP * (size_t)n)) || (lengths && ((rc = d_sl.alloc(sizeof(double) * CAP * (size_t)n)) ||
                                                                       (rc = d_sl1.alloc(sizeof(double) * CAP * (size_t)n)))))
@@ -545,26 +461,13 @@ int voronoi_count(voronoi_state* st, const void* points, int dtype, int64_t n, d
     return flags ? fail_flags(flags) : 0;
   }
   hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(1024), 0, s, d_pts.as<double2>(), (long long)n, pad, g, d_frame.as<frame_info>(), d_flag);
-  unsigned *k_in = d_keys.as<unsigned>(), *k_out = k_in + n;
-  int *i_in = d_idx.as<int>(), *i_out = i_in + n;
-  hipLaunchKernelGGL(bin_key_kernel, dim3(blocks_of(n)), dim3(256), 0, s, d_pts.as<double2>(), (long long)n, d_frame.as<frame_info>(), k_in, i_in);
-  ZK_HIP(hipGetLastError());
-  size_t bytes = 0;
-  ZK_HIP(rocprim::radix_sort_pairs(nullptr, bytes, k_in, k_out, i_in, i_out, (size_t)n, 0, key_bits, s));
-  if ((rc = tmp.ensure(bytes))) return rc;
-  ZK_HIP(rocprim::radix_sort_pairs(tmp.p, bytes, k_in, k_out, i_in, i_out, (size_t)n, 0, key_bits, s));
-  const long long span = bins + 1 > n ? bins + 1 : n;
-  hipLaunchKernelGGL(bin_start_kernel, dim3(blocks_of(span)), dim3(256), 0, s, k_out, i_out, d_pts.as<double2>(), (long long)n, bins,
-                     d_bin.as<int>(), d_spts.as<double2>());
-  const cell_input in = {d_pts.as<double2>(), d_spts.as<double2>(), i_out, d_bin.as<int>(), (long long)n};
+  if ((rc = build_point_grid(&grid, tmp, d_pts.as<double2>(), n, g, &d_frame.as<frame_info>()->grid, s))) return rc;
+  const cell_input in = {d_pts.as<double2>(), grid.spts, grid.sidx, grid.bin_start, (long long)n};
   hipLaunchKernelGGL(cell_kernel, dim3((unsigned)((n + 1 + CELL_LANES - 1) / CELL_LANES)), dim3(CELL_LANES), 0, s, in,
                      d_frame.as<frame_info>(), mode, dmax, threshold, d_cnt.as<int>(), d_sj.as<int>(), d_sl.as<double>(), d_sl1.as<double>(),
                      d_flag);
   ZK_HIP(hipGetLastError());
-  bytes = 0;
-  ZK_HIP(rocprim::exclusive_scan(nullptr, bytes, d_cnt.as<int>(), d_off.as<int>(), 0, (size_t)(n + 1), rocprim::plus<int>(), s));
-  if ((rc = tmp.ensure(bytes))) return rc;
-  ZK_HIP(rocprim::exclusive_scan(tmp.p, bytes, d_cnt.as<int>(), d_off.as<int>(), 0, (size_t)(n + 1), rocprim::plus<int>(), s));
+  if ((rc = exclusive_sum<int>(tmp, d_cnt.as<int>(), d_off.as<int>(), (size_t)(n + 1), s))) return rc;
 
   // the error flags and the number of rows cross to the host: the rows size the sort
   int flags = 0, total = 0;
@@ -579,25 +482,20 @@ int voronoi_count(voronoi_state* st, const void* points, int dtype, int64_t n, d
   if ((rc = d_rk.alloc(sizeof(u64) * 2 * (size_t)keys_n)) || (lengths && (rc = d_rp.alloc(sizeof(int) * 2 * (size_t)keys_n)))) return rc;
   u64 *r_in = d_rk.as<u64>(), *r_out = r_in + keys_n;
   int *p_in = d_rp.as<int>(), *p_out = lengths ? p_in + keys_n : nullptr;   // row positions: neighbour mode only
-  hipLaunchKernelGGL(compact_kernel, dim3(blocks_of(n)), dim3(256), 0, s, d_cnt.as<int>(), d_off.as<int>(), i_out, d_sj.as<int>(),
+  hipLaunchKernelGGL(compact_kernel, dim3(blocks_of(n)), dim3(256), 0, s, d_cnt.as<int>(), d_off.as<int>(), grid.sidx, d_sj.as<int>(),
                      (long long)n, (long long)total, mode, r_in, p_in);
   ZK_HIP(hipGetLastError());
   long long m = keys_n;
   const u64* sorted = r_out;
   if (lengths) {
-    bytes = 0;
-    ZK_HIP(rocprim::radix_sort_pairs(nullptr, bytes, r_in, r_out, p_in, p_out, (size_t)keys_n, 0, 64, s));
-    if ((rc = tmp.ensure(bytes))) return rc;
-    ZK_HIP(rocprim::radix_sort_pairs(tmp.p, bytes, r_in, r_out, p_in, p_out, (size_t)keys_n, 0, 64, s));
+    if ((rc = zk_prim(tmp, [&](void* p, size_t& b) { return rocprim::radix_sort_pairs(p, b, r_in, r_out, p_in, p_out, (size_t)keys_n, 0, 64, s); })))
+      return rc;
   } else {
-    bytes = 0;
-    ZK_HIP(rocprim::radix_sort_keys(nullptr, bytes, r_in, r_out, (size_t)keys_n, 0, 64, s));
-    if ((rc = tmp.ensure(bytes))) return rc;
-    ZK_HIP(rocprim::radix_sort_keys(tmp.p, bytes, r_in, r_out, (size_t)keys_n, 0, 64, s));
-    bytes = 0;
-    ZK_HIP(rocprim::unique(nullptr, bytes, r_out, r_in, (unsigned int*)(d_flag + 1), (size_t)keys_n, rocprim::equal_to<u64>(), s));
-    if ((rc = tmp.ensure(bytes))) return rc;
-    ZK_HIP(rocprim::unique(tmp.p, bytes, r_out, r_in, (unsigned int*)(d_flag + 1), (size_t)keys_n, rocprim::equal_to<u64>(), s));
+    if ((rc = zk_prim(tmp, [&](void* p, size_t& b) { return rocprim::radix_sort_keys(p, b, r_in, r_out, (size_t)keys_n, 0, 64, s); })) ||
+        (rc = zk_prim(tmp, [&](void* p, size_t& b) {
+           return rocprim::unique(p, b, r_out, r_in, (unsigned int*)(d_flag + 1), (size_t)keys_n, rocprim::equal_to<u64>(), s);
+         })))
+      return rc;
     int unique_n = 0;
     ZK_HIP(hipMemcpyAsync(&unique_n, d_flag + 1, sizeof(int), hipMemcpyDeviceToHost, s));
     ZK_HIP(hipStreamSynchronize(s));
@@ -667,7 +565,6 @@ int voronoi_call(int device, const void* points, int dtype, int64_t n, double pa
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------
-#ifndef ZK_VORONOI_NO_ABI
 extern "C" int zk_voronoi_cells_dev(int device, const void* points_dev, int points_dtype, int64_t n_points, double pad, int mode, double dmax,
                                     double threshold, void** state, int64_t* counts_host, int64_t* ijs_dev, double* ridge_dev,
                                     double* edge_dev, void* hip_stream) {
@@ -696,4 +593,3 @@ extern "C" int zk_voronoi_cells(int device, const void* points_host, int points_
   return voronoi_call(device, d_pts.p, points_dtype, n_points, pad, mode, dmax, threshold, state, counts_host, ijs_host, ridge_host, edge_host,
                       hipMemcpyDeviceToHost, (hipStream_t)0);
 }
-#endif

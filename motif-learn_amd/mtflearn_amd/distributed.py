@@ -329,7 +329,8 @@ def _empty_image(shape, dtype, like):
         return _native.DeviceArray(shape, dtype, like.device.index)
     import torch
     tdtype = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.uint8): torch.uint8,
-              np.dtype(np.int16): torch.int16, np.dtype(np.uint16): getattr(torch, "uint16", None)}[np.dtype(dtype)]
+              np.dtype(np.int16): torch.int16, np.dtype(np.uint16): getattr(torch, "uint16", None),
+              np.dtype(np.int64): torch.int64}[np.dtype(dtype)]
     return torch.empty(shape, dtype=tdtype, device=like.device)
 
 
@@ -494,35 +495,28 @@ def find_regions_device(points, edges):
         raise ValueError("find_regions_device needs len(points) + len(edges) + 4 < 2^31")
     if n == 0 and e:
         raise ValueError("edges without points")
-
-    def empty(shape, dtype):
-        if _is_native(points):
-            return _native.DeviceArray(shape, dtype, points.device.index)
-        import torch
-        return torch.empty(shape, dtype=torch.int64 if dtype == np.int64 else torch.float64, device=points.device)
-
     lib = _native.load()
     device, stream = points.device.index, c_void_p(_current_stream_ptr(points))
     state, counts = c_void_p(), (c_int64 * 3)()
     _native.check(lib.zk_find_regions_dev(device, c_void_p(points.data_ptr()), n, c_void_p(edges.data_ptr()), e, byref(state), counts,
                                           None, None, None, None, None, stream), "zk_find_regions_dev")
     f, v, a = (int(c) for c in counts)
-    offsets, vertices, ks = empty((f + 1,), np.int64), empty((v,), np.int64), empty((f,), np.int64)
-    centers, adjacency = empty((f, 2), np.float64), empty((a, 2), np.int64)
+    offsets, vertices, ks = (_empty_image(shape, np.int64, points) for shape in ((f + 1,), (v,), (f,)))
+    centers, adjacency = _empty_like((f, 2), points), _empty_image((a, 2), np.int64, points)
     _native.check(lib.zk_find_regions_dev(device, None, 0, None, 0, byref(state), counts, c_void_p(offsets.data_ptr()),
                                           c_void_p(vertices.data_ptr()), c_void_p(ks.data_ptr()), c_void_p(centers.data_ptr()),
                                           c_void_p(adjacency.data_ptr()), stream), "zk_find_regions_dev")
     return offsets, vertices, ks, centers, adjacency
 
 
-def _voronoi_device(points, pad, mode, dmax, threshold, stream, what):
-    """Both phases of ``zk_voronoi_cells_dev`` on resident points; returns ``(ijs, ridge, edge)`` of the points' kind."""
+def _resident_points(points, what, spare=0):
+    """``(points, ZK_* code)`` of resident ``(N, 2)`` points for ``zk_voronoi_cells_dev`` and ``zk_knn_distances_dev``: float64 or
+    int32 as they are, any other real torch type converted to float64 on the device.  ``what`` needs
+    ``len(points) < 2^26 - spare``."""
     if len(points.shape) != 2 or points.shape[1] != 2:
         raise ValueError(f"points must have shape (N, 2), not {tuple(points.shape)}")
     if not points.is_cuda:
         raise ValueError("points must live on the GPU")
-    if not (np.isfinite(pad) and pad > 0):
-        raise ValueError(f"pad must be positive and finite, not {pad}")
     if _is_native(points):
         if points.dtype not in (np.float64, np.int32):
             raise TypeError(f"points must be a float64 or int32 DeviceArray, not {points.dtype}")
@@ -535,19 +529,20 @@ def _voronoi_device(points, pad, mode, dmax, threshold, stream, what):
             points = points.to(torch.float64)
         points = points.contiguous()
         code = _native.ZK_F64 if points.dtype == torch.float64 else _native.ZK_I32
+    if int(points.shape[0]) + spare >= 2 ** 26:
+        raise ValueError(f"{what} needs len(points) < 2^26" + (f" - {spare}" if spare else ""))
+    return points, code
+
+
+def _voronoi_device(points, pad, mode, dmax, threshold, stream, what):
+    """Both phases of ``zk_voronoi_cells_dev`` on resident points; returns ``(ijs, ridge, edge)`` of the points' kind."""
+    points, code = _resident_points(points, what, spare=4)
+    if not (np.isfinite(pad) and pad > 0):
+        raise ValueError(f"pad must be positive and finite, not {pad}")
     n = int(points.shape[0])
-    if n + 4 >= 2 ** 26:
-        raise ValueError(f"{what} needs len(points) < 2^26 - 4")
-
-    def empty(shape, dtype):
-        if _is_native(points):
-            return _native.DeviceArray(shape, dtype, points.device.index)
-        import torch
-        return torch.empty(shape, dtype=torch.int64 if dtype == np.int64 else torch.float64, device=points.device)
-
     lengths = mode == _native.VORONOI_NEIGHBOURS
     if n == 0:
-        return empty((0, 2), np.int64), empty((0,), np.float64), empty((0,), np.float64)
+        return _empty_image((0, 2), np.int64, points), _empty_like((0,), points), _empty_like((0,), points)
     lib = _native.load()
     device = points.device.index
     if stream is None:
@@ -557,8 +552,8 @@ def _voronoi_device(points, pad, mode, dmax, threshold, stream, what):
     _native.check(lib.zk_voronoi_cells_dev(device, c_void_p(points.data_ptr()), code, n, pad, mode, dmax, threshold, byref(state), counts,
                                            None, None, None, stream), "zk_voronoi_cells_dev")
     m = int(counts[0])
-    ijs = empty((m, 2), np.int64)
-    ridge, edge = (empty((m,), np.float64), empty((m,), np.float64)) if lengths else (None, None)
+    ijs = _empty_image((m, 2), np.int64, points)
+    ridge, edge = (_empty_like((m,), points), _empty_like((m,), points)) if lengths else (None, None)
     _native.check(lib.zk_voronoi_cells_dev(device, None, code, 0, pad, mode, dmax, threshold, byref(state), counts, c_void_p(ijs.data_ptr()),
                                            c_void_p(ridge.data_ptr()) if lengths else None, c_void_p(edge.data_ptr()) if lengths else None,
                                            stream), "zk_voronoi_cells_dev")
@@ -578,29 +573,6 @@ def voronoi_neighbours_device(points, pad=0.05, stream=None):
     return _voronoi_device(points, float(pad), _native.VORONOI_NEIGHBOURS, 0.0, 0.0, stream, "voronoi_neighbours_device")
 
 
-def _knn_points(points, what):
-    """``(points, ZK_* code)`` of resident ``(N, 2)`` points for ``zk_knn_distances_dev``: float64 or int32 as they are, any
-    other real torch type converted to float64 on the device."""
-    if len(points.shape) != 2 or points.shape[1] != 2:
-        raise ValueError(f"points must have shape (N, 2), not {tuple(points.shape)}")
-    if not points.is_cuda:
-        raise ValueError("points must live on the GPU")
-    if _is_native(points):
-        if points.dtype not in (np.float64, np.int32):
-            raise TypeError(f"points must be a float64 or int32 DeviceArray, not {points.dtype}")
-        return points, _native.ZK_F64 if points.dtype == np.float64 else _native.ZK_I32
-    import torch
-    if points.dtype.is_complex or points.dtype == torch.bool:
-        raise ValueError(f"points must be real numbers, not {points.dtype}")
-    if points.dtype not in (torch.float64, torch.int32):
-        points = points.to(torch.float64)
-    points = points.contiguous()
-    n = int(points.shape[0])
-    if n >= 2 ** 26:
-        raise ValueError(f"{what} needs len(points) < 2^26")
-    return points, _native.ZK_F64 if points.dtype == torch.float64 else _native.ZK_I32
-
-
 def estimate_d_device(points, threshold='otsu', return_k=False):
     """:func:`mtflearn_amd.graph.estimate_d` of points resident on the GPU: ``points`` ``(N, 2)``, a torch tensor of any real
     type or a float64 / int32 :class:`~mtflearn_amd._native.DeviceArray` -- what :func:`local_max_device` or
@@ -608,7 +580,7 @@ def estimate_d_device(points, threshold='otsu', return_k=False):
     pass (ranges, histograms, side sums) cross to the host, where the scalar rules run.  ``N < 12`` raises ``ValueError``;
     a non-finite coordinate raises ``RuntimeError`` from the device.  Runs on torch's current stream."""
     from . import graph
-    points, code = _knn_points(points, "estimate_d_device")
+    points, code = _resident_points(points, "estimate_d_device")
     n = int(points.shape[0])
     if n < graph.KNN:
         raise ValueError(f"Expected n_neighbors <= n_samples_fit, but n_neighbors = {graph.KNN}, n_samples_fit = {n}")

@@ -79,6 +79,25 @@ def test_knn_distances_of_int32_key_points_and_the_refusals(golden):
     assert close(graph.knn_distances(rc.point_sets()["n13"]), golden["n13/dd"])                      # the library is unharmed
 
 
+def test_knn_distances_on_a_frame_of_zero_span():
+    """A bounding box without extent takes the frame's ``span == 0`` branch (bin side 1); one without extent in x only bins by y
+    alone (rc.point_sets() has a set without extent in y, none without extent in x)."""
+    got = graph.knn_distances(np.full((12, 2), 3.5))
+    assert got.shape == (12, 12) and got.tobytes() == np.zeros((12, 12)).tobytes()
+    y = np.cumsum(1 + np.arange(13) % 5 / 8)                                                        # dyadic: every |yi - yj| is exact
+    want = np.sort(np.abs(y[:, None] - y[None, :]), axis=1)[:, :12]
+    got = graph.knn_distances(np.stack([np.full(13, 7.25), y], axis=1))
+    assert got.shape == (13, 12) and got.tobytes() == want.tobytes()
+
+
+@pytest.mark.parametrize("kind", ("native", "torch"))
+def test_estimate_d_device_of_int32_points_equals_that_of_the_same_values_in_float64(kind):
+    """One loader for both types: int32 pairs are widened exactly, so nothing after the load can differ."""
+    pts = np.unique(np.random.default_rng(3).integers(0, 200, (400, 2)), axis=0).astype(np.int32)
+    want = distributed.estimate_d_device(resident(pts.astype(np.float64), kind), return_k=True)
+    assert distributed.estimate_d_device(resident(pts, kind), return_k=True) == want and want[0] > 0
+
+
 @pytest.mark.parametrize("name", rc.POINT_SET_NAMES)
 def test_histograms_and_otsu(golden, otsu_parts, name):
     parts = otsu_parts[name]

@@ -126,6 +126,15 @@ def test_resident_nan_and_duplicate_fail_and_the_next_call_succeeds(golden):
     assert np.array_equal(to_host(distributed.vnn_graph_device(resident(pts, "torch"), dmax, threshold=threshold)), golden["n65/ijs"])
 
 
+@pytest.mark.parametrize("kind", ("native", "torch"))
+def test_int32_points_give_the_rows_of_the_same_values_in_float64(kind):
+    """One loader for both types: int32 pairs are widened exactly, so pairs, ridge and edge lengths agree byte for byte."""
+    pts = np.rint(12 * vc.honeycomb(7, 7, 0.04, 22)).astype(np.int32)       # 98 key points as local_max gives them: whole pixels
+    want = [to_host(a) for a in distributed.voronoi_neighbours_device(resident(pts.astype(np.float64), kind))]
+    got = [to_host(a) for a in distributed.voronoi_neighbours_device(resident(pts, kind))]
+    assert len(want[0]) > len(pts) and all(g.dtype == w.dtype and g.tobytes() == w.tobytes() for g, w in zip(got, want))
+
+
 def test_csr_matrix_of_the_graph(golden):
     pts, dmax, threshold = vc.cases()["grid_3x3_jittered"]
     matrix = graph.vnn_graph(pts, threshold=threshold, dmax=dmax, return_ijs=False)
