@@ -642,6 +642,41 @@ int zk_refine_points_dev(int device, const void* image_dev, int image_dtype, int
                          int64_t n_points, int64_t size, int mode, double* out_dev, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Thresholded centroid refinement of key points: the reference's com_refine (features/_keypoint.py:26-43).  No plan involved.
+ * image: (H, W) of ZK_F32 or ZK_F64.  corners: n int32 pairs (x0, y0); window i is image[y0 : y0 + size, x0 : x0 + size],
+ * 2 <= size <= 64, widened to float64.  threshold: ZK_THRESHOLD_LI or ZK_THRESHOLD_OTSU, both defined on that float64 window:
+ *   Otsu  np.histogram(window, 256) (np.linspace's edges, NumPy's bin rule) and the centre of the bin that maximises the
+ *         between-class variance, the cumulative sums taken sequentially in bin order as np.cumsum does; the first maximum.
+ *   Li    v = window - min; from mean(v), t <- (mean_back - mean_fore) / (log(mean_back) - log(mean_fore)) over v > t and the
+ *         rest, until two iterates differ by no more than half the smallest gap between distinct values, or mean_back == 0; a NaN
+ *         from an empty side ends the loop and stays.  thresholds = t + min.  A window still running after 1000 steps is an error.
+ *   A window of one value has that value as its threshold and no iteration.
+ * Values below the threshold count as zero (none when it is NaN); centroids (n, 2) float64 holds
+ * (sum(w * col) / sum(w), sum(w * row) / sum(w)) with window-local indices and every product rounded once; 0 / 0 = NaN is kept.
+ * thresholds (n float64) and iterations (n int32: Li's steps, 0 for Otsu) may be NULL.  Sums go through a fixed tree that depends on
+ * size alone: no floating-point atomics, two runs agree bit for bit.  Parity with scikit-image is not pinned (it bins a float32
+ * window in float32).
+ *
+ * zk_com_refine_points_dev takes key points instead, ZK_I32 or ZK_F64 pairs (x, y): the corner is rint(point) - size / 2 and
+ * out = (centroid - size / 2.0) + point, both on the device.
+ *
+ * Errors (ZK_E_BADARG, nothing returned): a dtype other than the two float types, n >= 2^24, size outside [2, 64], an unknown
+ * threshold, a window that leaves the frame (the host variant checks before anything is launched, the _dev variants on the
+ * device, where such a window reads and writes nothing).  No per-window global memory.  zk_com_refine takes and fills host
+ * arrays; the _dev variants take and fill device arrays on hip_stream, which is synchronised before they return (the error flag
+ * crosses to the host).
+ * ------------------------------------------------------------------------------------------------------ */
+#define ZK_THRESHOLD_LI   0
+#define ZK_THRESHOLD_OTSU 1
+int zk_com_refine(int device, const void* image_host, int image_dtype, int64_t H, int64_t W, const int32_t* corners_host, int64_t n,
+                  int64_t size, int threshold, double* centroids_out, double* thresholds_out, int32_t* iterations_out);
+int zk_com_refine_dev(int device, const void* image_dev, int image_dtype, int64_t H, int64_t W, const int32_t* corners_dev, int64_t n,
+                      int64_t size, int threshold, double* centroids_dev, double* thresholds_dev, int32_t* iterations_dev,
+                      void* hip_stream);
+int zk_com_refine_points_dev(int device, const void* image_dev, int image_dtype, int64_t H, int64_t W, const void* points_dev,
+                             int points_dtype, int64_t n, int64_t size, int threshold, double* out_dev, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * The device passes of the reference's estimate_d (graph/vnn.py:18-40): the bond length vnn_graph cuts at when no dmax is given.
  * No plan involved.
  *

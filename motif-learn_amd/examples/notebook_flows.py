@@ -84,6 +84,9 @@ def main():
           f" {int((ks.numpy() == 6).sum())} hexagons of {len(ks)} polygons")
     moved = atoms.numpy() - keep
     print(f"         centroids moved the key points by at most {np.abs(moved).max():.2f} px")
+    from mtflearn_amd.distributed import com_refine_device
+    cut = com_refine_device(clean, d_keep, 9)                              # reference: com_refine(pts, img, 9); Li per window, 'otsu' on request
+    print(f"         thresholded centroids (9 x 9 windows, Li) differ from the plain ones by at most {np.nanmax(np.abs(cut.numpy() - atoms.numpy())):.2f} px")
 
 
 if __name__ == "__main__":

@@ -21,6 +21,7 @@ ZK_E_BADARG = -10001                # zernike_hip.h: a refused argument
 ZK_I32 = 5                         # int32 key points (local_max): zk_voronoi_cells and zk_knn_distances only
 VORONOI_NEIGHBOURS, VORONOI_GRAPH = 0, 1                           # zk_voronoi_cells modes
 REFINE_BOX, REFINE_DISK = 0, 1                                     # zk_refine_points modes
+THRESHOLD_LI, THRESHOLD_OTSU = 0, 1                                # zk_com_refine thresholds
 KNN_RANGES, KNN_HIST, KNN_SIDES, KNN_GAPS = 0, 1, 2, 3             # zk_knn_stats ops
 PATH_AUTO, PATH_GENERIC, PATH_FOLDED, PATH_SEPARABLE, PATH_STREAM, PATH_DIRECT = 0, 1, 2, 3, 4, 5
 OP_POINTS, OP_MAPS = 1, 2
@@ -144,6 +145,11 @@ SYMBOLS = {
                                      POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p]),
     "zk_refine_points": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "zk_refine_points_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "zk_com_refine": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "zk_com_refine_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
+    "zk_com_refine_points_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p,
+                                         c_void_p]),
     "zk_knn_distances": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_void_p]),
     "zk_knn_distances_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p]),
     "zk_knn_stats": (c_int, [c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),

@@ -34,7 +34,7 @@ __all__ = ["shard_bounds", "one_gpu_rank_env", "RcclComm", "TorchComm", "DeviceC
            "frame_moments_device", "frame_maps_device", "normalize_image_device", "standardize_image_device",
            "percentile_clip_device", "local_max_device", "points_moments_device", "remove_background_device", "denoise_svd_device",
            "denoise_svd_memory_view_device", "find_regions_device", "voronoi_neighbours_device", "vnn_graph_device", "refine_points_device",
-           "estimate_d_device", "sharded_patch_moments", "sharded_frame_moments",
+           "com_refine_device", "estimate_d_device", "sharded_patch_moments", "sharded_frame_moments",
            "sharded_frame_maps", "sharded_frames_moments"]
 
 
@@ -631,6 +631,51 @@ def refine_points_device(image, points, size=3, mode=None):
         if rc == _native.ZK_E_BADARG:
             raise ValueError(_native.last_error())
         _native.check(rc, "zk_refine_points_dev")
+    return out
+
+
+def com_refine_device(image, points, size, threshold=None):
+    """:func:`mtflearn_amd.features.com_refine_points` of a frame and key points resident on the GPU: ``image`` ``(H, W)``
+    float32 / float64, ``points`` ``(N, 2)`` int32 or float64 ``(x, y)`` (what :func:`local_max_device` or
+    :func:`refine_points_device` return), both torch tensors or both :class:`~mtflearn_amd._native.DeviceArray`.  Returns the
+    ``(N, 2)`` float64 refined points on the device, of the same kind -- what :func:`vnn_graph_device`,
+    :func:`estimate_d_device` and :func:`find_regions_device` accept.  Rounding the points to window corners and the two final
+    additions are done on the device with the host function's own rounded operations: a point gives the same bits on either
+    route.  As there, the thresholds (``threshold='otsu'``: Otsu, anything else: Li) are defined on the window widened to
+    float64 and parity with scikit-image is unpinned.  There is NO border clearing here: every ``size x size`` window must lie
+    inside the frame, or ``ValueError`` is raised (the windows are checked on the device: nothing is written for such a
+    point, and only the flag crosses to the host) -- the contract of :func:`refine_points_device`.  A frame that is not float,
+    ``size`` outside ``[2, 64]`` or ``N >= 2^24`` raise ``ValueError`` too.  Runs on torch's current stream."""
+    if len(image.shape) != 2:
+        raise ValueError(f"com_refine_device needs a 2D image, not {len(image.shape)}-D")
+    if not image.is_cuda or not points.is_cuda:
+        raise ValueError("image and points must live on the GPU")
+    if _is_native(image) != _is_native(points) or image.device.index != points.device.index:
+        raise ValueError("image and points must be of one kind and on one device")
+    try:
+        code = _dtype_code(image)
+    except TypeError as e:
+        raise ValueError(f"com_refine_device needs a float frame: {e}") from None
+    kind = str(points.dtype).replace("torch.", "")
+    if len(points.shape) != 2 or points.shape[1] != 2 or kind not in ("int32", "float64"):
+        raise TypeError("points must be an (N, 2) int32 or float64 array of (x, y)")
+    if not _is_native(image):
+        image, points = image.contiguous(), points.contiguous()
+    if int(size) != size or not 2 <= int(size) <= 64:
+        raise ValueError(f"size must be an integer in [2, 64], not {size}")
+    n = int(points.shape[0])
+    if n >= 2 ** 24:
+        raise ValueError("com_refine_device needs len(points) < 2^24")
+    h, w = (int(v) for v in image.shape)
+    out = _empty_like((n, 2), image)
+    if n:
+        rc = _native.load().zk_com_refine_points_dev(image.device.index, c_void_p(image.data_ptr()), code, h, w, c_void_p(points.data_ptr()),
+                                                     _native.ZK_I32 if kind == "int32" else _native.ZK_F64, n, int(size),
+                                                     _native.THRESHOLD_OTSU if threshold == 'otsu' else _native.THRESHOLD_LI,
+                                                     c_void_p(out.data_ptr()), c_void_p(_current_stream_ptr(image)))
+        if rc == _native.ZK_E_BADARG:
+            raise ValueError(_native.last_error())
+        _native.check(rc, "zk_com_refine_points_dev")
     return out
 
 

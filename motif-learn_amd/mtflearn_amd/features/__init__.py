@@ -7,10 +7,10 @@ from .moments import (zmoments, construct_rot_maps_matrix, construct_complex_mat
 from .pickers import (estimate_patch_size, radial_profile, autocorrelation, estimate_n_max, estimate_n_max_from_patch,
                       _get_cumulative_energy)
 from .consumers import pca
-from .keypoints import KeyPoints, refine_points
+from .keypoints import KeyPoints, com_refine_points, refine_points
 from .peaks import local_max
 
 __all__ = ["ZPs", "zmoments", "construct_rot_maps_matrix", "construct_complex_matrix",
            "construct_real_matrix", "nm2j", "nm2j_complex", "check_array1d",
            "estimate_patch_size", "radial_profile", "autocorrelation", "estimate_n_max", "estimate_n_max_from_patch", "pca",
-           "KeyPoints", "refine_points", "local_max"]
+           "KeyPoints", "refine_points", "com_refine_points", "local_max"]

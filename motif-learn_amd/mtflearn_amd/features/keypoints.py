@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["disk_patch", "center_of_mass_refine", "refine_points", "com_refine", "clear_border", "KeyPoints"]
+__all__ = ["disk_patch", "center_of_mass_refine", "refine_points", "com_refine", "com_refine_points", "clear_border", "KeyPoints"]
 
 
 def _interior(pts, x_limit, y_limit, size):
@@ -98,6 +98,58 @@ def com_refine(pts, img, size, threshold=None):
         w[w < level_of(w)] = 0
         moved[k] = np.subtract(ndimage.center_of_mass(w), size / 2)[::-1]
     return moved + kp.pts
+
+
+def com_refine_points(pts, img, size, threshold=None, return_thresholds=False):
+    """``com_refine(pts, img, size, threshold)`` on the GPU (``zk_com_refine``): NumPy in, NumPy out, the reference's argument
+    order and rule.  The points are border-cleared by ``clear_border(pts, img.shape, size)``; the window of a kept point starts
+    at ``np.rint(pt).astype(int) - size // 2`` and is ``size x size``; it is thresholded (``threshold='otsu'``: Otsu, anything
+    else: Li, as in the reference), what lies below the threshold counts as zero, and the float64 ``(M, 2)`` result is
+    ``(centroid_xy - size / 2) + pts_kept``.  With ``return_thresholds`` the call returns ``(points, thresholds (M) float64,
+    iterations (M) int32)``: the threshold of every window and the steps Li's iteration took (0 for Otsu).
+
+    The thresholds are defined on the window WIDENED TO FLOAT64: Otsu is the 256-bin histogram of ``np.histogram`` and the bin
+    centre of the largest between-class variance, Li the iteration of ``threshold_li`` from the window's mean with half the
+    smallest gap between distinct values as its tolerance.  Parity with scikit-image is unpinned, as for ``graph.estimate_d``
+    (scikit-image is not installed where this package is tested); in particular scikit-image bins a float32 window in float32.
+    A window of zeros gives ``nan, nan`` (0 / 0), as SciPy does.
+
+    ``img`` must be a 2-D float32 or float64 frame and ``2 <= size <= 64``; anything else raises ``ValueError`` naming it
+    (scikit-image takes another histogram route for integer frames: the host :func:`com_refine` remains for those).  Empty
+    ``pts`` returns a ``(0, 2)`` array without touching the device."""
+    from ctypes import c_void_p
+    from .. import _native
+    img, pts = np.asarray(img), np.asarray(pts)
+    if img.ndim != 2 or img.dtype not in (np.float32, np.float64):
+        raise ValueError(f"com_refine_points needs a 2-D float32 or float64 frame, not {img.ndim}-D {img.dtype}")
+    if pts.size == 0:
+        pts = pts.reshape(0, 2).astype(np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 2 or pts.dtype.kind not in "iuf":
+        raise ValueError(f"com_refine_points needs real points of shape (N, 2), not {pts.dtype} {pts.shape}")
+    if int(size) != size or not 2 <= int(size) <= 64:
+        raise ValueError(f"size must be an integer in [2, 64], not {size}")
+    size = int(size)
+    if pts.dtype.kind == "f" and not np.isfinite(pts).all():
+        raise ValueError("com_refine_points needs finite points")
+    if len(pts) >= 2 ** 24:
+        raise ValueError("com_refine_points needs len(pts) < 2^24")
+    kept = clear_border(pts, img.shape, size)
+    moved, levels, steps = np.empty((len(kept), 2), np.float64), np.empty(len(kept), np.float64), np.empty(len(kept), np.int32)
+    if len(kept):
+        first = np.rint(kept).astype(int) - size // 2
+        height, width = img.shape
+        if first.min() < 0 or (first[:, 0] + size > width).any() or (first[:, 1] + size > height).any():
+            raise ValueError("com_refine_points needs every window inside the frame")      # border clearing guarantees it
+        img, first = np.ascontiguousarray(img), np.ascontiguousarray(first, dtype=np.int32)
+        lib = _native.load()
+        _native.require_device()
+        _native.check(lib.zk_com_refine(_native.default_device(), img.ctypes.data_as(c_void_p), _native.dtype_code(img.dtype), height, width,
+                                        first.ctypes.data_as(c_void_p), len(first), size,
+                                        _native.THRESHOLD_OTSU if threshold == 'otsu' else _native.THRESHOLD_LI,
+                                        moved.ctypes.data_as(c_void_p), levels.ctypes.data_as(c_void_p), steps.ctypes.data_as(c_void_p)),
+                      "zk_com_refine")
+    out = (moved - size / 2) + kept
+    return (out, levels, steps) if return_thresholds else out
 
 
 class KeyPoints:
