@@ -858,6 +858,32 @@ int zk_force_layout_stage(double* xy, int64_t n_nodes, const int64_t* node1, con
                           const double* force_params, int num_negative_samples, double learning_rate, int64_t* rng_state,
                           double* log_out);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Linear synthesis out = C . T: the device side of ZPs.inverse_transform, patches back from moments (csrc/zk_synth.hip; the
+ * reference has no counterpart).  Independent of zk_plan: any table.
+ *   table  : host, (n_funcs, n_pixels) float64, C order; uploaded once (its rows padded with zeros to a multiple of 4) and
+ *            resident for the object's lifetime.  1 <= n_funcs <= 4096, 1 <= n_pixels <= 2^24.
+ *   coeffs : (n_rows, n_funcs) float64, C order
+ *   out    : (n_rows, n_pixels) of out_dtype (ZK_F32 | ZK_F64): out[p, x] = sum_j coeffs[p, j] table[j, x], accumulated in
+ *            float64 on the matrix cores (v_mfma_f64_16x16x4_f64) and rounded once.  A zero table column gives +0.0.
+ * For the Zernike inverse the table is G^-1 diag(s) B (least squares; G = B B^T / area the Gram matrix of the masked basis B)
+ * or diag(s) B (the textbook sum), computed by the caller in float64 (mtflearn_amd/features/zernike_polys.py).
+ * No atomics, and a row's sum does not depend on its place in the batch: two runs, and two chunkings, agree bit for bit.
+ *
+ * zk_synth_apply cuts the rows into chunks of at most `chunk_bytes` of coefficients + output (default 256 MiB,
+ * zk_synth_set_host_chunk; at least 64 rows) and moves chunk c host -> device -> kernel -> device -> host through three device
+ * slots on three streams of the object's own, consecutive chunks overlapping, straight from / into the caller's arrays
+ * (page-locked arrays, zk_host_alloc, move by DMA without blocking the calling thread); it returns when out_host is complete.
+ * zk_synth_apply_dev enqueues on exactly `hip_stream` (NULL = HIP's default stream) and does not synchronise.
+ * n_rows == 0 succeeds and launches nothing.  The object is bound to one device and is not thread-safe.
+ * ------------------------------------------------------------------------------------------------------ */
+typedef struct zk_synth zk_synth;
+int zk_synth_create(int device, int n_funcs, int64_t n_pixels, const double* table_host, zk_synth** out);
+int zk_synth_destroy(zk_synth* s);
+int zk_synth_set_host_chunk(zk_synth* s, int64_t chunk_bytes);   /* staging size of the host variant */
+int zk_synth_apply(zk_synth* s, const double* coeffs_host, int64_t n_rows, int out_dtype /* ZK_F32 | ZK_F64 */, void* out_host);
+int zk_synth_apply_dev(zk_synth* s, const double* coeffs_dev, int64_t n_rows, int out_dtype, void* out_dev, void* hip_stream);
+
 /* Device memory for callers that have no allocator of their own (a NumPy / C user of the *_dev entry points). */
 int zk_device_malloc(int device, int64_t bytes, void** out_dev);
 int zk_device_free(int device, void* dev);

@@ -5,6 +5,7 @@
   notebook 3 (dense):  ZPs.fit_transform(frame) -> rot_maps / mirror_map / |Z_nm| maps
   resident chain:      lattice rendered on the device -> denoise -> background removal -> local maxima -> moments at them
   refined chain:       the same key points -> sub-pixel centroids -> bond length -> Voronoi bonds -> polygons, all resident
+  motifs:              k-means centres of the key-point moments -> ZPs.inverse_transform -> the motif each class stands for
 
 Only the import line differs from the reference (`from mtflearn import ZPs`).  Needs an MI355X.
 Run:  python motif-learn_amd/examples/notebook_flows.py
@@ -87,6 +88,21 @@ def main():
     from mtflearn_amd.distributed import com_refine_device
     cut = com_refine_device(clean, d_keep, 9)                              # reference: com_refine(pts, img, 9); Li per window, 'otsu' on request
     print(f"         thresholded centroids (9 x 9 windows, Li) differ from the plain ones by at most {np.nanmax(np.abs(cut.numpy() - atoms.numpy())):.2f} px")
+
+    # ---- back from moments: what does each k-means class look like? ------------------------------------------------
+    from mtflearn_amd.clustering import DeviceRows, kmeans_fit
+    from mtflearn_amd.distributed import inverse_transform_device
+    t = time.perf_counter()
+    with DeviceRows.adopt(moments.data_ptr(), *moments.shape, device=moments.device.index) as rows:
+        labels, centres, _ = kmeans_fit(rows, 4, random_state=0)           # (4, 66) centres; the moment matrix stays on the device
+    d_centres = _native.DeviceArray.from_numpy(centres)
+    motifs = inverse_transform_device(zps, d_centres).numpy()              # (4, 32, 32): least-squares inverse, exact in the basis' span
+    threefold = inverse_transform_device(zps, d_centres, m_select=(0, 3, 6)).numpy()   # the same centres, their 3-fold part only
+    print(f"motifs : k-means centres {centres.shape} -> patches {motifs.shape} in {1e3 * (time.perf_counter() - t):.1f} ms;"
+          f" class sizes {np.bincount(labels, minlength=4).tolist()}")
+    share = np.linalg.norm(threefold.reshape(4, -1), axis=1) / np.linalg.norm(motifs.reshape(4, -1), axis=1)
+    print("         share of each motif carried by |m| in (0, 3, 6):", np.round(share, 2).tolist())
+    print("         same patches from the host call:", np.array_equal(motifs, zps.inverse_transform(centres)))
 
 
 if __name__ == "__main__":

@@ -201,6 +201,11 @@ SYMBOLS = {
     "zk_force_layout_stage": (c_int, [POINTER(c_double), c_int64, POINTER(c_int64), POINTER(c_int64), POINTER(c_double), c_int64,
                                       POINTER(c_int64), c_int, c_int64, POINTER(c_double), c_int, c_double, POINTER(c_int64),
                                       POINTER(c_double)]),
+    "zk_synth_create": (c_int, [c_int, c_int, c_int64, POINTER(c_double), POINTER(c_void_p)]),
+    "zk_synth_destroy": (c_int, [c_void_p]),
+    "zk_synth_set_host_chunk": (c_int, [c_void_p, c_int64]),
+    "zk_synth_apply": (c_int, [c_void_p, POINTER(c_double), c_int64, c_int, c_void_p]),
+    "zk_synth_apply_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "zk_device_malloc": (c_int, [c_int, c_int64, POINTER(c_void_p)]),
     "zk_device_free": (c_int, [c_int, c_void_p]),
     "zk_device_copy": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int]),
@@ -575,6 +580,59 @@ class Plan:
     def release_staging(self):
         """Free the staging buffers the host-buffer entry points have grown (re-created on demand)."""
         check(self._lib.zk_plan_release_staging(self._h), "zk_plan_release_staging")
+
+
+class Synthesis:
+    """Owns one ``zk_synth``: a ``(n_funcs, n_pixels)`` float64 table resident on one GPU and the product ``out = C . table``
+    on its matrix cores (csrc/zk_synth.hip) -- the device side of ``ZPs.inverse_transform``, usable with any table."""
+
+    def __init__(self, table, device=0):
+        lib = load()
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.ndim != 2 or table.size == 0:
+            raise ValueError("the synthesis table must be a non-empty (n_funcs, n_pixels) matrix")
+        self.n_funcs, self.n_pixels = int(table.shape[0]), int(table.shape[1])
+        self.device = int(device)
+        require_device()
+        handle = c_void_p()
+        check(lib.zk_synth_create(self.device, self.n_funcs, self.n_pixels, table.ctypes.data_as(POINTER(c_double)), byref(handle)),
+              "zk_synth_create")
+        self._h = handle
+        self._lib = lib
+
+    @classmethod
+    def create(cls, table, device=0):
+        return cls(table, device=device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.zk_synth_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def set_host_chunk(self, chunk_bytes):
+        """Bytes of coefficients + output per chunk of :meth:`apply` (0: the default of 256 MiB)."""
+        check(self._lib.zk_synth_set_host_chunk(self._h, int(chunk_bytes)), "zk_synth_set_host_chunk")
+
+    def apply(self, coeffs, dtype=np.float64):
+        """``(N, n_funcs)`` host coefficients -> ``(N, n_pixels)`` host array of ``dtype`` (float64 / float32)."""
+        code = dtype_code(np.dtype(dtype))
+        if code not in (ZK_F32, ZK_F64):
+            raise ValueError("dtype must be float64 or float32")
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+        if coeffs.ndim != 2 or coeffs.shape[1] != self.n_funcs:
+            raise ValueError(f"coefficients must be (N, {self.n_funcs})")
+        out = pinned.empty((coeffs.shape[0], self.n_pixels), dtype=dtype)
+        check(self._lib.zk_synth_apply(self._h, coeffs.ctypes.data_as(POINTER(c_double)), coeffs.shape[0], code,
+                                       out.ctypes.data_as(c_void_p)), "zk_synth_apply")
+        return out
+
+    def apply_dev(self, coeffs_ptr, n_rows, out_ptr, code=ZK_F64, stream=0):
+        """``zk_synth_apply_dev``: ``(n_rows, n_funcs)`` float64 on the device -> ``(n_rows, n_pixels)`` of ``code`` on the
+        device, enqueued on ``stream`` (no synchronisation)."""
+        check(self._lib.zk_synth_apply_dev(self._h, c_void_p(coeffs_ptr), int(n_rows), int(code), c_void_p(out_ptr), c_void_p(stream)),
+              "zk_synth_apply_dev")
 
 
 def allgather_rows_plan(rank, world, n_planes, height, width, rows_per_rank, row_off, n_rows, algo=COMM_AUTO):

@@ -24,6 +24,7 @@ device pointers.
 from __future__ import annotations
 
 import struct
+import warnings
 from ctypes import byref, c_int64, c_void_p
 
 import numpy as np
@@ -34,7 +35,7 @@ __all__ = ["shard_bounds", "one_gpu_rank_env", "RcclComm", "TorchComm", "DeviceC
            "frame_moments_device", "frame_maps_device", "normalize_image_device", "standardize_image_device",
            "percentile_clip_device", "local_max_device", "points_moments_device", "remove_background_device", "denoise_svd_device",
            "denoise_svd_memory_view_device", "find_regions_device", "voronoi_neighbours_device", "vnn_graph_device", "refine_points_device",
-           "com_refine_device", "estimate_d_device", "sharded_patch_moments", "sharded_frame_moments",
+           "com_refine_device", "estimate_d_device", "inverse_transform_device", "sharded_patch_moments", "sharded_frame_moments",
            "sharded_frame_maps", "sharded_frames_moments"]
 
 
@@ -692,6 +693,41 @@ def vnn_graph_device(points, dmax=None, threshold=0.1, pad=0.05, stream=None, th
     if not threshold > 0:
         raise ValueError(f"threshold must be > 0, not {threshold}")
     return _voronoi_device(points, float(pad), _native.VORONOI_GRAPH, dmax, threshold, stream, "vnn_graph_device")[0]
+
+
+def inverse_transform_device(zps, coeffs_dev, n_rows=None, method="lstsq", m_select=None, dtype=np.float64, out=None):
+    """The resident twin of ``ZPs.inverse_transform``: ``coeffs_dev`` is an ``(N, P)`` float64 torch tensor or ``DeviceArray`` of
+    real moments of ``zps``'s full set (k-means centres, class means, rows of ``points_moments_device``); the first ``n_rows``
+    of them (default: all) come back as an ``(n_rows, size, size)`` array of ``dtype`` (float64 / float32) of the same kind on the
+    same device, enqueued on torch's current stream (a ``DeviceArray``: the default stream) without synchronising.  The synthesis
+    table is ``zps``'s cached one (``method``, ``m_select`` as there); everything is checked before any device call."""
+    if not getattr(coeffs_dev, "is_cuda", False):
+        raise ValueError("coeffs_dev must live on the GPU")
+    if not coeffs_dev.is_contiguous():
+        raise ValueError("coeffs_dev must be contiguous")
+    if len(coeffs_dev.shape) != 2 or coeffs_dev.shape[1] != len(zps.n) or not _is_f64(coeffs_dev):
+        raise ValueError(f"coeffs_dev must be an (N, {len(zps.n)}) float64 matrix of real Zernike moments")
+    n_rows = int(coeffs_dev.shape[0] if n_rows is None else n_rows)
+    if not 0 <= n_rows <= coeffs_dev.shape[0]:
+        raise ValueError(f"n_rows must be between 0 and {coeffs_dev.shape[0]}")
+    np_dtype = zps._inverse_dtype(dtype)
+    entry = zps._synthesis_entry(method, m_select)
+    if entry["cond"] is not None and entry["cond"] > zps._COND_LIMIT:
+        warnings.warn(zps._cond_message(entry["cond"]), UserWarning, stacklevel=2)
+    shape = (n_rows, zps.size, zps.size)
+    if out is not None and (tuple(out.shape) != shape or not out.is_contiguous() or _numpy_dtype(out) != np_dtype
+                            or out.device.index != coeffs_dev.device.index):
+        raise ValueError(f"out must be a contiguous {shape} array of {np_dtype} on the device of coeffs_dev")
+    if coeffs_dev.device.index != zps._pick_device():
+        raise ValueError(f"coeffs_dev is on cuda:{coeffs_dev.device.index} but this ZPs computes on device {zps._pick_device()}: "
+                         "bind it to the array's device (ZPs.to_device / MTFLEARN_AMD_DEVICE)")
+    if out is None:
+        out = _empty_image(shape, np_dtype, coeffs_dev)
+    if n_rows == 0:
+        return out
+    synth = zps._synthesis_device(entry)
+    synth.apply_dev(coeffs_dev.data_ptr(), n_rows, out.data_ptr(), _native.dtype_code(np_dtype), _current_stream_ptr(coeffs_dev))
+    return out
 
 
 def _device_frame(image, what):

@@ -33,7 +33,7 @@ from scipy.special import factorial
 from sklearn.base import BaseEstimator, TransformerMixin
 
 from .. import _native
-from .moments import zmoments
+from .moments import check_array1d, zmoments
 
 __all__ = ["ZPs"]
 
@@ -82,6 +82,7 @@ class ZPs(BaseEstimator, TransformerMixin):
         self._plan = None
         self._device = None
         self._lock = threading.RLock()
+        self._synth = {}     # inverse_transform: (method, selection) -> synthesis table and its device object
 
     # ------------------------------------------------------------------ basis (host)
     def _generate_polynomials(self):
@@ -134,6 +135,10 @@ class ZPs(BaseEstimator, TransformerMixin):
             if self._plan is not None and self._plan.device != int(index):
                 self._plan.close()
                 self._plan = None
+            for entry in getattr(self, "_synth", {}).values():
+                if entry["device"] is not None and entry["device"].device != int(index):
+                    entry["device"].close()
+                    entry["device"] = None
             self._device = int(index)
         return self
 
@@ -148,16 +153,22 @@ class ZPs(BaseEstimator, TransformerMixin):
         with self._lock:
             if self._plan is not None:
                 self._plan.release_staging()
+            for entry in getattr(self, "_synth", {}).values():      # the synthesis tables' device copies and their slots
+                if entry["device"] is not None:
+                    entry["device"].close()
+                    entry["device"] = None
 
     def __getstate__(self):
         state = dict(super().__getstate__())
         state["_plan"] = None  # device handles do not pickle / deepcopy
         state.pop("_lock", None)
+        state.pop("_synth", None)
         return state
 
     def __setstate__(self, state):
         super().__setstate__(state)
         self._lock = threading.RLock()
+        self._synth = {}
 
     @staticmethod
     def _device_operand(images):
@@ -361,6 +372,123 @@ class ZPs(BaseEstimator, TransformerMixin):
             rot, ab, mir = self._device_plan().points_maps(operand, pts, len(cn), folds=folds, m_unselect=m_unselect, p=p,
                                                            theta=theta, want_abs=abs_moments)
         return self._rows_result(rot, ab, mir, cn, cm)
+
+    # ------------------------------------------------------------------ inverse transform
+    def _selection(self, m_select):
+        """0/1 vector over the basis functions: 1 where ``|m|`` is in ``m_select`` (``zmoments.select``'s rule), all ones for
+        ``None``."""
+        if m_select is None:
+            return np.ones(len(self.m), dtype=bool)
+        wanted = np.unique(np.abs(check_array1d(list(m_select) if not np.isscalar(m_select) else m_select)))
+        return np.isin(np.abs(self.m), wanted)
+
+    def _gram(self):
+        """``(B, G)``: the masked basis as ``(P, size^2)`` and its Gram matrix ``G = B B^T / area``, ``area = pi size^2 / 4`` --
+        what ``transform`` followed by the textbook sum multiplies a coefficient vector with.  The identity only in the
+        continuum: on this pixel grid it is far from it (DESIGN, "Back from moments")."""
+        basis = self.polynomials.reshape(len(self.n), -1)
+        return basis, basis @ basis.T / (np.pi * self.size * self.size / 4.0)
+
+    def _synthesis_entry(self, method, m_select):
+        """The cached ``{"table", "cond", "device"}`` of one ``(method, selection)``: ``table`` is the ``(P, size^2)`` float64
+        synthesis table ``G^-1 diag(s) B`` (``"lstsq"``, through a Cholesky factorisation of ``G``) or ``diag(s) B``
+        (``"direct"``), ``cond`` the 2-norm condition number of ``G`` (``None`` for ``"direct"``), ``device`` the
+        :class:`_native.Synthesis` holding the table on the GPU once a call has needed it.  Host work only."""
+        if method not in ("lstsq", "direct"):
+            raise ValueError(f"method must be 'lstsq' or 'direct', not {method!r}.")
+        keep = self._selection(m_select)
+        key = (method, keep.tobytes())
+        with self._lock:
+            entry = self._synth.pop(key, None)
+            if entry is not None:
+                self._synth[key] = entry                     # most recently used last
+            else:
+                basis, gram = self._gram()
+                picked = basis * keep[:, None]
+                if method == "lstsq":
+                    from scipy.linalg import cho_factor, cho_solve
+                    cond = float(np.linalg.cond(gram))
+                    table = cho_solve(cho_factor(gram, lower=True), picked)      # numpy.linalg.LinAlgError when G is not positive definite
+                else:
+                    cond, table = None, picked
+                # (+ 0.0: the basis and the solve leave -0.0 outside the disk; the table holds +0.0 there)
+                entry = {"table": np.ascontiguousarray(table + 0.0, dtype=np.float64), "cond": cond, "device": None}
+                self._synth[key] = entry
+                while len(self._synth) > self._SYNTH_CACHE:  # a sweep over selections does not pile up tables on the device
+                    evicted = self._synth.pop(next(iter(self._synth)))
+                    if evicted["device"] is not None:
+                        evicted["device"].close()
+                        evicted["device"] = None             # (a call that still holds the entry re-creates it)
+            return entry
+
+    def _synthesis_device(self, entry):
+        with self._lock:
+            if entry["device"] is None:
+                entry["device"] = _native.Synthesis(entry["table"], device=self._pick_device())
+            return entry["device"]
+
+    def _inverse_operand(self, X):
+        """``(N, P)`` C-contiguous float64 coefficients of ``X``, a rank-2 ``zmoments`` of this instance's full set (complex ones
+        through ``to_real``) or an ``(N, P)`` array."""
+        if isinstance(X, zmoments):
+            if X.data.ndim == 3:
+                raise ValueError("inverse_transform needs rank-2 moments (N, N_poly), one row per patch; these are the rank-3 "
+                                 "moments of a dense frame.  Use transform_at(image, points) to get rank-2 moments of chosen windows.")
+            if X.is_complex:
+                X = X.to_real()
+            if not (np.array_equal(X.n, self.n) and np.array_equal(X.m, self.m)):
+                raise ValueError(f"the (n, m) of these moments is not the full set of this ZPs(n_max={self.n_max}, size={self.size}) "
+                                 f"({len(self.n)} functions); pass m_select to inverse_transform instead of selecting the moments first.")
+            data = X.data
+        else:
+            data = np.asarray(X)
+            if np.iscomplexobj(data):
+                raise ValueError("inverse_transform takes complex moments as a zmoments only (their (n, m) labels say how to pair them).")
+            if data.ndim != 2 or data.shape[1] != len(self.n):
+                raise ValueError(f"inverse_transform needs an (N, {len(self.n)}) matrix of real Zernike moments.")
+        return np.ascontiguousarray(data, dtype=np.float64)
+
+    @staticmethod
+    def _inverse_dtype(dtype):
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError(f"dtype must be float64 or float32, not {dtype}.")
+        return dtype
+
+    _COND_LIMIT = 1e8
+    _SYNTH_CACHE = 8         # (method, selection) tables kept, least recently used dropped first
+
+    def _cond_message(self, cond):
+        return (f"the Gram matrix of ZPs(n_max={self.n_max}, size={self.size}) has condition number {cond:.1e} > 1e8: the "
+                f"least-squares inverse amplifies rounding and noise in the moments by that much.  Use n_max <= {self.size // 2}.")
+
+    def inverse_transform(self, X, method="lstsq", m_select=None, dtype=np.float64) -> np.ndarray:
+        """Patches ``(N, size, size)`` back from moments (extension; the reference has no inverse).
+
+        ``X`` is a rank-2 ``zmoments`` of this instance's full set (a complex one is converted with ``to_real``) or an
+        ``(N, P)`` array.  With ``B`` the masked basis ``(P, size^2)``, ``G = B B^T / area`` and ``s`` the 0/1 vector of the
+        functions whose ``|m|`` is in ``m_select`` (``zmoments.select``'s rule; ``None``: all):
+
+        * ``method="lstsq"``: ``z G^-1 diag(s) B`` -- the orthogonal projection of the patch onto the span of the basis, exact
+          for patches in the span; with ``m_select`` the part of that fit the selected terms carry.
+        * ``method="direct"``: ``z diag(s) B`` -- the textbook sum.  APPROXIMATE on this grid: the masked basis is far from
+          orthonormal on ``linspace(-1, 1, size)^2``, and the sum misses patches in the span by 22-56 % of their maximum.
+
+        Either is one product with a ``(P, size^2)`` table computed once on the host and cached per ``(method, selection)``
+        (the 8 most recently used; ``release()`` frees their device copies);
+        the product runs on the GPU's matrix cores in float64 and is rounded once to ``dtype`` (float64 or float32).  Pixels
+        outside the disk are +0.0.  Raises ``numpy.linalg.LinAlgError`` when ``G`` is not positive definite, and warns when
+        ``cond(G) > 1e8`` (the ``n_max > size / 2`` regime the constructor warns about)."""
+        data = self._inverse_operand(X)
+        dtype = self._inverse_dtype(dtype)
+        entry = self._synthesis_entry(method, m_select)
+        if entry["cond"] is not None and entry["cond"] > self._COND_LIMIT:
+            warnings.warn(self._cond_message(entry["cond"]), UserWarning, stacklevel=2)
+        if data.shape[0] == 0:
+            return np.empty((0, self.size, self.size), dtype=dtype)
+        with self._lock:
+            out = self._synthesis_device(entry).apply(data, dtype)
+        return out.reshape(data.shape[0], self.size, self.size)
 
     def _valid_mask(self, height, width):
         head = (self.size - 1) // 2
