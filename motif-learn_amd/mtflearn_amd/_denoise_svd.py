@@ -22,7 +22,8 @@ from time import time
 import numpy as np
 from numpy.lib.stride_tricks import sliding_window_view
 
-from . import _native
+from . import _device, _native
+from ._device import from_host, to_host
 
 MOMENTS_MAX_PATCH = 48          # zk_windows_moments: largest patch edge (csrc/zk_denoise.hip)
 
@@ -63,24 +64,6 @@ def extract_patches(data, patch_shape=64, extraction_step=1):
 
 
 # ----------------------------------------------------------------------------------------------- device plumbing
-def _dist():
-    from . import distributed
-    return distributed
-
-
-def _to_device(array, like):
-    """Host float64 array -> device array of ``like``'s kind on its device (torch: on the current stream)."""
-    array = np.ascontiguousarray(array, dtype=np.float64)
-    if _dist()._is_native(like):
-        return _native.DeviceArray.from_numpy(array, like.device.index)
-    import torch
-    return torch.from_numpy(array).to(like.device)
-
-
-def _to_host(array):
-    return array.numpy() if _dist()._is_native(array) else array.cpu().numpy()
-
-
 def _ptr(array):
     return c_void_p(array.data_ptr()) if array is not None else None
 
@@ -89,8 +72,7 @@ class _Windows:
     """The implicit window matrix ``A`` (``N = ni * nj`` rows, ``D = ph * pw`` columns) of a device-resident frame."""
 
     def __init__(self, image, patch, ii, jj):
-        d = _dist()
-        self.image, self.code = image, d._image_code(image)
+        self.image, self.code = image, _device.code(image)
         self.h, self.w = (int(v) for v in image.shape)
         self.ph, self.pw = int(patch[0]), int(patch[1])
         self.ii = np.ascontiguousarray(ii, dtype=np.int32)
@@ -104,39 +86,42 @@ class _Windows:
     def _grid(self):
         return (self.ii.ctypes.data_as(c_void_p), len(self.ii), self.jj.ctypes.data_as(c_void_p), len(self.jj))
 
+    def _empty(self, shape):
+        return _device.empty(shape, np.float64, self.image)
+
     def _stream(self):
-        return c_void_p(_dist()._current_stream_ptr(self.image))
+        return c_void_p(_device.stream_ptr(self.image))
 
     def apply_dev(self, q_dev, n_columns, mean_dev=None):
         """``(A - 1 mean^T) Q`` -> ``(N, n_columns)`` on the device."""
-        out = _dist()._empty_like((self.n, n_columns), self.image)
+        out = self._empty((self.n, n_columns))
         _native.check(self.lib.zk_windows_apply_dev(*self._head(), _ptr(q_dev), n_columns, _ptr(mean_dev), _ptr(out), self._stream()),
                       "zk_windows_apply_dev")
         return out
 
     def apply_t_dev(self, y_dev, n_columns):
         """``A^T Y`` -> ``(D, n_columns)`` on the device."""
-        out = _dist()._empty_like((self.d, n_columns), self.image)
+        out = self._empty((self.d, n_columns))
         _native.check(self.lib.zk_windows_apply_t_dev(*self._head(), _ptr(y_dev), n_columns, _ptr(out), self._stream()),
                       "zk_windows_apply_t_dev")
         return out
 
     def apply(self, q):
-        return _to_host(self.apply_dev(_to_device(q, self.image), q.shape[1]))
+        return to_host(self.apply_dev(from_host(q, self.image), q.shape[1]))
 
     def apply_t(self, y):
-        return _to_host(self.apply_t_dev(_to_device(y, self.image), y.shape[1]))
+        return to_host(self.apply_t_dev(from_host(y, self.image), y.shape[1]))
 
     def moments_dev(self):
         """Mean ``(D,)`` and covariance ``(D, D)`` of the dense windows, on the device (the grid of this object is not used)."""
-        mean = _dist()._empty_like((self.d,), self.image)
-        cov = _dist()._empty_like((self.d, self.d), self.image)
+        mean = self._empty((self.d,))
+        cov = self._empty((self.d, self.d))
         _native.check(self.lib.zk_windows_moments_dev(*self._head()[:7], _ptr(mean), _ptr(cov), self._stream()), "zk_windows_moments_dev")
         return mean, cov
 
     def reconstruct_dev(self, y_dev, n_components, v_dev=None, mean_dev=None):
         """Overlap-add of ``Y V + mean`` (or of the explicit batch ``Y`` when ``v_dev`` is None) -> ``(H, W)`` on the device."""
-        out = _dist()._empty_like((self.h, self.w), self.image)
+        out = self._empty((self.h, self.w))
         _native.check(self.lib.zk_windows_reconstruct_dev(self.image.device.index, self.h, self.w, self.ph, self.pw, *self._grid(), _ptr(y_dev),
                                                           n_components, _ptr(v_dev), _ptr(mean_dev), _ptr(out), self._stream()),
                       "zk_windows_reconstruct_dev")
@@ -217,8 +202,8 @@ def _denoise_svd_device(image, patch, ii, jj, n_components, say=lambda *a: None)
     say("Reconstructing...")
     t0 = time()
     k = len(s)
-    clean = win.reconstruct_dev(_to_device(u * s, image), k, _to_device(vt, image))
-    if not _dist()._is_native(clean):
+    clean = win.reconstruct_dev(from_host(u * s, image), k, from_host(vt, image))
+    if not _device.is_native(clean):
         import torch
         torch.cuda.current_stream(clean.device).synchronize()
     say("done in %.2fs." % (time() - t0))

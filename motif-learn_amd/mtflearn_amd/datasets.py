@@ -33,7 +33,7 @@ lattice-constant tables, and ``generate_two_blobs``.  :mod:`mtflearn_amd.synthet
 and stays as it is.
 
 There is no CPU fallback: without a HIP device the rendering functions raise ``RuntimeError``.  Frames that should stay on the
-GPU come from ``render_gaussians_device`` / ``honeycomb_image_device`` of :mod:`mtflearn_amd.distributed`.
+GPU come from ``render_gaussians_device`` / ``honeycomb_image_device`` of :mod:`mtflearn_amd.resident`.
 """
 from __future__ import annotations
 
@@ -42,7 +42,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from . import _native
+from . import _device, _native
 
 __all__ = [
     "add_tapered_gaussian",
@@ -82,11 +82,10 @@ def _render_host(frame, pts, amps, sigma, r_factor, taper, offsets=None, list_bu
 
 def _render_device(frame, pts, amps, sigma, r_factor, taper, offsets=None, list_budget=0):
     """``zk_render_gaussians_dev`` on a resident float32 / float64 frame (a DeviceArray or a torch tensor), in place."""
-    from .distributed import _current_stream_ptr, _dtype_code
     _native.check(_native.load().zk_render_gaussians_dev(
-        frame.device.index, c_void_p(frame.data_ptr()), _dtype_code(frame),
+        frame.device.index, c_void_p(frame.data_ptr()), _device.code(frame, _device.FLOATS),
         *_render_args(pts, amps, tuple(frame.shape), sigma, r_factor, taper, offsets, list_budget),
-        c_void_p(_current_stream_ptr(frame))), "zk_render_gaussians_dev")
+        c_void_p(_device.stream_ptr(frame))), "zk_render_gaussians_dev")
 
 
 def _points_and_amplitudes(ndim, pts, sigma, amplitude, r_factor):
@@ -321,7 +320,7 @@ class HoneyCombLattice:
         intensity_A, intensity_B : amplitudes of the two sublattices.
         normalize : divide the image by its maximum.
         """
-        from .distributed import honeycomb_image_device
+        from .resident import honeycomb_image_device
         return honeycomb_image_device(self, sigma=sigma, intensity_A=intensity_A, intensity_B=intensity_B,
                                       normalize=normalize).numpy()
 

@@ -20,6 +20,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _denoise_svd as _svd
+from ._device import from_host, to_host
 from ._denoise_svd import DenoiseSVD, extract_patches, low_rank_svd, reconstruct_patches
 from .features.pickers import denoise_fft
 
@@ -62,9 +63,9 @@ def _memory_view_device(image, p, n_components, threshold):
     h, w = (int(v) for v in image.shape)
     dense = _svd._Windows(image, (p, p), np.arange(h - p + 1), np.arange(w - p + 1))
     mean, cov = dense.moments_dev()
-    top, ratio, n_components = _select_components(_svd._to_host(cov), n_components, threshold)
-    proj = dense.apply_dev(_svd._to_device(top, image), n_components, mean)
-    recon = dense.reconstruct_dev(proj, n_components, _svd._to_device(top.T, image), mean)
+    top, ratio, n_components = _select_components(to_host(cov), n_components, threshold)
+    proj = dense.apply_dev(from_host(top, image), n_components, mean)
+    recon = dense.reconstruct_dev(proj, n_components, from_host(top.T, image), mean)
     return recon, ratio, n_components
 
 

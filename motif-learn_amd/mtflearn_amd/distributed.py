@@ -20,23 +20,23 @@ Two communicators share one interface:
 
 torch is used for device memory and streams only; the arithmetic is ``libzernike_hip.so`` called on raw
 device pointers.
+
+The single-GPU ``<name>_device`` entry points live in :mod:`mtflearn_amd.resident` and are re-exported here, where they
+lived first: ``distributed.<name>_device`` remains a valid spelling.
 """
 from __future__ import annotations
 
 import struct
-import warnings
-from ctypes import byref, c_int64, c_void_p
 
 import numpy as np
 
-from . import _native
+from . import _device, _native
+from ._device import FLOATS, stream_ptr as _current_stream_ptr
+from .resident import *                            # noqa: F401,F403  the resident entry points, under their first address
+from .resident import __all__ as _resident_names
 
-__all__ = ["shard_bounds", "one_gpu_rank_env", "RcclComm", "TorchComm", "DeviceCompute", "patch_moments_device",
-           "frame_moments_device", "frame_maps_device", "normalize_image_device", "standardize_image_device",
-           "percentile_clip_device", "local_max_device", "points_moments_device", "remove_background_device", "denoise_svd_device",
-           "denoise_svd_memory_view_device", "find_regions_device", "voronoi_neighbours_device", "vnn_graph_device", "refine_points_device",
-           "com_refine_device", "estimate_d_device", "inverse_transform_device", "sharded_patch_moments", "sharded_frame_moments",
-           "sharded_frame_maps", "sharded_frames_moments"]
+__all__ = ["shard_bounds", "one_gpu_rank_env", "RcclComm", "TorchComm", "DeviceCompute", "sharded_patch_moments",
+           "sharded_frame_moments", "sharded_frame_maps", "sharded_frames_moments", *_resident_names]
 
 
 def shard_bounds(n_units: int, rank: int, world: int):
@@ -116,652 +116,9 @@ def _chunk_bounds(padded: int, n_chunks: int):
     return [(edges[c], edges[c + 1]) for c in range(n_chunks) if edges[c + 1] > edges[c]]
 
 
-def _is_native(array):
-    """A :class:`mtflearn_amd._native.DeviceArray` (device memory of the library's own, no torch involved)?"""
-    return isinstance(array, _native.DeviceArray)
-
-
-def _empty_like(shape, like):
-    """Uninitialised float64 device array of ``shape`` on ``like``'s device, of ``like``'s kind."""
-    if _is_native(like):
-        return _native.DeviceArray(shape, np.float64, like.device.index)
-    import torch
-    return torch.empty(shape, dtype=torch.float64, device=like.device)
-
-
-def _current_stream_ptr(tensor):
-    if _is_native(tensor):
-        return 0                                  # the device's default stream
-    import torch
-    return torch.cuda.current_stream(tensor.device).cuda_stream if tensor.is_cuda else 0
-
-
-def _is_f64(array):
-    if _is_native(array):
-        return array.dtype == np.float64
-    import torch
-    return array.dtype == torch.float64
-
-
 def _dtype_code(tensor):
     """ZK_F32 / ZK_F64 of a torch tensor or DeviceArray; anything else is an error (the kernels would read it as float64)."""
-    if _is_native(tensor):
-        if tensor.dtype == np.float32:
-            return _native.ZK_F32
-        if tensor.dtype == np.float64:
-            return _native.ZK_F64
-        raise TypeError(f"the device entry points take float32 or float64 arrays, not {tensor.dtype}; convert first "
-                        "(ZPs.transform does that for NumPy input)")
-    import torch
-    if tensor.dtype == torch.float32:
-        return _native.ZK_F32
-    if tensor.dtype == torch.float64:
-        return _native.ZK_F64
-    raise TypeError(f"the device entry points take float32 or float64 tensors, not {tensor.dtype}; convert first "
-                    "(ZPs.transform does that for NumPy input)")
-
-
-def _check_operand(plan, tensor, what):
-    if not tensor.is_cuda:
-        raise ValueError(f"{what} must live on the GPU")
-    if not tensor.is_contiguous():
-        raise ValueError(f"{what} must be contiguous")
-    if tensor.device.index != plan.device:
-        raise ValueError(f"{what} is on cuda:{tensor.device.index} but the plan was created on device {plan.device}: "
-                         "create the plan on the tensor's device (MTFLEARN_AMD_DEVICE / ZPs.to_device)")
-
-
-# ---------------------------------------------------------------------------------------------------------
-# single-GPU device entry points on torch tensors
-# ---------------------------------------------------------------------------------------------------------
-def patch_moments_device(plan: "_native.Plan", patches, out=None):
-    """Run the batch kernel on a CUDA/HIP torch tensor ``(N, K, K)`` (float32/float64) on torch's
-    current stream; returns the ``(N, n_poly)`` float64 tensor (no host copies)."""
-    _check_operand(plan, patches, "patches")
-    code = _dtype_code(patches)
-    n = patches.shape[0]
-    if out is None:
-        out = _empty_like((n, plan.n_poly), patches)
-    else:
-        _check_operand(plan, out, "out")
-    plan.transform_patches_dev(patches.data_ptr(), code, n, out.data_ptr(), _current_stream_ptr(patches))
-    return out
-
-
-def frame_moments_device(plan: "_native.Plan", image, row0=0, n_rows=None, out=None, full=None):
-    """Run the dense kernel for output rows ``[row0, row0+n_rows)`` of a CUDA/HIP torch frame ``(H, W)``.
-    Returns ``(n_poly, n_rows, W)`` float64 -- or, with ``full`` (an ``(n_poly, H, W)`` tensor), writes the
-    band in place into it and returns ``full``."""
-    _check_operand(plan, image, "image")
-    code = _dtype_code(image)
-    h, w = image.shape
-    n_rows = h - row0 if n_rows is None else n_rows
-    stream = _current_stream_ptr(image)
-    if full is not None:
-        _check_operand(plan, full, "full")
-        assert tuple(full.shape) == (plan.n_poly, h, w) and _is_f64(full)
-        plan.transform_frame_dev(image.data_ptr(), code, h, w, row0, n_rows, full.data_ptr() + row0 * w * 8, stream,
-                                 plane_stride=h * w)
-        return full
-    if out is None:
-        out = _empty_like((plan.n_poly, n_rows, w), image)
-    else:
-        _check_operand(plan, out, "out")
-    plan.transform_frame_dev(image.data_ptr(), code, h, w, row0, n_rows, out.data_ptr(), stream)
-    return out
-
-
-def frame_maps_device(plan: "_native.Plan", image, n_complex, folds=(2, 3, 4, 6), m_unselect=(0, 1), p=2,
-                      theta=None, want_abs=True, row0=0, n_rows=None, full=None):
-    """Fused frame -> symmetry maps for output rows ``[row0, row0+n_rows)`` of a CUDA/HIP torch frame.
-    Returns ``(rot, abs, mirror)`` float64 tensors of shapes ``(len(folds), n_rows, W)``,
-    ``(n_complex, n_rows, W)``, ``(n_rows, W)`` (``None`` for outputs not requested).  With
-    ``full = (rot_full, abs_full, mirror_full)`` (whole-frame tensors, entries ``None`` where not wanted) the
-    band is written in place into them and ``full`` is returned."""
-    _check_operand(plan, image, "image")
-    code = _dtype_code(image)
-    h, w = image.shape
-    n_rows = h - row0 if n_rows is None else n_rows
-    stream = _current_stream_ptr(image)
-    if full is not None:
-        ptr = lambda t: t.data_ptr() + row0 * w * 8 if t is not None else 0
-        plan.frame_maps_dev(image.data_ptr(), code, h, w, row0, n_rows, folds if full[0] is not None else None,
-                            m_unselect, p, theta if full[2] is not None else None, ptr(full[0]), ptr(full[1]),
-                            ptr(full[2]), stream, plane_stride=h * w)
-        return full
-    mk = lambda planes: _empty_like((planes, n_rows, w), image)
-    rot = mk(len(folds)) if folds is not None and len(folds) else None
-    ab = mk(n_complex) if want_abs else None
-    mir = _empty_like((n_rows, w), image) if theta is not None else None
-    ptr = lambda t: t.data_ptr() if t is not None else 0
-    plan.frame_maps_dev(image.data_ptr(), code, h, w, row0, n_rows, folds, m_unselect, p, theta,
-                        ptr(rot), ptr(ab), ptr(mir), stream)
-    return rot, ab, mir
-
-
-def _image_code(image):
-    """ZK_* code of a 2-D device image for ``zk_local_max_dev`` and ``zk_background_*_dev``: the two float types and the narrow detector formats."""
-    if _is_native(image):
-        code = _native.dtype_code(image.dtype)
-        name = image.dtype
-    else:
-        import torch
-        code = {torch.float32: _native.ZK_F32, torch.float64: _native.ZK_F64, torch.uint8: _native.ZK_U8,
-                torch.int16: _native.ZK_I16, getattr(torch, "uint16", None): _native.ZK_U16}.get(image.dtype)
-        name = image.dtype
-    if code is None:
-        raise TypeError(f"device images must be float32, float64, uint8, uint16 or int16, not {name}")
-    return code
-
-
-def _numpy_dtype(image):
-    if _is_native(image):
-        return image.dtype
-    import torch
-    return {torch.float32: np.float32, torch.float64: np.float64, torch.uint8: np.uint8, torch.int16: np.int16,
-            getattr(torch, "uint16", None): np.uint16}[image.dtype]
-
-
-def _empty_points(n, like):
-    if _is_native(like):
-        return _native.DeviceArray((n, 2), np.int32, like.device.index)
-    import torch
-    return torch.empty((n, 2), dtype=torch.int32, device=like.device)
-
-
-def local_max_device(image, min_distance, threshold=None):
-    """:func:`mtflearn_amd.features.local_max` of a frame resident on the GPU (a torch tensor or a
-    :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` of float32 / float64 / uint8 / uint16 / int16).  Returns the
-    ``(N, 2)`` int32 ``(x, y)`` points as a device array of the same kind, in the layout :func:`points_moments_device`
-    reads: the frame never crosses to the host, only the point count does.  Runs on torch's current stream."""
-    from .features.peaks import _check_distance, _comparison_threshold
-    if len(image.shape) != 2:
-        raise ValueError(f"local_max_device needs a 2D image, not {len(image.shape)}-D")
-    if not image.is_cuda:
-        raise ValueError("image must live on the GPU")
-    if not _is_native(image) and not image.is_contiguous():
-        image = image.contiguous()
-    code = _image_code(image)
-    r = _check_distance(min_distance)
-    has_t, t = (0, 0.0) if threshold is None else (1, _comparison_threshold(_numpy_dtype(image), threshold))
-    h, w = (int(v) for v in image.shape)
-    lib = _native.load()
-    stream = c_void_p(_current_stream_ptr(image))
-    capacity = max(1024, h * w // 8)                   # kept points of a real frame: a few % of its pixels
-    out = _empty_points(capacity, image)
-    n = c_int64()
-    for _ in range(2):                                  # the second pass only when the first guess was short
-        _native.check(lib.zk_local_max_dev(image.device.index, c_void_p(image.data_ptr()), code, h, w, r, has_t, t,
-                                           c_void_p(out.data_ptr()), capacity, byref(n), stream), "zk_local_max_dev")
-        if n.value <= capacity:
-            break
-        capacity = n.value
-        out = _empty_points(capacity, image)
-    n = n.value
-    return out[:n]
-
-
-def points_moments_device(plan: "_native.Plan", image, points, out=None):
-    """Moments of the windows centred on device-resident key points (``zk_transform_points_dev``): ``image`` an
-    ``(H, W)`` float32 / float64 frame, ``points`` ``(N, 2)`` int32 ``(x, y)`` (what :func:`local_max_device` returns),
-    both torch tensors or both :class:`~mtflearn_amd._native.DeviceArray`.  Returns the ``(N, n_poly)`` float64 moments
-    on the device -- ``ZPs.transform_at(frame, points)`` with neither the frame nor the points crossing PCIe."""
-    _check_operand(plan, image, "image")
-    _check_operand(plan, points, "points")
-    code = _dtype_code(image)
-    if len(points.shape) != 2 or points.shape[1] != 2 or points.element_size() != 4 or not (
-            points.dtype == np.int32 if _is_native(points) else str(points.dtype) == "torch.int32"):
-        raise TypeError("points must be an (N, 2) int32 array of (x, y)")
-    h, w = image.shape
-    n = int(points.shape[0])
-    if out is None:
-        out = _empty_like((n, plan.n_poly), image)
-    else:
-        _check_operand(plan, out, "out")
-        assert tuple(out.shape) == (n, plan.n_poly) and _is_f64(out)
-    if n:
-        plan.transform_points_dev(image.data_ptr(), code, h, w, points.data_ptr(), n, out.data_ptr(), _current_stream_ptr(image))
-    return out
-
-
-def _empty_image(shape, dtype, like):
-    """Uninitialised device array of ``shape`` and NumPy ``dtype`` on ``like``'s device, of ``like``'s kind."""
-    if _is_native(like):
-        return _native.DeviceArray(shape, dtype, like.device.index)
-    import torch
-    tdtype = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.uint8): torch.uint8,
-              np.dtype(np.int16): torch.int16, np.dtype(np.uint16): getattr(torch, "uint16", None),
-              np.dtype(np.int64): torch.int64}[np.dtype(dtype)]
-    return torch.empty(shape, dtype=tdtype, device=like.device)
-
-
-def remove_background_device(image, method, parameter, clip=True, **method_kw):
-    """:mod:`mtflearn_amd.background` on a frame resident on the GPU (a torch tensor or a
-    :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` of float32 / float64 / uint8 / uint16 / int16).
-
-    ``method``: ``"opening"`` (``parameter`` = size), ``"rolling_ball"`` (radius) or ``"baseline"`` (sigma; ``num_iters``
-    as a keyword, default 10).  Returns ``(residual, background)`` as device arrays of the image's kind, in the image's dtype
-    (float64 for the baseline), the same numbers as the host ``remove_background_*``.  Runs on torch's current stream and no
-    pixel crosses to the host, so a frame goes to :func:`local_max_device` and :func:`points_moments_device` without PCIe."""
-    from .background import _method_parameter
-    if len(image.shape) != 2:
-        raise ValueError("image must be a 2D array.")
-    param = _method_parameter(method, parameter, method_kw)
-    if not image.is_cuda:
-        raise ValueError("image must live on the GPU")
-    if not _is_native(image) and not image.is_contiguous():
-        image = image.contiguous()
-    code = _image_code(image)
-    h, w = (int(v) for v in image.shape)
-    out_dtype = np.float64 if method == "baseline" else _numpy_dtype(image)
-    background = _empty_image((h, w), out_dtype, image)
-    residual = _empty_image((h, w), out_dtype, image)
-    lib = _native.load()
-    args = (image.device.index, c_void_p(image.data_ptr()), code, h, w)
-    outs = (int(bool(clip)), c_void_p(background.data_ptr()), c_void_p(residual.data_ptr()), c_void_p(_current_stream_ptr(image)))
-    if method == "opening":
-        _native.check(lib.zk_background_opening_dev(*args, param[0], param[1], *outs), "zk_background_opening_dev")
-    elif method == "rolling_ball":
-        _native.check(lib.zk_background_rolling_ball_dev(*args, param, *outs), "zk_background_rolling_ball_dev")
-    else:
-        (wy, wx), iters = param
-        _native.check(lib.zk_background_baseline_dev(*args, wy.ctypes.data_as(c_void_p), len(wy) - 1, wx.ctypes.data_as(c_void_p),
-                                                     len(wx) - 1, iters, *outs), "zk_background_baseline_dev")
-    return residual, background
-
-
-def _device_image(image):
-    """The :class:`mtflearn_amd.utils._Operand` of a device-resident image of any shape, on torch's current stream."""
-    from .utils import _Operand
-    if not image.is_cuda:
-        raise ValueError("image must live on the GPU")
-    if not _is_native(image) and not image.is_contiguous():
-        image = image.contiguous()
-    return _Operand(image, _current_stream_ptr(image))
-
-
-def normalize_image_device(image, mode="minmax", eps=1e-8, vmin=0.0, vmax=1.0):
-    """:func:`mtflearn_amd.utils.normalize_image` of an image resident on the GPU (a torch tensor or a :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` or ``(H, W, C)``
-    of float32 / float64 / uint8 / uint16 / int16).  Returns the float32 result as a device array of the same kind, the same
-    numbers as the host function; only the statistics (two floats, a count, three sums) cross to the host.  Runs on torch's
-    current stream."""
-    from .utils import _check_mode, _normalize_core
-    _check_mode(mode)
-    return _normalize_core(_device_image(image), mode, float(eps), float(vmin), float(vmax), False)
-
-
-def standardize_image_device(image):
-    """:func:`mtflearn_amd.utils.standardize_image` of an image resident on the GPU (as :func:`normalize_image_device`):
-    float32 for a float32 image, float64 otherwise, as a device array of the same kind."""
-    from .utils import _standardize_core
-    return _standardize_core(_device_image(image))
-
-
-def percentile_clip_device(image, low=1.0, high=99.0, method="auto", high_ratio_thresh=5.0, mad_k=8.0, iqr_k=3.0, eps=1e-8):
-    """:func:`mtflearn_amd.utils.percentile_clip` of an image resident on the GPU (as :func:`normalize_image_device`).  Returns
-    ``(out, did_clip, info)`` with ``out`` the float32 image (clipped or not) as a device array of the same kind and ``info``
-    the host function's dictionary; only the order statistics (at most 16 floats per call) cross to the host."""
-    from .utils import _check_method, _check_percentile, _clip_core
-    method = _check_method(method)
-    _check_percentile(high)
-    _check_percentile(low)
-    return _clip_core(_device_image(image), low, high, method, high_ratio_thresh, mad_k, iqr_k, eps)
-
-
-def render_gaussians_device(frame_dev, pts, sigma, amplitude=1, r_factor=3.0):
-    """:func:`mtflearn_amd.datasets.add_tapered_gaussian` into a frame resident on the GPU (a torch tensor or a
-    :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` of float32 / float64): the tapered Gaussians at the host points
-    ``pts`` are added in place and the frame is returned, the same numbers as the host function bit for bit.  Only the points
-    cross to the device.  Runs on torch's current stream, which is synchronised before the call returns."""
-    from .datasets import _points_and_amplitudes, _render_device
-    pts, amps = _points_and_amplitudes(len(frame_dev.shape), pts, sigma, amplitude, r_factor)
-    if not frame_dev.is_cuda:
-        raise ValueError("image must live on the GPU")
-    if not frame_dev.is_contiguous():
-        raise ValueError("the frame is added to in place and must be contiguous")
-    _dtype_code(frame_dev)
-    if len(pts) and frame_dev.numel():
-        _render_device(frame_dev, pts, amps, sigma, r_factor, True)
-    return frame_dev
-
-
-def honeycomb_image_device(lattice, like=None, **to_image_kw):
-    """:meth:`mtflearn_amd.datasets.HoneyCombLattice.to_image` with the image left on the GPU: the float32
-    ``(size, size)`` frame as a :class:`~mtflearn_amd._native.DeviceArray` on the default device, or, with ``like`` a torch
-    tensor (or a DeviceArray), as an array of that kind on that device.  ``to_image_kw``: ``sigma``, ``intensity_A``,
-    ``intensity_B``, ``normalize``.  The frame is born on the device and goes on to :func:`remove_background_device`,
-    :func:`local_max_device` and :func:`points_moments_device` without a host copy; only the site coordinates go up."""
-    from .datasets import _render_device
-    from .utils import _Operand, _map, _stats
-    unknown = set(to_image_kw) - {"sigma", "intensity_A", "intensity_B", "normalize"}
-    if unknown:
-        raise TypeError(f"to_image() got an unexpected keyword argument {sorted(unknown)[0]!r}")
-    sigma, pts, amps = lattice._render_lists(to_image_kw.get("sigma"), to_image_kw.get("intensity_A", 1.0),
-                                             to_image_kw.get("intensity_B", 0.5))
-    size = lattice.size
-    if like is None or _is_native(like):
-        _native.load()
-        _native.require_device()
-        device = _native.default_device() if like is None else like.device.index
-        img = _native.DeviceArray.from_numpy(np.zeros((size, size), np.float32), device)
-    else:
-        import torch
-        img = torch.zeros((size, size), dtype=torch.float32, device=like.device)
-    if len(pts) and size:
-        _render_device(img, pts, amps, sigma, 3.0, True)
-    if to_image_kw.get("normalize", False) and size:
-        operand = _Operand(img, _current_stream_ptr(img))
-        vmax = float(_stats(operand)[1])
-        if vmax > 0.0:
-            # x / vmax in float64 rounded once is the float32 quotient: 53 bits are more than 2 * 24 + 2
-            img = _map(operand, _native.MAP_DIVIDE, [vmax])
-    return img
-
-
-def _as_dtype_device(array, np_dtype, what):
-    """``array`` as a contiguous device array of ``np_dtype``: a torch tensor is converted on the device, a DeviceArray must
-    already have the type."""
-    if not array.is_cuda:
-        raise ValueError(f"{what} must live on the GPU")
-    if _is_native(array):
-        if array.dtype != np_dtype:
-            raise TypeError(f"{what} must be a {np.dtype(np_dtype).name} DeviceArray, not {array.dtype}")
-        return array
-    import torch
-    return array.to({np.float64: torch.float64, np.int64: torch.int64}[np_dtype]).contiguous()
-
-
-def find_regions_device(points, edges):
-    """:func:`mtflearn_amd.graph.find_regions` of points and bonds resident on the GPU: ``points`` ``(N, 2)`` (torch tensor of
-    any real type, e.g. what :func:`local_max_device` returns, converted to float64 on the device; or a float64
-    :class:`~mtflearn_amd._native.DeviceArray`), ``edges`` ``(E, 2)`` directed index pairs (torch integer tensor, or an int64
-    DeviceArray) on the same device.  Returns ``(offsets, vertices, ks, centers, adjacency)`` as device arrays of the same kind:
-    polygon ``f`` is ``vertices[offsets[f]:offsets[f + 1]]`` (int64), ``ks`` its size (int64), ``centers`` ``(F, 2)`` float64
-    bit-equal to ``nodes[region].mean(axis=0)``, ``adjacency`` ``(A, 2)`` int64 pairs of polygons that share a bond.  Only the
-    three counts cross to the host.  The edge values cannot be checked before the launch here: the device checks them, and
-    a pair outside ``[0, N)`` or a self-loop raises ``RuntimeError`` (``ZK_E_BADARG``) with nothing computed.  Runs on torch's
-    current stream, which is synchronised before the call returns."""
-    if len(points.shape) != 2 or points.shape[1] != 2:
-        raise ValueError(f"points must have shape (N, 2), not {tuple(points.shape)}")
-    if len(edges.shape) != 2 or edges.shape[1] != 2:
-        raise ValueError(f"edges must have shape (E, 2), not {tuple(edges.shape)}")
-    if not _is_native(edges) and (edges.dtype.is_floating_point or edges.dtype.is_complex or str(edges.dtype) == "torch.bool"):
-        raise ValueError(f"edges must be of an integer type, not {edges.dtype}")
-    points = _as_dtype_device(points, np.float64, "points")
-    edges = _as_dtype_device(edges, np.int64, "edges")
-    if points.device.index != edges.device.index:
-        raise ValueError("points and edges must live on the same device")
-    n, e = int(points.shape[0]), int(edges.shape[0])
-    if n + e + 4 >= 2 ** 31:
-        raise ValueError("find_regions_device needs len(points) + len(edges) + 4 < 2^31")
-    if n == 0 and e:
-        raise ValueError("edges without points")
-    lib = _native.load()
-    device, stream = points.device.index, c_void_p(_current_stream_ptr(points))
-    state, counts = c_void_p(), (c_int64 * 3)()
-    _native.check(lib.zk_find_regions_dev(device, c_void_p(points.data_ptr()), n, c_void_p(edges.data_ptr()), e, byref(state), counts,
-                                          None, None, None, None, None, stream), "zk_find_regions_dev")
-    f, v, a = (int(c) for c in counts)
-    offsets, vertices, ks = (_empty_image(shape, np.int64, points) for shape in ((f + 1,), (v,), (f,)))
-    centers, adjacency = _empty_like((f, 2), points), _empty_image((a, 2), np.int64, points)
-    _native.check(lib.zk_find_regions_dev(device, None, 0, None, 0, byref(state), counts, c_void_p(offsets.data_ptr()),
-                                          c_void_p(vertices.data_ptr()), c_void_p(ks.data_ptr()), c_void_p(centers.data_ptr()),
-                                          c_void_p(adjacency.data_ptr()), stream), "zk_find_regions_dev")
-    return offsets, vertices, ks, centers, adjacency
-
-
-def _resident_points(points, what, spare=0):
-    """``(points, ZK_* code)`` of resident ``(N, 2)`` points for ``zk_voronoi_cells_dev`` and ``zk_knn_distances_dev``: float64 or
-    int32 as they are, any other real torch type converted to float64 on the device.  ``what`` needs
-    ``len(points) < 2^26 - spare``."""
-    if len(points.shape) != 2 or points.shape[1] != 2:
-        raise ValueError(f"points must have shape (N, 2), not {tuple(points.shape)}")
-    if not points.is_cuda:
-        raise ValueError("points must live on the GPU")
-    if _is_native(points):
-        if points.dtype not in (np.float64, np.int32):
-            raise TypeError(f"points must be a float64 or int32 DeviceArray, not {points.dtype}")
-        code = _native.ZK_F64 if points.dtype == np.float64 else _native.ZK_I32
-    else:
-        import torch
-        if points.dtype.is_complex or points.dtype == torch.bool:
-            raise ValueError(f"points must be real numbers, not {points.dtype}")
-        if points.dtype not in (torch.float64, torch.int32):
-            points = points.to(torch.float64)
-        points = points.contiguous()
-        code = _native.ZK_F64 if points.dtype == torch.float64 else _native.ZK_I32
-    if int(points.shape[0]) + spare >= 2 ** 26:
-        raise ValueError(f"{what} needs len(points) < 2^26" + (f" - {spare}" if spare else ""))
-    return points, code
-
-
-def _voronoi_device(points, pad, mode, dmax, threshold, stream, what):
-    """Both phases of ``zk_voronoi_cells_dev`` on resident points; returns ``(ijs, ridge, edge)`` of the points' kind."""
-    points, code = _resident_points(points, what, spare=4)
-    if not (np.isfinite(pad) and pad > 0):
-        raise ValueError(f"pad must be positive and finite, not {pad}")
-    n = int(points.shape[0])
-    lengths = mode == _native.VORONOI_NEIGHBOURS
-    if n == 0:
-        return _empty_image((0, 2), np.int64, points), _empty_like((0,), points), _empty_like((0,), points)
-    lib = _native.load()
-    device = points.device.index
-    if stream is None:
-        stream = _current_stream_ptr(points)
-    stream = c_void_p(int(getattr(stream, "cuda_stream", stream)))
-    state, counts = c_void_p(), (c_int64 * 1)()
-    _native.check(lib.zk_voronoi_cells_dev(device, c_void_p(points.data_ptr()), code, n, pad, mode, dmax, threshold, byref(state), counts,
-                                           None, None, None, stream), "zk_voronoi_cells_dev")
-    m = int(counts[0])
-    ijs = _empty_image((m, 2), np.int64, points)
-    ridge, edge = (_empty_like((m,), points), _empty_like((m,), points)) if lengths else (None, None)
-    _native.check(lib.zk_voronoi_cells_dev(device, None, code, 0, pad, mode, dmax, threshold, byref(state), counts, c_void_p(ijs.data_ptr()),
-                                           c_void_p(ridge.data_ptr()) if lengths else None, c_void_p(edge.data_ptr()) if lengths else None,
-                                           stream), "zk_voronoi_cells_dev")
-    return ijs, ridge, edge
-
-
-def voronoi_neighbours_device(points, pad=0.05, stream=None):
-    """:func:`mtflearn_amd.graph.voronoi_neighbours` of points resident on the GPU: ``points`` ``(N, 2)``, a torch tensor of
-    any real type or a float64 / int32 :class:`~mtflearn_amd._native.DeviceArray`.  What :func:`local_max_device` returns --
-    ``(N, 2)`` int32, column 0 is x, column 1 is y -- is taken as it is and widened on the device; the neighbours do not depend
-    on which column is x.  Returns ``(ijs, ridge_lengths, edge_lengths)`` as device arrays of the same kind (int64 ``(M, 2)``,
-    float64 ``(M)``, float64 ``(M)``).  Only the row count crosses to the host.  The values cannot be checked before the launch
-    here: the device checks them, and a non-finite coordinate, two coincident points or a cell of more than 32 vertices (a point
-    with more than 32 Voronoi neighbours, or nearly as many: cells are clipped in bin order) raise ``RuntimeError``
-    (``ZK_E_BADARG``) with nothing computed.  Runs on ``stream`` (default: torch's current stream for tensors, the default
-    stream for a DeviceArray), which is synchronised before the call returns."""
-    return _voronoi_device(points, float(pad), _native.VORONOI_NEIGHBOURS, 0.0, 0.0, stream, "voronoi_neighbours_device")
-
-
-def estimate_d_device(points, threshold='otsu', return_k=False):
-    """:func:`mtflearn_amd.graph.estimate_d` of points resident on the GPU: ``points`` ``(N, 2)``, a torch tensor of any real
-    type or a float64 / int32 :class:`~mtflearn_amd._native.DeviceArray` -- what :func:`local_max_device` or
-    :func:`refine_points_device` return.  The points and their distance matrix stay on the device; a few hundred numbers per
-    pass (ranges, histograms, side sums) cross to the host, where the scalar rules run.  ``N < 12`` raises ``ValueError``;
-    a non-finite coordinate raises ``RuntimeError`` from the device.  Runs on torch's current stream."""
-    from . import graph
-    points, code = _resident_points(points, "estimate_d_device")
-    n = int(points.shape[0])
-    if n < graph.KNN:
-        raise ValueError(f"Expected n_neighbors <= n_samples_fit, but n_neighbors = {graph.KNN}, n_samples_fit = {n}")
-    device, stream = points.device.index, _current_stream_ptr(points)
-    dd = _empty_like((n, graph.KNN), points)
-    _native.check(_native.load().zk_knn_distances_dev(device, c_void_p(points.data_ptr()), code, n, graph.KNN, c_void_p(dd.data_ptr()),
-                                                      c_void_p(stream)), "zk_knn_distances_dev")
-    parts = graph._estimate_from_distances(device, dd.data_ptr(), n, stream, threshold)
-    return (parts["t"], parts["k"]) if return_k else parts["t"]
-
-
-def refine_points_device(image, points, size=3, mode=None):
-    """:func:`mtflearn_amd.features.refine_points` of a frame and key points resident on the GPU: ``image`` ``(H, W)`` float32 /
-    float64, ``points`` ``(N, 2)`` int32 ``(x, y)`` (what :func:`local_max_device` returns), both torch tensors or both
-    :class:`~mtflearn_amd._native.DeviceArray`.  Returns the ``(N, 2)`` float64 ``(x, y)`` centroids on the device, of the same
-    kind -- what :func:`vnn_graph_device`, :func:`estimate_d_device` and :func:`find_regions_device` accept; round them to
-    int32 for :func:`points_moments_device`.  The numbers are those of the host ``center_of_mass_refine``, bit for bit.  A
-    frame that is not float, ``N >= 2^24`` or a box that leaves the frame raise ``ValueError`` (the boxes are checked on the
-    device: nothing is written for such a point, and only the flag crosses to the host).  Runs on torch's current stream."""
-    if len(image.shape) != 2:
-        raise ValueError(f"refine_points_device needs a 2D image, not {len(image.shape)}-D")
-    if not image.is_cuda or not points.is_cuda:
-        raise ValueError("image and points must live on the GPU")
-    if _is_native(image) != _is_native(points) or image.device.index != points.device.index:
-        raise ValueError("image and points must be of one kind and on one device")
-    try:
-        code = _dtype_code(image)
-    except TypeError as e:
-        raise ValueError(f"refine_points_device needs a float frame: {e}") from None
-    if len(points.shape) != 2 or points.shape[1] != 2 or not (
-            points.dtype == np.int32 if _is_native(points) else str(points.dtype) == "torch.int32"):
-        raise TypeError("points must be an (N, 2) int32 array of (x, y)")
-    if not _is_native(image):
-        image, points = image.contiguous(), points.contiguous()
-    size = int(size)
-    if not 0 <= size <= 64:
-        raise ValueError(f"size must be in [0, 64], not {size}")
-    n = int(points.shape[0])
-    if n >= 2 ** 24:
-        raise ValueError("refine_points_device needs len(points) < 2^24 (the reference's label image has the frame's type)")
-    h, w = (int(v) for v in image.shape)
-    out = _empty_like((n, 2), image)
-    if n:
-        lib = _native.load()
-        rc = lib.zk_refine_points_dev(image.device.index, c_void_p(image.data_ptr()), code, h, w, c_void_p(points.data_ptr()), n, size,
-                                      _native.REFINE_DISK if mode == 'disk' else _native.REFINE_BOX, c_void_p(out.data_ptr()),
-                                      c_void_p(_current_stream_ptr(image)))
-        if rc == _native.ZK_E_BADARG:
-            raise ValueError(_native.last_error())
-        _native.check(rc, "zk_refine_points_dev")
-    return out
-
-
-def com_refine_device(image, points, size, threshold=None):
-    """:func:`mtflearn_amd.features.com_refine_points` of a frame and key points resident on the GPU: ``image`` ``(H, W)``
-    float32 / float64, ``points`` ``(N, 2)`` int32 or float64 ``(x, y)`` (what :func:`local_max_device` or
-    :func:`refine_points_device` return), both torch tensors or both :class:`~mtflearn_amd._native.DeviceArray`.  Returns the
-    ``(N, 2)`` float64 refined points on the device, of the same kind -- what :func:`vnn_graph_device`,
-    :func:`estimate_d_device` and :func:`find_regions_device` accept.  Rounding the points to window corners and the two final
-    additions are done on the device with the host function's own rounded operations: a point gives the same bits on either
-    route.  As there, the thresholds (``threshold='otsu'``: Otsu, anything else: Li) are defined on the window widened to
-    float64 and parity with scikit-image is unpinned.  There is NO border clearing here: every ``size x size`` window must lie
-    inside the frame, or ``ValueError`` is raised (the windows are checked on the device: nothing is written for such a
-    point, and only the flag crosses to the host) -- the contract of :func:`refine_points_device`.  A frame that is not float,
-    ``size`` outside ``[2, 64]`` or ``N >= 2^24`` raise ``ValueError`` too.  Runs on torch's current stream."""
-    if len(image.shape) != 2:
-        raise ValueError(f"com_refine_device needs a 2D image, not {len(image.shape)}-D")
-    if not image.is_cuda or not points.is_cuda:
-        raise ValueError("image and points must live on the GPU")
-    if _is_native(image) != _is_native(points) or image.device.index != points.device.index:
-        raise ValueError("image and points must be of one kind and on one device")
-    try:
-        code = _dtype_code(image)
-    except TypeError as e:
-        raise ValueError(f"com_refine_device needs a float frame: {e}") from None
-    kind = str(points.dtype).replace("torch.", "")
-    if len(points.shape) != 2 or points.shape[1] != 2 or kind not in ("int32", "float64"):
-        raise TypeError("points must be an (N, 2) int32 or float64 array of (x, y)")
-    if not _is_native(image):
-        image, points = image.contiguous(), points.contiguous()
-    if int(size) != size or not 2 <= int(size) <= 64:
-        raise ValueError(f"size must be an integer in [2, 64], not {size}")
-    n = int(points.shape[0])
-    if n >= 2 ** 24:
-        raise ValueError("com_refine_device needs len(points) < 2^24")
-    h, w = (int(v) for v in image.shape)
-    out = _empty_like((n, 2), image)
-    if n:
-        rc = _native.load().zk_com_refine_points_dev(image.device.index, c_void_p(image.data_ptr()), code, h, w, c_void_p(points.data_ptr()),
-                                                     _native.ZK_I32 if kind == "int32" else _native.ZK_F64, n, int(size),
-                                                     _native.THRESHOLD_OTSU if threshold == 'otsu' else _native.THRESHOLD_LI,
-                                                     c_void_p(out.data_ptr()), c_void_p(_current_stream_ptr(image)))
-        if rc == _native.ZK_E_BADARG:
-            raise ValueError(_native.last_error())
-        _native.check(rc, "zk_com_refine_points_dev")
-    return out
-
-
-def vnn_graph_device(points, dmax=None, threshold=0.1, pad=0.05, stream=None, threshold_method=None):
-    """:func:`mtflearn_amd.graph.vnn_graph` of points resident on the GPU (see :func:`voronoi_neighbours_device` for the
-    operands, the errors and the stream): the int64 ``(E, 2)`` sorted, symmetrised bonds as a device array of the points'
-    kind, ready for :func:`find_regions_device` -- key points go from :func:`local_max_device` to polygons without a host copy.
-    Without ``dmax`` it is ``estimate_d_device(points, threshold=threshold_method)``, as in the reference."""
-    if dmax is None:
-        dmax = estimate_d_device(points, threshold=threshold_method)
-    dmax, threshold = float(dmax), float(threshold)
-    if not dmax > 0:
-        raise ValueError(f"dmax must be positive, not {dmax}")
-    if not threshold > 0:
-        raise ValueError(f"threshold must be > 0, not {threshold}")
-    return _voronoi_device(points, float(pad), _native.VORONOI_GRAPH, dmax, threshold, stream, "vnn_graph_device")[0]
-
-
-def inverse_transform_device(zps, coeffs_dev, n_rows=None, method="lstsq", m_select=None, dtype=np.float64, out=None):
-    """The resident twin of ``ZPs.inverse_transform``: ``coeffs_dev`` is an ``(N, P)`` float64 torch tensor or ``DeviceArray`` of
-    real moments of ``zps``'s full set (k-means centres, class means, rows of ``points_moments_device``); the first ``n_rows``
-    of them (default: all) come back as an ``(n_rows, size, size)`` array of ``dtype`` (float64 / float32) of the same kind on the
-    same device, enqueued on torch's current stream (a ``DeviceArray``: the default stream) without synchronising.  The synthesis
-    table is ``zps``'s cached one (``method``, ``m_select`` as there); everything is checked before any device call."""
-    if not getattr(coeffs_dev, "is_cuda", False):
-        raise ValueError("coeffs_dev must live on the GPU")
-    if not coeffs_dev.is_contiguous():
-        raise ValueError("coeffs_dev must be contiguous")
-    if len(coeffs_dev.shape) != 2 or coeffs_dev.shape[1] != len(zps.n) or not _is_f64(coeffs_dev):
-        raise ValueError(f"coeffs_dev must be an (N, {len(zps.n)}) float64 matrix of real Zernike moments")
-    n_rows = int(coeffs_dev.shape[0] if n_rows is None else n_rows)
-    if not 0 <= n_rows <= coeffs_dev.shape[0]:
-        raise ValueError(f"n_rows must be between 0 and {coeffs_dev.shape[0]}")
-    np_dtype = zps._inverse_dtype(dtype)
-    entry = zps._synthesis_entry(method, m_select)
-    if entry["cond"] is not None and entry["cond"] > zps._COND_LIMIT:
-        warnings.warn(zps._cond_message(entry["cond"]), UserWarning, stacklevel=2)
-    shape = (n_rows, zps.size, zps.size)
-    if out is not None and (tuple(out.shape) != shape or not out.is_contiguous() or _numpy_dtype(out) != np_dtype
-                            or out.device.index != coeffs_dev.device.index):
-        raise ValueError(f"out must be a contiguous {shape} array of {np_dtype} on the device of coeffs_dev")
-    if coeffs_dev.device.index != zps._pick_device():
-        raise ValueError(f"coeffs_dev is on cuda:{coeffs_dev.device.index} but this ZPs computes on device {zps._pick_device()}: "
-                         "bind it to the array's device (ZPs.to_device / MTFLEARN_AMD_DEVICE)")
-    if out is None:
-        out = _empty_image(shape, np_dtype, coeffs_dev)
-    if n_rows == 0:
-        return out
-    synth = zps._synthesis_device(entry)
-    synth.apply_dev(coeffs_dev.data_ptr(), n_rows, out.data_ptr(), _native.dtype_code(np_dtype), _current_stream_ptr(coeffs_dev))
-    return out
-
-
-def _device_frame(image, what):
-    if len(image.shape) != 2:
-        raise ValueError(f"{what} needs a 2D image, not {len(image.shape)}-D")
-    if not image.is_cuda:
-        raise ValueError("image must live on the GPU")
-    if not _is_native(image) and not image.is_contiguous():
-        image = image.contiguous()
-    _image_code(image)
-    return image
-
-
-def denoise_svd_device(image, patch_size, n_components, extraction_step=None, return_s=False):
-    """:func:`mtflearn_amd.denoise_svd` of a frame resident on the GPU (a torch tensor or a
-    :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` of float32 / float64 / uint8 / uint16 / int16).  Returns the float64
-    clean frame as a device array of the same kind (and the singular values, a host array, with ``return_s``): the frame and
-    the result never cross to the host, only the thin factors of the randomized SVD do.  Runs on torch's current stream."""
-    from ._denoise_svd import _check_components, _denoise_svd_device, _svd_arguments
-    image = _device_frame(image, "denoise_svd_device")
-    patch, _, ii, jj = _svd_arguments(tuple(int(v) for v in image.shape), patch_size, extraction_step)
-    n_components = _check_components(n_components)
-    clean, s = _denoise_svd_device(image, patch, ii, jj, n_components)
-    return (clean, s) if return_s else clean
-
-
-def denoise_svd_memory_view_device(image, patch_size, n_components=None, threshold=0.9):
-    """:func:`mtflearn_amd.denoise.denoise_svd_memory_view` of a frame resident on the GPU (as :func:`denoise_svd_device`).
-    Returns ``(recon, explained_variance_ratio, n_components)`` with ``recon`` a float64 device array of the image's kind; the
-    ``(p^2, p^2)`` covariance and the eigenvectors are all that crosses to the host and back."""
-    from .denoise import _memory_view_device, _memory_view_patch
-    image = _device_frame(image, "denoise_svd_memory_view_device")
-    p = _memory_view_patch(tuple(int(v) for v in image.shape), patch_size)
-    return _memory_view_device(image, p, n_components, threshold)
+    return _device.code(tensor, FLOATS)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -905,7 +262,7 @@ class DeviceCompute:
         self.plan, self.n_poly = plan, plan.n_poly
 
     def empty(self, shape, like):
-        return _empty_like(shape, like)
+        return _device.empty(shape, np.float64, like)
 
     def stream(self, tensor):
         return _current_stream_ptr(tensor)

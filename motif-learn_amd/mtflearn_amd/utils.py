@@ -29,7 +29,7 @@ Deviations from the reference:
 
 There is no CPU fallback: without a HIP device every function but the two helpers raises ``RuntimeError``.  Frames already on
 the GPU go through ``normalize_image_device`` / ``standardize_image_device`` / ``percentile_clip_device`` of
-:mod:`mtflearn_amd.distributed`.
+:mod:`mtflearn_amd.resident`.
 """
 from __future__ import annotations
 
@@ -37,7 +37,8 @@ from ctypes import byref, c_int64, c_void_p
 
 import numpy as np
 
-from . import _native
+from . import _device, _native
+from ._device import to_host as _download
 
 __all__ = [
     "normalize_image",
@@ -61,9 +62,8 @@ class _Operand:
     element types, and what the ``zk_image_*_dev`` calls need of it."""
 
     def __init__(self, array, stream=0):
-        from .distributed import _image_code
         self.array = array
-        self.code = _image_code(array)
+        self.code = _device.code(array)
         self.shape = tuple(int(v) for v in array.shape)
         self.n = int(np.prod(self.shape, dtype=np.int64)) if self.shape else 1
         self.device = int(array.device.index)
@@ -96,10 +96,6 @@ def _upload(array):
     return _Operand(_native.DeviceArray.from_numpy(array, _native.default_device()))
 
 
-def _download(array):
-    return array.numpy() if isinstance(array, _native.DeviceArray) else array.cpu().numpy()
-
-
 def _stats(operand, center=None, wide=False):
     """``(min, max, n_nonfinite, sums)`` of ``zk_image_stats_dev``: float32 min / max over the finite elements, the count of
     the others, and float64 ``[sum x, sum |x|, sum x^2]`` -- or ``[sum (x - center)^2, 0, 0]`` with ``center``."""
@@ -130,9 +126,8 @@ def _order_stats(operand, ranks, center=None):
 def _map(operand, op, params, keep_nonfinite=False):
     """``zk_image_map_dev``: the elementwise pass ``op`` with up to four scalar ``params``; a device array of the operand's kind
     and shape, float32 (float64 for ``MAP_STANDARDIZE`` of a non-float32 image)."""
-    from .distributed import _empty_image
     dtype = np.float64 if (op == _native.MAP_STANDARDIZE and operand.code != _native.ZK_F32) else np.float32
-    out = _empty_image(operand.shape, dtype, operand.array)
+    out = _device.empty(operand.shape, dtype, operand.array)
     p = np.zeros(4, np.float64)
     p[:len(params)] = params
     _native.check(_native.load().zk_image_map_dev(*operand.head, op, p.ctypes.data_as(c_void_p), int(bool(keep_nonfinite)),
