@@ -780,7 +780,7 @@ int zk_project_dev(int device, const double* X_dev, int64_t n_rows, int n_featur
                    const double* components_dev, int n_components, double* Y_dev, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------
- * Clustering consumers of the moment matrix, csrc/zk_cluster.hip:
+ * Clustering consumers of the moment matrix, csrc/zk_rows.hip, zk_kmeans.hip, zk_mixture.hip:
  *   kmeans_lbs(X, n)   reference clustering/_clustering_functions.py:8-22  (sklearn KMeans(n, random_state).fit(X).labels_)
  *   gmm_lbs(X, n)      reference clustering/_clustering_functions.py:25-33 (sklearn GaussianMixture(n, type).fit(X).predict(X))
  * zk_rows = a float64 matrix (N, D), D <= 127, resident on one device together with the work buffers of these passes.

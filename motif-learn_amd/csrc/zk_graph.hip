@@ -8,17 +8,12 @@
 //                                   tau_rand_int state): compiled host code in the reference (numba) and compiled host code here,
 //                                   zk_force_layout_stage, operation for operation.
 // The sparse symmetrisation between them is SciPy's, as in the reference (mtflearn_amd/manifold.py).
-#include "zk_internal.h"
-#include "zk_fold.h"  // ZK_CONST / zk_const
+#include "zk_rows.h"  // the resident matrix; ZK_GLOBAL_PTR / ZK_LDS_PTR
 
 #include <cmath>
 #include <cstring>
 #include <limits>
 #include <vector>
-
-// the resident matrix (zk_cluster.hip)
-extern "C" const double* zk_rows_data(const zk_rows* m);
-int zk_rows_shape(const zk_rows* m, int* device, int64_t* n_rows, int* n_features, void** stream);
 
 namespace {
 
@@ -169,8 +164,6 @@ __global__ __launch_bounds__(64 * WAVES) void knn_kernel(const double* __restric
 // a quarter let four times as many values into the insertion code), two query blocks per wave with alternating accumulator
 // chains (782 workgroups for 256 CUs: four on some, three on most) -- both 27-28 ms.
 typedef double zk_v4d __attribute__((ext_vector_type(4)));
-#define ZK_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define ZK_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 // unit rows in the blocked layout: `steps` feature steps of four (the kernel instance that holds D, zero features beyond it), rows
 // padded with zeros to `Np` (a multiple of 64)
@@ -411,16 +404,13 @@ __global__ __launch_bounds__(256) void affinity_kernel(const double* __restrict_
 extern "C" int zk_rows_knn_correlation(zk_rows* m, int k, int local_connectivity, double perplexity, int64_t* ind_out, double* dist_out,
                                        double* P_out) {
   if (!m || !ind_out || !dist_out) return zk_fail(ZK_E_BADARG, "null pointer");
-  int device = 0, D = 0;
-  int64_t N = 0;
-  void* stream_v = nullptr;
-  int rc = zk_rows_shape(m, &device, &N, &D, &stream_v);
-  if (rc) return rc;
+  const int D = m->D;
+  const int64_t N = m->N;
   if (k < 1 || k > 64 || k > N) return zk_fail(ZK_E_BADARG, "need 1 <= n_neighbors <= min(64, n_samples)");
   if (P_out && (local_connectivity < 0 || local_connectivity >= k || !(perplexity > 0.0))) return zk_fail(ZK_E_BADARG, "bad affinity parameters");
   if ((size_t)64 * D * sizeof(double) + 16 * 64 * 16 > 64 * 1024) return zk_fail(ZK_E_BADARG, "too many features for the query tile");
-  ZK_ON_DEVICE(device);
-  hipStream_t s = (hipStream_t)stream_v;
+  ZK_ON_DEVICE(m->device);
+  hipStream_t s = m->stream;
   const long long Np = (N + 7) & ~7LL;
   double *Z = nullptr, *Zt = nullptr, *d_dist = nullptr, *d_P = nullptr;
   long long* d_ind = nullptr;
@@ -449,7 +439,7 @@ extern "C" int zk_rows_knn_correlation(zk_rows* m, int k, int local_connectivity
     return zk_hip_fail(e, "hipMalloc(kNN buffers)");
   }
   if (mfma) {
-    hipLaunchKernelGGL(unit_rows_blocked_kernel, dim3((unsigned)((Np64 + 255) / 256)), dim3(256), 0, s, zk_rows_data(m), (long long)N, D, Np64,
+    hipLaunchKernelGGL(unit_rows_blocked_kernel, dim3((unsigned)((Np64 + 255) / 256)), dim3(256), 0, s, m->X, (long long)N, D, Np64,
                        steps, Z);
     const int sb = steps <= 12 ? 4 : 2;  // candidate blocks per stage (the kernel's SB)
     const size_t stage = (size_t)sb * steps * 64 * sizeof(double);
@@ -504,7 +494,7 @@ extern "C" int zk_rows_knn_correlation(zk_rows* m, int k, int local_connectivity
       part_bufs[1] = d_pdist;
     }
   } else {
-    hipLaunchKernelGGL(unit_rows_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, zk_rows_data(m), (long long)N, D, Np, Z, Zt);
+    hipLaunchKernelGGL(unit_rows_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, m->X, (long long)N, D, Np, Z, Zt);
     const size_t lds = (size_t)64 * D * sizeof(double);
     const unsigned grid = (unsigned)((N + 63) / 64);
     if (k <= 16)

@@ -5,7 +5,7 @@
 and ``GaussianMixture(n, covariance_type, random_state).fit(X).predict(X)``, each followed by the reference's relabelling by
 cluster size.  The ``(N, D)`` matrix is uploaded once (or adopted where it already is: ``DeviceRows.adopt``) and every pass
 over it -- squared distances to seeding candidates, Lloyd assignment with the per-cluster sums, the mixture's E step and the
-weighted second moments of its M step -- is a kernel of ``csrc/zk_cluster.hip``.  What happens between passes is
+weighted second moments of its M step -- is a kernel of ``csrc/zk_rows.hip``, ``zk_kmeans.hip`` or ``zk_mixture.hip``.  What happens between passes is
 scikit-learn's own control flow, restated here on ``k x D``-sized arrays: the k-means++ draws from the caller's
 ``RandomState`` (same calls in the same order, so the same candidates), centre averaging, the centre-shift / strict
 convergence tests, empty-cluster relocation, Cholesky factors of the covariances (SciPy), the lower-bound test.  References

@@ -87,7 +87,7 @@ if os.path.exists(cl):
     log = [l.rstrip() for l in open(os.path.join(G, f"{TAG}_cluster.log")) if l.startswith(("matrix", "  ", "kmeans_fit", "gmm_fit"))]
     with open(os.path.join(P, f"{TAG}_cluster_kernel_stats.csv"), "w") as f:
         f.write("# rocprofv3 --kernel-trace --stats --output-format csv -- python3 motif-learn_amd/tools/time_clustering.py   (1 x MI355X)\n")
-        f.write("# clustering consumers (csrc/zk_cluster.hip) on a resident 4 068 289 x 45 float64 matrix (1.46 GB), k = 6; the tool's own\n")
+        f.write("# clustering consumers (csrc/zk_rows.hip, zk_kmeans.hip, zk_mixture.hip) on a resident 4 068 289 x 45 float64 matrix (1.46 GB), k = 6; the tool's own\n")
         f.write("# wall-clock lines (synchronous C-ABI calls: table upload + kernel + reduction + a few hundred bytes back):\n")
         for l in log:
             f.write("#   " + l + "\n")

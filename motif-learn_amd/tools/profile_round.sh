@@ -19,6 +19,6 @@ for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_IN
   k=$((k+1))
   timeout -k 10 400 rocprofv3 --pmc $set --output-format csv -d $O/${TAG}_sq$k -o p -- python3 $R/motif-learn_amd/tools/run_dense.py --reps 2 > $O/${TAG}_sq$k.log 2>&1
 done
-# (4) the clustering consumers (zk_cluster.hip): kernel trace of tools/time_clustering.py
+# (4) the clustering consumers (zk_rows.hip, zk_kmeans.hip, zk_mixture.hip): kernel trace of tools/time_clustering.py
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_cluster -o c -- python3 $R/motif-learn_amd/tools/time_clustering.py > $O/${TAG}_cluster.log 2>&1
 find $O/${TAG}_* -name "*.csv" | head -40

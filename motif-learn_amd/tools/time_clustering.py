@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the clustering passes (csrc/zk_cluster.hip) on a resident (N, D) matrix: per-pass wall time of the synchronous C-ABI
+"""Times the clustering passes (csrc/zk_rows.hip, zk_kmeans.hip, zk_mixture.hip) on a resident (N, D) matrix: per-pass wall time of the synchronous C-ABI
 calls (kernel + reduction + a few hundred bytes of D2H) and the whole kmeans_lbs / gmm_lbs against scikit-learn on the host.
 Usage: time_clustering.py [N] [D] [k] [--sklearn]"""
 import os, sys, time

@@ -1,4 +1,4 @@
-"""The row passes of csrc/zk_cluster.hip (mtflearn_amd.clustering.DeviceRows) stated by another route.
+"""The row passes of csrc/zk_rows.hip, zk_kmeans.hip and zk_mixture.hip (mtflearn_amd.clustering.DeviceRows) stated by another route.
 
 Every pass is written in ``np.longdouble`` (64-bit mantissa on x86: 2^11 times finer than the kernels' float64), in row
 chunks so that memory stays small.  Decisions are ordered by (value, index) -- the first minimum / maximum wins, as in

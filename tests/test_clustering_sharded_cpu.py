@@ -15,7 +15,7 @@ from conftest import ROOT
 
 
 class HostRows:
-    """NumPy stand-in for ``mtflearn_amd.clustering.DeviceRows`` (the passes of csrc/zk_cluster.hip)."""
+    """NumPy stand-in for ``mtflearn_amd.clustering.DeviceRows`` (the passes of csrc/zk_rows.hip, zk_kmeans.hip and zk_mixture.hip)."""
 
     def __init__(self, X):
         self.X = np.ascontiguousarray(X, dtype=np.float64)

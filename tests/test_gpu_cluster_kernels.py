@@ -1,4 +1,4 @@
-"""The kernels of csrc/zk_cluster.hip against tests/cluster_reference.py: past one tile per wave, at every template
+"""The kernels of csrc/zk_rows.hip, zk_kmeans.hip and zk_mixture.hip against tests/cluster_reference.py: past one tile per wave, at every template
 instantiation, at ties, with non-finite rows, and at the limits the C ABI refuses.
 
 C1 (``test_exact_*``) uses matrices of integers / 4 with one column holding ``r mod 1024`` and one ``r // 1024``: every sum a

@@ -251,7 +251,7 @@ def matrix_core_estep_cases():
 
 
 def test_row_passes_on_edge_shapes():
-    """Every pass of csrc/zk_cluster.hip against its NumPy statement (the stand-in of tests/test_clustering_sharded_cpu.py) on
+    """Every pass of csrc/zk_rows.hip, zk_kmeans.hip and zk_mixture.hip against its NumPy statement (the stand-in of tests/test_clustering_sharded_cpu.py) on
     the shapes where tiling can go wrong: 1 to 127 features (odd, even, exactly 64), row counts below / at / just past a
     64-row tile, one cluster to more than the register-resident limit, ragged last tiles."""
     import cluster_reference as ref
