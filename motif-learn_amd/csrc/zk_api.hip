@@ -287,8 +287,6 @@ static int check_dtype(int dtype) {
   return 0;
 }
 
-static size_t elem_size(int dtype) { return dtype == ZK_F32 ? 4 : 8; }
-
 extern "C" int zk_transform_patches_dev(zk_plan* p, const void* patches, int dtype, int64_t n_patches,
                                         double* out, void* hip_stream) {
   if (!p) return zk_fail(ZK_E_BADARG, "null plan");
@@ -414,7 +412,7 @@ extern "C" int zk_transform_points_dev(zk_plan* p, const void* image, int dtype,
   // Plans without the key-point kernel (n_max > 16, sets or bases off the separable path): cut the windows
   // on the device into a plan-owned batch, chunk by chunk, and run the batch path on it -- what the
   // reference does on the host (features/_keypoint.py:60-78 + _zps.py:146-157).
-  const size_t patch_bytes = (size_t)p->size * p->size * elem_size(dtype);
+  const size_t patch_bytes = (size_t)p->size * p->size * zk_elem_size(dtype);
   int64_t chunk = (int64_t)((size_t)1 << 30) / (int64_t)patch_bytes;  // <= 1 GiB of windows at a time
   if (chunk < 64) chunk = 64;
   if (chunk > n_points) chunk = n_points;

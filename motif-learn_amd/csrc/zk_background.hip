@@ -39,8 +39,6 @@ constexpr int RB_WAVES = 4;
 constexpr int RB_TW = 64 * RB_NX, RB_TH = RB_WAVES * RB_TY;
 constexpr int RB_MAX_R = 1536;           // two staged rows of (RB_TW + 2 R) float64 stay within 64 KiB of LDS
 
-size_t element_size(int dtype) { return dtype == ZK_F64 ? 8 : dtype == ZK_F32 ? 4 : dtype == ZK_U8 ? 1 : 2; }
-
 // SciPy's 'reflect' boundary: period 2n, the second half mirrored
 __device__ __forceinline__ int reflect_index(int i, int n) {
   if ((unsigned)i < (unsigned)n) return i;
@@ -421,7 +419,7 @@ int run_host(int device, const args& a, const void* img_host, int dtype, int64_t
   int rc = check_common(dtype, H, W, img_host, bg_host);
   if (rc || (rc = check_method(a))) return rc;
   ZK_ON_DEVICE(device);
-  const size_t in_bytes = (size_t)H * W * element_size(dtype);
+  const size_t in_bytes = (size_t)H * W * zk_elem_size(dtype);
   const size_t out_bytes = a.method == M_BASELINE ? (size_t)H * W * 8 : in_bytes;
   dev_buf d_img, d_bg, d_res;
   if ((rc = d_img.alloc(in_bytes)) || (rc = d_bg.alloc(out_bytes)) || (res_host && (rc = d_res.alloc(out_bytes)))) return rc;

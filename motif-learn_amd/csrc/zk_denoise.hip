@@ -36,8 +36,6 @@ constexpr int ZK_DN_LC = 16;        // columns of Q / Y per pass of apply and ap
 constexpr int ZK_DN_CHUNKS = 512;   // most window chunks of apply_t
 constexpr int ZK_DN_MAX_P = 48;     // largest patch edge of the moments kernel (its border tables stay within 64 KiB of LDS)
 
-size_t element_size(int dtype) { return dtype == ZK_F64 ? 8 : dtype == ZK_F32 ? 4 : dtype == ZK_U8 ? 1 : 2; }
-
 // the window grid of one call: origins checked on the host, then resident
 struct grid_desc {
   int H, W, ph, pw, ni, nj;
@@ -519,7 +517,7 @@ extern "C" int zk_windows_apply(int device, const void* image_host, int dtype, i
   const size_t D = (size_t)patch_h * patch_w, N = (size_t)n_rows * n_cols;
   staged img, Q, mu;
   dev_buf Y;
-  if ((rc = img.up(image_host, (size_t)height * width * element_size(dtype))) || (rc = Q.up(Q_host, D * n_columns * 8)) ||
+  if ((rc = img.up(image_host, (size_t)height * width * zk_elem_size(dtype))) || (rc = Q.up(Q_host, D * n_columns * 8)) ||
       (mean_host && (rc = mu.up(mean_host, D * 8))) || (rc = Y.alloc(N * n_columns * 8)))
     return rc;
   if ((rc = apply_dev(device, img.b.p, dtype, height, width, patch_h, patch_w, row_origins, n_rows, col_origins, n_cols, Q.b.as<double>(),
@@ -546,7 +544,7 @@ extern "C" int zk_windows_apply_t(int device, const void* image_host, int dtype,
   const size_t D = (size_t)patch_h * patch_w, N = (size_t)n_rows * n_cols;
   staged img, Y;
   dev_buf Z;
-  if ((rc = img.up(image_host, (size_t)height * width * element_size(dtype))) || (rc = Y.up(Y_host, N * n_columns * 8)) ||
+  if ((rc = img.up(image_host, (size_t)height * width * zk_elem_size(dtype))) || (rc = Y.up(Y_host, N * n_columns * 8)) ||
       (rc = Z.alloc(D * n_columns * 8)))
     return rc;
   if ((rc = apply_t_dev(device, img.b.p, dtype, height, width, patch_h, patch_w, row_origins, n_rows, col_origins, n_cols, Y.b.as<double>(),
@@ -570,7 +568,7 @@ extern "C" int zk_windows_moments(int device, const void* image_host, int dtype,
   const size_t D = (size_t)patch_h * patch_w;
   staged img;
   dev_buf mu, C;
-  if ((rc = img.up(image_host, (size_t)height * width * element_size(dtype))) || (rc = mu.alloc(D * 8)) || (rc = C.alloc(D * D * 8))) return rc;
+  if ((rc = img.up(image_host, (size_t)height * width * zk_elem_size(dtype))) || (rc = mu.alloc(D * 8)) || (rc = C.alloc(D * D * 8))) return rc;
   if ((rc = moments_dev(device, img.b.p, dtype, height, width, patch_h, patch_w, mu.as<double>(), C.as<double>(), (hipStream_t)0))) return rc;
   ZK_HIP(hipMemcpy(mean_host, mu.p, D * 8, hipMemcpyDeviceToHost));
   ZK_HIP(hipMemcpy(cov_host, C.p, D * D * 8, hipMemcpyDeviceToHost));

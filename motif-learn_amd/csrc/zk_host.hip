@@ -1,33 +1,12 @@
 // zk_host.hip -- the host-buffer entry points of the C ABI (what ZPs.transform calls with NumPy arrays):
-// zk_transform_patches / zk_transform_frame / zk_transform_points / zk_frame_maps.
-//
-// A job is cut into chunks of at most `host_chunk` bytes of input + output (default 256 MiB); chunk c goes
-//     H2D on the ring's copy-in stream  ->  kernel on the plan's stream  ->  D2H on the ring's copy-out stream
-// through one of ZK_RING_SLOTS device slots, consecutive chunks overlapping (events order the three streams;
-// the host only waits when it needs a slot back).  The device footprint is the ring (<= 3 chunks), whatever
-// the job size: a 4096^2 frame at n_max 10 needs 0.8 GB of staging instead of the 9 GB result.
-//
-// Host memory: copies straight from / into the caller's arrays.  Page-locked arrays (zk_host_alloc -- the
-// Python layer hands its results out of a pool of them -- or anything hipHostRegister'ed) move by DMA at
-// link speed and fully asynchronously; pageable arrays go through the runtime's own staging, which blocks
-// the calling thread per copy (the kernel of the chunk before still overlaps with it).
+// zk_transform_patches / zk_transform_frame / zk_transform_points / zk_frame_maps / zk_moment_maps / zk_points_maps.
+// Each cuts its job into chunks and sends them through the plan's staging ring; the protocol is zk_ring.h's.
 #include <string.h>
 
-#include "zk_internal.h"
-
-#define ZK_RING_SLOTS 3
-
+#include "zk_ring.h"
 
 struct zk_host_ring {
-  void* d_in[ZK_RING_SLOTS] = {};
-  size_t in_cap[ZK_RING_SLOTS] = {};
-  void* d_out[ZK_RING_SLOTS] = {};
-  size_t out_cap[ZK_RING_SLOTS] = {};
-  hipEvent_t ev_in[ZK_RING_SLOTS] = {};    // H2D of the slot's chunk done
-  hipEvent_t ev_k[ZK_RING_SLOTS] = {};     // kernel of the slot's chunk done
-  hipEvent_t ev_out[ZK_RING_SLOTS] = {};   // D2H of the slot's chunk done
-  bool out_busy[ZK_RING_SLOTS] = {};
-  hipStream_t s_in = nullptr, s_out = nullptr;
+  zk_ring ring;
   void* d_frame = nullptr;                 // whole frame (+ points) of the dense / key-point calls
   size_t frame_cap = 0;
   void* d_raw[ZK_RING_SLOTS] = {};         // narrow inputs (ZK_U8 / U16 / I16) as they arrive, before widening
@@ -36,14 +15,8 @@ struct zk_host_ring {
 
 namespace {
 
-size_t elem_size(int dtype) { return dtype == ZK_U8 ? 1 : (dtype == ZK_U16 || dtype == ZK_I16) ? 2 : dtype == ZK_F32 ? 4 : 8; }
 bool is_narrow(int dtype) { return dtype == ZK_U8 || dtype == ZK_U16 || dtype == ZK_I16; }
 int kernel_dtype(int dtype) { return is_narrow(dtype) ? ZK_F32 : dtype; }  // what the kernels read
-
-int check_dtype(int dtype) {
-  if (dtype < ZK_F32 || dtype > ZK_I16) return zk_fail(ZK_E_BADARG, "dtype must be ZK_F32, ZK_F64, ZK_U8, ZK_U16 or ZK_I16");
-  return 0;
-}
 
 // narrow integers -> float32 (exact), 4 elements per thread
 template <typename S>
@@ -76,77 +49,43 @@ size_t chunk_bytes(const zk_plan* p) {
   return (size_t)(mb > 0 ? mb : 256) << 20;
 }
 
+// What every entry point refuses before it touches the device, in this order.  An entry point without a dtype passes
+// ZK_F64, one without a frame H = W = 1, one without a count unit = nullptr.  1: an empty job, nothing to do.
+int check_job(const zk_plan* p, int dtype, int64_t H, int64_t W, const char* unit, int64_t n, bool pointers) {
+  if (!p) return zk_fail(ZK_E_BADARG, "null plan");
+  if (dtype < ZK_F32 || dtype > ZK_I16) return zk_fail(ZK_E_BADARG, "dtype must be ZK_F32, ZK_F64, ZK_U8, ZK_U16 or ZK_I16");
+  if (H <= 0 || W <= 0) return zk_fail(ZK_E_BADARG, "bad frame shape");
+  if (unit && n < 0) return zk_fail(ZK_E_BADARG, std::string("negative ") + unit + " count");
+  if (unit && n == 0) return 1;
+  if (!pointers) return zk_fail(ZK_E_BADARG, "null host pointer");
+  return 0;
+}
+
+// the plan's ring, created on the first host call
 int ring_get(zk_plan* p, zk_host_ring** out) {
   if (!p->ring) {
-    zk_host_ring* r = new (std::nothrow) zk_host_ring();
-    if (!r) return zk_fail(ZK_E_NOMEM, "out of host memory");
-    p->ring = r;
-    ZK_HIP(hipStreamCreateWithFlags(&r->s_in, hipStreamNonBlocking));
-    ZK_HIP(hipStreamCreateWithFlags(&r->s_out, hipStreamNonBlocking));
-    for (int k = 0; k < ZK_RING_SLOTS; ++k) {
-      ZK_HIP(hipEventCreateWithFlags(&r->ev_in[k], hipEventDisableTiming));
-      ZK_HIP(hipEventCreateWithFlags(&r->ev_k[k], hipEventDisableTiming));
-      ZK_HIP(hipEventCreateWithFlags(&r->ev_out[k], hipEventDisableTiming));
+    p->ring = new (std::nothrow) zk_host_ring();
+    if (!p->ring) return zk_fail(ZK_E_NOMEM, "out of host memory");
+    const int rc = zk_ring_create(&p->ring->ring);
+    if (rc) {
+      zk_host_release(p);
+      return rc;
     }
   }
-  for (int k = 0; k < ZK_RING_SLOTS; ++k) p->ring->out_busy[k] = false;
   *out = p->ring;
-  return 0;
-}
-
-// wait until every copy of the job has landed, whatever happened before
-int ring_drain(zk_plan* p, zk_host_ring* r, int rc) {
-  const hipError_t a = hipStreamSynchronize(r->s_in), b = hipStreamSynchronize(p->stream),
-                   c = hipStreamSynchronize(r->s_out);
-  if (rc) return rc;
-  if (a != hipSuccess) return zk_hip_fail(a, "hipStreamSynchronize(copy-in)");
-  if (b != hipSuccess) return zk_hip_fail(b, "hipStreamSynchronize(kernel)");
-  if (c != hipSuccess) return zk_hip_fail(c, "hipStreamSynchronize(copy-out)");
-  return 0;
-}
-
-// Software pipeline over the chunks of a job: chunk c is staged in and its kernel enqueued BEFORE the copy-out
-// of chunk c-1 is issued, so that a copy that blocks the calling thread (pageable memory) still runs under the
-// kernel of the next chunk.  `launch(c, slot)` / `copy_out(c, slot)` return 0 or a negative code; the streams are
-// drained before returning, whatever happened.
-template <class L, class O>
-int run_chunks(zk_plan* p, zk_host_ring* r, int n_chunks, L launch, O copy_out) {
-  int rc = 0;
-  for (int c = 0; c <= n_chunks && !rc; ++c) {
-    if (c < n_chunks) rc = launch(c, c % ZK_RING_SLOTS);
-    if (c > 0 && !rc) rc = copy_out(c - 1, (c - 1) % ZK_RING_SLOTS);
-  }
-  return ring_drain(p, r, rc);
-}
-
-// the slot is about to be reused: its previous D2H must have left d_out, its previous kernel d_in
-int slot_acquire(zk_host_ring* r, int slot) {
-  if (r->out_busy[slot]) {
-    ZK_HIP(hipEventSynchronize(r->ev_out[slot]));
-    r->out_busy[slot] = false;
-  }
   return 0;
 }
 
 }  // namespace
 
 void zk_host_release(zk_plan* p) {
-  zk_host_ring* r = p->ring;
-  if (!r) return;
-  if (r->s_in) (void)hipStreamSynchronize(r->s_in);
-  if (r->s_out) (void)hipStreamSynchronize(r->s_out);
-  for (int k = 0; k < ZK_RING_SLOTS; ++k) {
-    if (r->d_in[k]) (void)hipFree(r->d_in[k]);
-    if (r->d_raw[k]) (void)hipFree(r->d_raw[k]);
-    if (r->d_out[k]) (void)hipFree(r->d_out[k]);
-    if (r->ev_in[k]) (void)hipEventDestroy(r->ev_in[k]);
-    if (r->ev_k[k]) (void)hipEventDestroy(r->ev_k[k]);
-    if (r->ev_out[k]) (void)hipEventDestroy(r->ev_out[k]);
-  }
-  if (r->d_frame) (void)hipFree(r->d_frame);
-  if (r->s_in) (void)hipStreamDestroy(r->s_in);
-  if (r->s_out) (void)hipStreamDestroy(r->s_out);
-  delete r;
+  zk_host_ring* h = p->ring;
+  if (!h) return;
+  zk_ring_destroy(&h->ring);
+  for (int k = 0; k < ZK_RING_SLOTS; ++k)
+    if (h->d_raw[k]) (void)hipFree(h->d_raw[k]);
+  if (h->d_frame) (void)hipFree(h->d_frame);
+  delete h;
   p->ring = nullptr;
 }
 
@@ -189,57 +128,36 @@ extern "C" int zk_host_free(void* ptr) {
 // ------------------------------------------------------------------------------------------------------
 extern "C" int zk_transform_patches(zk_plan* p, const void* patches_host, int dtype, int64_t n_patches,
                                     double* out_host) {
-  if (!p) return zk_fail(ZK_E_BADARG, "null plan");
-  int rc = check_dtype(dtype);
-  if (rc) return rc;
-  if (n_patches < 0) return zk_fail(ZK_E_BADARG, "negative patch count");
-  if (n_patches == 0) return 0;
-  if (!patches_host || !out_host) return zk_fail(ZK_E_BADARG, "null host pointer");
+  int rc = check_job(p, dtype, 1, 1, "patch", n_patches, patches_host && out_host);
+  if (rc) return rc < 0 ? rc : 0;
   ZK_ON_PLAN_DEVICE(p);
-  zk_host_ring* r;
-  if ((rc = ring_get(p, &r))) return rc;
+  zk_host_ring* h;
+  if ((rc = ring_get(p, &h))) return rc;
+  zk_ring* r = &h->ring;
   const int kdt = kernel_dtype(dtype);
   const bool narrow = is_narrow(dtype);
   const size_t px_per = (size_t)p->size * p->size;
-  const size_t raw_unit = px_per * elem_size(dtype), in_unit = px_per * elem_size(kdt),
+  const size_t raw_unit = px_per * zk_elem_size(dtype), in_unit = px_per * zk_elem_size(kdt),
                out_unit = (size_t)p->n_poly * sizeof(double);
-  int64_t chunk = (int64_t)(chunk_bytes(p) / (in_unit + out_unit)) & ~(int64_t)255;  // whole waves of 64 patches
-  if (chunk < 256) chunk = 256;
-  if (chunk > n_patches) chunk = n_patches;
-  const int n_chunks = (int)((n_patches + chunk - 1) / chunk);
-  auto count = [&](int c) { return n_patches - c * chunk < chunk ? n_patches - c * chunk : chunk; };
+  const zk_chunks ch = zk_chunk_plan(chunk_bytes(p), in_unit + out_unit, 256, n_patches);  // whole waves of 64 patches
   p->job_units = n_patches;
   struct reset_units {
     zk_plan* p;
     ~reset_units() { p->job_units = 0; }
   } reset{p};
-  return run_chunks(
-      p, r, n_chunks,
-      [&](int c, int slot) -> int {
-        int e = slot_acquire(r, slot);
-        if (!e) e = zk_ensure(&r->d_in[slot], &r->in_cap[slot], (size_t)chunk * in_unit);
-        if (!e && narrow) e = zk_ensure(&r->d_raw[slot], &r->raw_cap[slot], (size_t)chunk * raw_unit);
-        if (!e) e = zk_ensure(&r->d_out[slot], &r->out_cap[slot], (size_t)chunk * out_unit);
-        if (e) return e;
-        // the slot's previous kernels must have consumed the landing buffer before the next H2D overwrites it
-        if (c >= ZK_RING_SLOTS) ZK_HIP(hipStreamWaitEvent(r->s_in, r->ev_k[slot], 0));
-        ZK_HIP(hipMemcpyAsync(narrow ? r->d_raw[slot] : r->d_in[slot], (const char*)patches_host + (size_t)c * chunk * raw_unit,
-                              (size_t)count(c) * raw_unit, hipMemcpyHostToDevice, r->s_in));
-        ZK_HIP(hipEventRecord(r->ev_in[slot], r->s_in));
-        ZK_HIP(hipStreamWaitEvent(p->stream, r->ev_in[slot], 0));
-        if (narrow && (e = widen(dtype, r->d_raw[slot], (float*)r->d_in[slot], (long long)count(c) * (long long)px_per, p->stream)))
-          return e;
-        if ((e = zk_transform_patches_dev(p, r->d_in[slot], kdt, count(c), (double*)r->d_out[slot], p->stream))) return e;
-        ZK_HIP(hipEventRecord(r->ev_k[slot], p->stream));
-        return 0;
+  return zk_ring_run(
+      r, p->stream, ch.n_chunks,
+      [&](int64_t c, int slot) -> int {
+        int e = zk_ring_slot(r, slot, (size_t)ch.chunk * in_unit, (size_t)ch.chunk * out_unit);
+        if (!e && narrow) e = zk_ensure(&h->d_raw[slot], &h->raw_cap[slot], (size_t)ch.chunk * raw_unit);
+        if (!e)
+          e = zk_ring_up(r, p->stream, c, slot, narrow ? h->d_raw[slot] : r->d_in[slot],
+                         (const char*)patches_host + (size_t)ch.first(c) * raw_unit, (size_t)ch.count(c) * raw_unit);
+        if (!e && narrow) e = widen(dtype, h->d_raw[slot], (float*)r->d_in[slot], (long long)ch.count(c) * (long long)px_per, p->stream);
+        return e ? e : zk_transform_patches_dev(p, r->d_in[slot], kdt, ch.count(c), (double*)r->d_out[slot], p->stream);
       },
-      [&](int c, int slot) -> int {
-        ZK_HIP(hipStreamWaitEvent(r->s_out, r->ev_k[slot], 0));
-        ZK_HIP(hipMemcpyAsync((char*)out_host + (size_t)c * chunk * out_unit, r->d_out[slot], (size_t)count(c) * out_unit,
-                              hipMemcpyDeviceToHost, r->s_out));
-        ZK_HIP(hipEventRecord(r->ev_out[slot], r->s_out));
-        r->out_busy[slot] = true;
-        return 0;
+      [&](int64_t c, int slot) -> int {
+        return zk_ring_down(r, slot, (char*)out_host + (size_t)ch.first(c) * out_unit, (size_t)ch.count(c) * out_unit);
       });
 }
 
@@ -260,62 +178,79 @@ int band_to_host(double* host, const double* d_src, int64_t planes, int64_t H, i
   return 0;
 }
 
-// the whole frame onto the device as the kernels' element type (narrow formats: raw bytes up, widened there);
-// `bytes` = size in the kernels' type, `extra` = room behind it for the caller
-int frame_up(zk_plan* p, zk_host_ring* r, const void* image_host, int dtype, long long n_px, size_t bytes, size_t extra) {
-  int rc = zk_ensure(&r->d_frame, &r->frame_cap, bytes + extra);
+// the whole frame onto the device as the kernels' element type (narrow formats: raw bytes up, widened there), on the
+// plan's stream; `extra` = room behind it for the caller
+int frame_up(zk_plan* p, zk_host_ring* h, const void* image_host, int dtype, int64_t H, int64_t W, size_t extra) {
+  const long long n_px = (long long)H * W;
+  const size_t bytes = (size_t)n_px * zk_elem_size(kernel_dtype(dtype));
+  int rc = zk_ensure(&h->d_frame, &h->frame_cap, bytes + extra);
   if (rc) return rc;
   if (!is_narrow(dtype)) {
-    ZK_HIP(hipMemcpyAsync(r->d_frame, image_host, bytes, hipMemcpyHostToDevice, p->stream));
+    ZK_HIP(hipMemcpyAsync(h->d_frame, image_host, bytes, hipMemcpyHostToDevice, p->stream));
     return 0;
   }
-  const size_t raw = (size_t)n_px * elem_size(dtype);
-  if ((rc = zk_ensure(&r->d_raw[0], &r->raw_cap[0], raw))) return rc;
-  ZK_HIP(hipMemcpyAsync(r->d_raw[0], image_host, raw, hipMemcpyHostToDevice, p->stream));
-  return widen(dtype, r->d_raw[0], (float*)r->d_frame, n_px, p->stream);
+  const size_t raw = (size_t)n_px * zk_elem_size(dtype);
+  if ((rc = zk_ensure(&h->d_raw[0], &h->raw_cap[0], raw))) return rc;
+  ZK_HIP(hipMemcpyAsync(h->d_raw[0], image_host, raw, hipMemcpyHostToDevice, p->stream));
+  return widen(dtype, h->d_raw[0], (float*)h->d_frame, n_px, p->stream);
 }
 
-int64_t band_rows(const zk_plan* p, size_t row_bytes, int64_t H) {
-  int64_t band = (int64_t)(chunk_bytes(p) / row_bytes) & ~(int64_t)7;  // whole blocks of the dense kernels
-  if (band < 8) band = 8;
-  return band > H ? H : band;
+// the frame, and behind it (256-byte aligned) the point list of a key-point call: *d_pts
+int frame_points_up(zk_plan* p, zk_host_ring* h, const void* image_host, int dtype, int64_t H, int64_t W,
+                    const int32_t* points_host, int64_t n_points, int32_t** d_pts) {
+  const size_t img_bytes = (size_t)H * W * zk_elem_size(kernel_dtype(dtype));
+  const size_t img_pad = (img_bytes + 255) & ~(size_t)255;
+  const size_t pts_bytes = (size_t)n_points * 2 * sizeof(int32_t);
+  const int rc = frame_up(p, h, image_host, dtype, H, W, img_pad - img_bytes + pts_bytes);
+  if (rc) return rc;
+  *d_pts = (int32_t*)((char*)h->d_frame + img_pad);
+  const hipError_t e = hipMemcpyAsync(*d_pts, points_host, pts_bytes, hipMemcpyHostToDevice, p->stream);
+  return e == hipSuccess ? 0 : zk_hip_fail(e, "hipMemcpyAsync(points)");
 }
+
+// The three outputs of the symmetry maps, each optional, of n units (rows of a moment matrix, or the pixels of a row
+// band) a chunk: packed in the slot's d_out as [rot | abs | mirror], planes of n doubles.
+struct maps_out {
+  double *rot, *ab, *mir;     // host destinations (may be null)
+  int64_t pl_rot, pl_abs, pl_mir;
+  maps_out(const zk_plan* p, double* rot_host, double* abs_host, double* mirror_host, int n_folds)
+      : rot(rot_host), ab(abs_host), mir(mirror_host), pl_rot(rot_host ? n_folds : 0),
+        pl_abs(abs_host ? zk_complex_count(zk_full_set_nmax(p)) : 0), pl_mir(mirror_host ? 1 : 0) {}
+  size_t unit_bytes() const { return (size_t)(pl_rot + pl_abs + pl_mir + 1) * sizeof(double); }
+  double* d_rot(void* d, int64_t n) const { return rot ? (double*)d : nullptr; }
+  double* d_abs(void* d, int64_t n) const { return ab ? (double*)d + n * pl_rot : nullptr; }
+  double* d_mir(void* d, int64_t n) const { return mir ? (double*)d + n * (pl_rot + pl_abs) : nullptr; }
+  // D2H of one chunk of the three row-major outputs
+  int rows_to_host(void* d, int64_t first, int64_t n, hipStream_t s) const {
+    if (rot) ZK_HIP(hipMemcpyAsync(rot + first * pl_rot, d_rot(d, n), (size_t)n * pl_rot * 8, hipMemcpyDeviceToHost, s));
+    if (ab) ZK_HIP(hipMemcpyAsync(ab + first * pl_abs, d_abs(d, n), (size_t)n * pl_abs * 8, hipMemcpyDeviceToHost, s));
+    if (mir) ZK_HIP(hipMemcpyAsync(mir + first, d_mir(d, n), (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    return 0;
+  }
+};
 
 }  // namespace
 
 extern "C" int zk_transform_frame(zk_plan* p, const void* image_host, int dtype, int64_t H, int64_t W,
                                   double* out_host) {
-  if (!p) return zk_fail(ZK_E_BADARG, "null plan");
-  int rc = check_dtype(dtype);
+  int rc = check_job(p, dtype, H, W, nullptr, 0, image_host && out_host);
   if (rc) return rc;
-  if (H <= 0 || W <= 0) return zk_fail(ZK_E_BADARG, "bad frame shape");
-  if (!image_host || !out_host) return zk_fail(ZK_E_BADARG, "null host pointer");
   ZK_ON_PLAN_DEVICE(p);
-  zk_host_ring* r;
-  if ((rc = ring_get(p, &r))) return rc;
-  const int kdt = kernel_dtype(dtype);
-  if ((rc = frame_up(p, r, image_host, dtype, (long long)H * W, (size_t)H * W * elem_size(kdt), 0))) return ring_drain(p, r, rc);
+  zk_host_ring* h;
+  if ((rc = ring_get(p, &h))) return rc;
+  zk_ring* r = &h->ring;
+  if ((rc = frame_up(p, h, image_host, dtype, H, W, 0))) return zk_ring_drain(r, p->stream, rc);
   const size_t row_bytes = (size_t)p->n_poly * W * sizeof(double);
-  const int64_t band = band_rows(p, row_bytes, H);
-  const int n_chunks = (int)((H + band - 1) / band);
-  auto rows = [&](int c) { return H - c * band < band ? H - c * band : band; };
-  return run_chunks(
-      p, r, n_chunks,
-      [&](int c, int slot) -> int {
-        int e = slot_acquire(r, slot);
-        if (!e) e = zk_ensure(&r->d_out[slot], &r->out_cap[slot], (size_t)band * row_bytes);
-        if (!e) e = zk_transform_frame_dev(p, r->d_frame, kdt, H, W, c * band, rows(c), (double*)r->d_out[slot], p->stream);
-        if (e) return e;
-        ZK_HIP(hipEventRecord(r->ev_k[slot], p->stream));
-        return 0;
+  const zk_chunks band = zk_chunk_plan(chunk_bytes(p), row_bytes, 8, H);  // whole blocks of the dense kernels
+  return zk_ring_run(
+      r, p->stream, band.n_chunks,
+      [&](int64_t c, int slot) -> int {
+        const int e = zk_ring_slot(r, slot, 0, (size_t)band.chunk * row_bytes);
+        return e ? e : zk_transform_frame_dev(p, h->d_frame, kernel_dtype(dtype), H, W, band.first(c), band.count(c),
+                                              (double*)r->d_out[slot], p->stream);
       },
-      [&](int c, int slot) -> int {
-        ZK_HIP(hipStreamWaitEvent(r->s_out, r->ev_k[slot], 0));
-        const int e = band_to_host(out_host, (const double*)r->d_out[slot], p->n_poly, H, W, c * band, rows(c), r->s_out);
-        if (e) return e;
-        ZK_HIP(hipEventRecord(r->ev_out[slot], r->s_out));
-        r->out_busy[slot] = true;
-        return 0;
+      [&](int64_t c, int slot) -> int {
+        return band_to_host(out_host, (const double*)r->d_out[slot], p->n_poly, H, W, band.first(c), band.count(c), r->s_out);
       });
 }
 
@@ -326,49 +261,34 @@ extern "C" int zk_frame_maps(zk_plan* p, const void* image_host, int dtype, int6
                              const int32_t* folds, int n_folds, const int32_t* m_unselect, int n_unselect,
                              int p_norm, const double* theta, int n_theta, double* rot_host, double* abs_host,
                              double* mirror_host) {
-  if (!p) return zk_fail(ZK_E_BADARG, "null plan");
-  int rc = check_dtype(dtype);
+  int rc = check_job(p, dtype, H, W, nullptr, 0, image_host);
   if (rc) return rc;
-  if (H <= 0 || W <= 0) return zk_fail(ZK_E_BADARG, "bad frame shape");
-  if (!image_host) return zk_fail(ZK_E_BADARG, "null host pointer");
   ZK_ON_PLAN_DEVICE(p);
-  zk_host_ring* r;
-  if ((rc = ring_get(p, &r))) return rc;
-  const int kdt = kernel_dtype(dtype);
-  if ((rc = frame_up(p, r, image_host, dtype, (long long)H * W, (size_t)H * W * elem_size(kdt), 0))) return ring_drain(p, r, rc);
-  const int64_t nc = zk_complex_count(zk_full_set_nmax(p));
-  const int64_t pl_rot = rot_host ? n_folds : 0, pl_abs = abs_host ? nc : 0, pl_mir = mirror_host ? 1 : 0;
-  const size_t row_bytes = (size_t)(pl_rot + pl_abs + pl_mir + 1) * W * sizeof(double);
-  const int64_t band = band_rows(p, row_bytes, H);
-  const int n_chunks = (int)((H + band - 1) / band);
-  auto rows = [&](int c) { return H - c * band < band ? H - c * band : band; };
-  auto d_rot = [&](int c, int slot) { return rot_host ? (double*)r->d_out[slot] : nullptr; };
-  auto d_abs = [&](int c, int slot) { return abs_host ? (double*)r->d_out[slot] + (size_t)pl_rot * rows(c) * W : nullptr; };
-  auto d_mir = [&](int c, int slot) {
-    return mirror_host ? (double*)r->d_out[slot] + (size_t)(pl_rot + pl_abs) * rows(c) * W : nullptr;
-  };
-  return run_chunks(
-      p, r, n_chunks,
-      [&](int c, int slot) -> int {
-        int e = slot_acquire(r, slot);
-        if (!e) e = zk_ensure(&r->d_out[slot], &r->out_cap[slot], (size_t)band * row_bytes);
-        if (!e)
-          e = zk_frame_maps_dev(p, r->d_frame, kdt, H, W, c * band, rows(c), folds, n_folds, m_unselect, n_unselect, p_norm,
-                                theta, n_theta, d_rot(c, slot), d_abs(c, slot), d_mir(c, slot), p->stream);
-        if (e) return e;
-        ZK_HIP(hipEventRecord(r->ev_k[slot], p->stream));
-        return 0;
+  zk_host_ring* h;
+  if ((rc = ring_get(p, &h))) return rc;
+  zk_ring* r = &h->ring;
+  if ((rc = frame_up(p, h, image_host, dtype, H, W, 0))) return zk_ring_drain(r, p->stream, rc);
+  const maps_out o(p, rot_host, abs_host, mirror_host, n_folds);
+  const size_t row_bytes = o.unit_bytes() * W;
+  const zk_chunks band = zk_chunk_plan(chunk_bytes(p), row_bytes, 8, H);
+  return zk_ring_run(
+      r, p->stream, band.n_chunks,
+      [&](int64_t c, int slot) -> int {
+        const int e = zk_ring_slot(r, slot, 0, (size_t)band.chunk * row_bytes);
+        void* d = r->d_out[slot];
+        const int64_t n = band.count(c) * W;
+        return e ? e : zk_frame_maps_dev(p, h->d_frame, kernel_dtype(dtype), H, W, band.first(c), band.count(c), folds, n_folds,
+                                         m_unselect, n_unselect, p_norm, theta, n_theta, o.d_rot(d, n), o.d_abs(d, n), o.d_mir(d, n),
+                                         p->stream);
       },
-      [&](int c, int slot) -> int {
-        ZK_HIP(hipStreamWaitEvent(r->s_out, r->ev_k[slot], 0));
+      [&](int64_t c, int slot) -> int {
+        void* d = r->d_out[slot];
+        const int64_t b0 = band.first(c), nb = band.count(c);
         int e = 0;
-        if (rot_host) e = band_to_host(rot_host, d_rot(c, slot), pl_rot, H, W, c * band, rows(c), r->s_out);
-        if (abs_host && !e) e = band_to_host(abs_host, d_abs(c, slot), pl_abs, H, W, c * band, rows(c), r->s_out);
-        if (mirror_host && !e) e = band_to_host(mirror_host, d_mir(c, slot), 1, H, W, c * band, rows(c), r->s_out);
-        if (e) return e;
-        ZK_HIP(hipEventRecord(r->ev_out[slot], r->s_out));
-        r->out_busy[slot] = true;
-        return 0;
+        if (o.rot) e = band_to_host(o.rot, o.d_rot(d, nb * W), o.pl_rot, H, W, b0, nb, r->s_out);
+        if (o.ab && !e) e = band_to_host(o.ab, o.d_abs(d, nb * W), o.pl_abs, H, W, b0, nb, r->s_out);
+        if (o.mir && !e) e = band_to_host(o.mir, o.d_mir(d, nb * W), 1, H, W, b0, nb, r->s_out);
+        return e;
       });
 }
 
@@ -377,51 +297,25 @@ extern "C" int zk_frame_maps(zk_plan* p, const void* image_host, int dtype, int6
 // ------------------------------------------------------------------------------------------------------
 extern "C" int zk_transform_points(zk_plan* p, const void* image_host, int dtype, int64_t H, int64_t W,
                                    const int32_t* points_host, int64_t n_points, double* out_host) {
-  if (!p) return zk_fail(ZK_E_BADARG, "null plan");
-  int rc = check_dtype(dtype);
-  if (rc) return rc;
-  if (H <= 0 || W <= 0) return zk_fail(ZK_E_BADARG, "bad frame shape");
-  if (n_points < 0) return zk_fail(ZK_E_BADARG, "negative point count");
-  if (n_points == 0) return 0;
-  if (!image_host || !points_host || !out_host) return zk_fail(ZK_E_BADARG, "null host pointer");
+  int rc = check_job(p, dtype, H, W, "point", n_points, image_host && points_host && out_host);
+  if (rc) return rc < 0 ? rc : 0;
   ZK_ON_PLAN_DEVICE(p);
-  zk_host_ring* r;
-  if ((rc = ring_get(p, &r))) return rc;
-  const int kdt = kernel_dtype(dtype);
-  const size_t img_bytes = (size_t)H * W * elem_size(kdt);
-  const size_t img_pad = (img_bytes + 255) & ~(size_t)255;
-  const size_t pts_bytes = (size_t)n_points * 2 * sizeof(int32_t);
-  if ((rc = frame_up(p, r, image_host, dtype, (long long)H * W, img_bytes, img_pad - img_bytes + pts_bytes))) return ring_drain(p, r, rc);
-  int32_t* d_pts = (int32_t*)((char*)r->d_frame + img_pad);
-  {
-    const hipError_t e = hipMemcpyAsync(d_pts, points_host, pts_bytes, hipMemcpyHostToDevice, p->stream);
-    if (e != hipSuccess) return ring_drain(p, r, zk_hip_fail(e, "hipMemcpyAsync(points)"));
-  }
+  zk_host_ring* h;
+  if ((rc = ring_get(p, &h))) return rc;
+  zk_ring* r = &h->ring;
+  int32_t* d_pts;
+  if ((rc = frame_points_up(p, h, image_host, dtype, H, W, points_host, n_points, &d_pts))) return zk_ring_drain(r, p->stream, rc);
   const size_t out_unit = (size_t)p->n_poly * sizeof(double);
-  int64_t chunk = (int64_t)(chunk_bytes(p) / out_unit) & ~(int64_t)255;
-  if (chunk < 256) chunk = 256;
-  if (chunk > n_points) chunk = n_points;
-  const int n_chunks = (int)((n_points + chunk - 1) / chunk);
-  auto count = [&](int c) { return n_points - c * chunk < chunk ? n_points - c * chunk : chunk; };
-  return run_chunks(
-      p, r, n_chunks,
-      [&](int c, int slot) -> int {
-        int e = slot_acquire(r, slot);
-        if (!e) e = zk_ensure(&r->d_out[slot], &r->out_cap[slot], (size_t)chunk * out_unit);
-        if (!e)
-          e = zk_transform_points_dev(p, r->d_frame, kdt, H, W, d_pts + 2 * c * chunk, count(c), (double*)r->d_out[slot],
-                                      p->stream);
-        if (e) return e;
-        ZK_HIP(hipEventRecord(r->ev_k[slot], p->stream));
-        return 0;
+  const zk_chunks ch = zk_chunk_plan(chunk_bytes(p), out_unit, 256, n_points);
+  return zk_ring_run(
+      r, p->stream, ch.n_chunks,
+      [&](int64_t c, int slot) -> int {
+        const int e = zk_ring_slot(r, slot, 0, (size_t)ch.chunk * out_unit);
+        return e ? e : zk_transform_points_dev(p, h->d_frame, kernel_dtype(dtype), H, W, d_pts + 2 * ch.first(c), ch.count(c),
+                                               (double*)r->d_out[slot], p->stream);
       },
-      [&](int c, int slot) -> int {
-        ZK_HIP(hipStreamWaitEvent(r->s_out, r->ev_k[slot], 0));
-        ZK_HIP(hipMemcpyAsync((char*)out_host + (size_t)c * chunk * out_unit, r->d_out[slot], (size_t)count(c) * out_unit,
-                              hipMemcpyDeviceToHost, r->s_out));
-        ZK_HIP(hipEventRecord(r->ev_out[slot], r->s_out));
-        r->out_busy[slot] = true;
-        return 0;
+      [&](int64_t c, int slot) -> int {
+        return zk_ring_down(r, slot, (char*)out_host + (size_t)ch.first(c) * out_unit, (size_t)ch.count(c) * out_unit);
       });
 }
 
@@ -429,128 +323,56 @@ extern "C" int zk_transform_points(zk_plan* p, const void* image_host, int dtype
 // symmetry maps of a batch of moment vectors (rank-2 tail), and of the windows at key points (moments + tail fused:
 // the (N, n_poly) matrix stays on the device)
 // ------------------------------------------------------------------------------------------------------
-namespace {
-
-struct rows_out {
-  double *rot, *ab, *mir;     // host destinations (may be null)
-  int64_t pl_rot, pl_abs, pl_mir;
-};
-
-// D2H of one chunk of the three row-major outputs, packed on the device as [rot | abs | mirror]
-int rows_to_host(const rows_out& o, const double* d, int64_t first, int64_t n, hipStream_t s) {
-  if (o.rot) ZK_HIP(hipMemcpyAsync(o.rot + first * o.pl_rot, d, (size_t)n * o.pl_rot * 8, hipMemcpyDeviceToHost, s));
-  if (o.ab) ZK_HIP(hipMemcpyAsync(o.ab + first * o.pl_abs, d + n * o.pl_rot, (size_t)n * o.pl_abs * 8, hipMemcpyDeviceToHost, s));
-  if (o.mir) ZK_HIP(hipMemcpyAsync(o.mir + first, d + n * (o.pl_rot + o.pl_abs), (size_t)n * 8, hipMemcpyDeviceToHost, s));
-  return 0;
-}
-
-}  // namespace
-
 extern "C" int zk_moment_maps(zk_plan* p, const double* moments_host, int64_t n_rows, const int32_t* folds, int n_folds,
                               const int32_t* m_unselect, int n_unselect, int p_norm, const double* theta, int n_theta,
                               double* rot_host, double* abs_host, double* mirror_host) {
-  if (!p) return zk_fail(ZK_E_BADARG, "null plan");
-  if (n_rows < 0) return zk_fail(ZK_E_BADARG, "negative row count");
-  if (n_rows == 0) return 0;
-  if (!moments_host) return zk_fail(ZK_E_BADARG, "null host pointer");
+  int rc = check_job(p, ZK_F64, 1, 1, "row", n_rows, moments_host);
+  if (rc) return rc < 0 ? rc : 0;
   ZK_ON_PLAN_DEVICE(p);
-  zk_host_ring* r;
-  int rc;
-  if ((rc = ring_get(p, &r))) return rc;
-  const int64_t nc = zk_complex_count(zk_full_set_nmax(p));
-  const rows_out o = {rot_host, abs_host, mirror_host, rot_host ? n_folds : 0, abs_host ? nc : 0, mirror_host ? 1 : 0};
-  const size_t in_unit = (size_t)p->n_poly * 8, out_unit = (size_t)(o.pl_rot + o.pl_abs + o.pl_mir + 1) * 8;
-  int64_t chunk = (int64_t)(chunk_bytes(p) / (in_unit + out_unit)) & ~(int64_t)255;
-  if (chunk < 256) chunk = 256;
-  if (chunk > n_rows) chunk = n_rows;
-  const int n_chunks = (int)((n_rows + chunk - 1) / chunk);
-  auto count = [&](int c) { return n_rows - c * chunk < chunk ? n_rows - c * chunk : chunk; };
-  return run_chunks(
-      p, r, n_chunks,
-      [&](int c, int slot) -> int {
-        int e = slot_acquire(r, slot);
-        if (!e) e = zk_ensure(&r->d_in[slot], &r->in_cap[slot], (size_t)chunk * in_unit);
-        if (!e) e = zk_ensure(&r->d_out[slot], &r->out_cap[slot], (size_t)chunk * out_unit);
-        if (e) return e;
-        if (c >= ZK_RING_SLOTS) ZK_HIP(hipStreamWaitEvent(r->s_in, r->ev_k[slot], 0));
-        ZK_HIP(hipMemcpyAsync(r->d_in[slot], moments_host + (size_t)c * chunk * p->n_poly, (size_t)count(c) * in_unit,
-                              hipMemcpyHostToDevice, r->s_in));
-        ZK_HIP(hipEventRecord(r->ev_in[slot], r->s_in));
-        ZK_HIP(hipStreamWaitEvent(p->stream, r->ev_in[slot], 0));
-        double* d = (double*)r->d_out[slot];
-        const int64_t n = count(c);
-        e = zk_moment_maps_dev(p, (const double*)r->d_in[slot], n, folds, n_folds, m_unselect, n_unselect, p_norm, theta, n_theta,
-                               o.rot ? d : nullptr, o.ab ? d + n * o.pl_rot : nullptr,
-                               o.mir ? d + n * (o.pl_rot + o.pl_abs) : nullptr, p->stream);
-        if (e) return e;
-        ZK_HIP(hipEventRecord(r->ev_k[slot], p->stream));
-        return 0;
+  zk_host_ring* h;
+  if ((rc = ring_get(p, &h))) return rc;
+  zk_ring* r = &h->ring;
+  const maps_out o(p, rot_host, abs_host, mirror_host, n_folds);
+  const size_t in_unit = (size_t)p->n_poly * 8, out_unit = o.unit_bytes();
+  const zk_chunks ch = zk_chunk_plan(chunk_bytes(p), in_unit + out_unit, 256, n_rows);
+  return zk_ring_run(
+      r, p->stream, ch.n_chunks,
+      [&](int64_t c, int slot) -> int {
+        const int64_t n = ch.count(c);
+        int e = zk_ring_slot(r, slot, (size_t)ch.chunk * in_unit, (size_t)ch.chunk * out_unit);
+        if (!e) e = zk_ring_up(r, p->stream, c, slot, r->d_in[slot], moments_host + (size_t)ch.first(c) * p->n_poly, (size_t)n * in_unit);
+        void* d = r->d_out[slot];
+        return e ? e : zk_moment_maps_dev(p, (const double*)r->d_in[slot], n, folds, n_folds, m_unselect, n_unselect, p_norm, theta,
+                                          n_theta, o.d_rot(d, n), o.d_abs(d, n), o.d_mir(d, n), p->stream);
       },
-      [&](int c, int slot) -> int {
-        ZK_HIP(hipStreamWaitEvent(r->s_out, r->ev_k[slot], 0));
-        const int e = rows_to_host(o, (const double*)r->d_out[slot], (int64_t)c * chunk, count(c), r->s_out);
-        if (e) return e;
-        ZK_HIP(hipEventRecord(r->ev_out[slot], r->s_out));
-        r->out_busy[slot] = true;
-        return 0;
-      });
+      [&](int64_t c, int slot) -> int { return o.rows_to_host(r->d_out[slot], ch.first(c), ch.count(c), r->s_out); });
 }
 
 extern "C" int zk_points_maps(zk_plan* p, const void* image_host, int dtype, int64_t H, int64_t W, const int32_t* points_host,
                               int64_t n_points, const int32_t* folds, int n_folds, const int32_t* m_unselect, int n_unselect,
                               int p_norm, const double* theta, int n_theta, double* rot_host, double* abs_host,
                               double* mirror_host) {
-  if (!p) return zk_fail(ZK_E_BADARG, "null plan");
-  int rc = check_dtype(dtype);
-  if (rc) return rc;
-  if (H <= 0 || W <= 0) return zk_fail(ZK_E_BADARG, "bad frame shape");
-  if (n_points < 0) return zk_fail(ZK_E_BADARG, "negative point count");
-  if (n_points == 0) return 0;
-  if (!image_host || !points_host) return zk_fail(ZK_E_BADARG, "null host pointer");
+  int rc = check_job(p, dtype, H, W, "point", n_points, image_host && points_host);
+  if (rc) return rc < 0 ? rc : 0;
   ZK_ON_PLAN_DEVICE(p);
-  zk_host_ring* r;
-  if ((rc = ring_get(p, &r))) return rc;
-  const int kdt = kernel_dtype(dtype);
-  const size_t img_bytes = (size_t)H * W * elem_size(kdt);
-  const size_t img_pad = (img_bytes + 255) & ~(size_t)255;
-  const size_t pts_bytes = (size_t)n_points * 2 * sizeof(int32_t);
-  if ((rc = frame_up(p, r, image_host, dtype, (long long)H * W, img_bytes, img_pad - img_bytes + pts_bytes))) return ring_drain(p, r, rc);
-  int32_t* d_pts = (int32_t*)((char*)r->d_frame + img_pad);
-  {
-    const hipError_t e = hipMemcpyAsync(d_pts, points_host, pts_bytes, hipMemcpyHostToDevice, p->stream);
-    if (e != hipSuccess) return ring_drain(p, r, zk_hip_fail(e, "hipMemcpyAsync(points)"));
-  }
-  const int64_t nc = zk_complex_count(zk_full_set_nmax(p));
-  const rows_out o = {rot_host, abs_host, mirror_host, rot_host ? n_folds : 0, abs_host ? nc : 0, mirror_host ? 1 : 0};
-  const size_t mom_unit = (size_t)p->n_poly * 8, out_unit = (size_t)(o.pl_rot + o.pl_abs + o.pl_mir + 1) * 8;
-  int64_t chunk = (int64_t)(chunk_bytes(p) / (mom_unit + out_unit)) & ~(int64_t)255;
-  if (chunk < 256) chunk = 256;
-  if (chunk > n_points) chunk = n_points;
-  const int n_chunks = (int)((n_points + chunk - 1) / chunk);
-  auto count = [&](int c) { return n_points - c * chunk < chunk ? n_points - c * chunk : chunk; };
-  return run_chunks(
-      p, r, n_chunks,
-      [&](int c, int slot) -> int {
-        int e = slot_acquire(r, slot);
-        if (!e) e = zk_ensure(&r->d_in[slot], &r->in_cap[slot], (size_t)chunk * mom_unit);  // the chunk's moments, device only
-        if (!e) e = zk_ensure(&r->d_out[slot], &r->out_cap[slot], (size_t)chunk * out_unit);
-        if (e) return e;
-        const int64_t n = count(c);
+  zk_host_ring* h;
+  if ((rc = ring_get(p, &h))) return rc;
+  zk_ring* r = &h->ring;
+  int32_t* d_pts;
+  if ((rc = frame_points_up(p, h, image_host, dtype, H, W, points_host, n_points, &d_pts))) return zk_ring_drain(r, p->stream, rc);
+  const maps_out o(p, rot_host, abs_host, mirror_host, n_folds);
+  const size_t mom_unit = (size_t)p->n_poly * 8, out_unit = o.unit_bytes();
+  const zk_chunks ch = zk_chunk_plan(chunk_bytes(p), mom_unit + out_unit, 256, n_points);
+  return zk_ring_run(
+      r, p->stream, ch.n_chunks,
+      [&](int64_t c, int slot) -> int {
+        const int64_t n = ch.count(c);
+        int e = zk_ring_slot(r, slot, (size_t)ch.chunk * mom_unit, (size_t)ch.chunk * out_unit);  // d_in: the chunk's moments, device only
         double* mom = (double*)r->d_in[slot];
-        double* d = (double*)r->d_out[slot];
-        if ((e = zk_transform_points_dev(p, r->d_frame, kdt, H, W, d_pts + 2 * c * chunk, n, mom, p->stream))) return e;
-        e = zk_moment_maps_dev(p, mom, n, folds, n_folds, m_unselect, n_unselect, p_norm, theta, n_theta, o.rot ? d : nullptr,
-                               o.ab ? d + n * o.pl_rot : nullptr, o.mir ? d + n * (o.pl_rot + o.pl_abs) : nullptr, p->stream);
-        if (e) return e;
-        ZK_HIP(hipEventRecord(r->ev_k[slot], p->stream));
-        return 0;
+        void* d = r->d_out[slot];
+        if (!e) e = zk_transform_points_dev(p, h->d_frame, kernel_dtype(dtype), H, W, d_pts + 2 * ch.first(c), n, mom, p->stream);
+        return e ? e : zk_moment_maps_dev(p, mom, n, folds, n_folds, m_unselect, n_unselect, p_norm, theta, n_theta, o.d_rot(d, n),
+                                          o.d_abs(d, n), o.d_mir(d, n), p->stream);
       },
-      [&](int c, int slot) -> int {
-        ZK_HIP(hipStreamWaitEvent(r->s_out, r->ev_k[slot], 0));
-        const int e = rows_to_host(o, (const double*)r->d_out[slot], (int64_t)c * chunk, count(c), r->s_out);
-        if (e) return e;
-        ZK_HIP(hipEventRecord(r->ev_out[slot], r->s_out));
-        r->out_busy[slot] = true;
-        return 0;
-      });
+      [&](int64_t c, int slot) -> int { return o.rows_to_host(r->d_out[slot], ch.first(c), ch.count(c), r->s_out); });
 }

@@ -134,6 +134,11 @@ static inline int zk_for_row_bands(int64_t row0, int64_t n_rows, int64_t W, int 
   return 0;
 }
 
+// bytes per element of a ZK_* dtype code
+static inline size_t zk_elem_size(int dtype) {
+  return dtype == ZK_F64 ? 8 : dtype == ZK_F32 ? 4 : dtype == ZK_U8 ? 1 : 2;
+}
+
 // grow-only device buffer
 static inline int zk_ensure(void** buf, size_t* have, size_t need) {
   if (*have >= need) return 0;

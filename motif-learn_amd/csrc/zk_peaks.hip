@@ -417,8 +417,6 @@ int check_args(int dtype, int64_t H, int64_t W, const void* img, double r, int64
   return 0;
 }
 
-size_t element_size(int dtype) { return dtype == ZK_F64 ? 8 : dtype == ZK_F32 ? 4 : dtype == ZK_U8 ? 1 : 2; }
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------
@@ -437,7 +435,7 @@ extern "C" int zk_local_max(int device, const void* image_host, int dtype, int64
   int rc = check_args(dtype, height, width, image_host, min_distance, capacity, points_host, n_found);
   if (rc) return rc;
   ZK_ON_DEVICE(device);
-  const size_t bytes = (size_t)height * width * element_size(dtype);
+  const size_t bytes = (size_t)height * width * zk_elem_size(dtype);
   dev_buf d_img, d_pts;
   if ((rc = d_img.alloc(bytes)) || (rc = d_pts.alloc((size_t)std::max<int64_t>(capacity, 1) * 8))) return rc;
   ZK_HIP(hipMemcpy(d_img.p, image_host, bytes, hipMemcpyHostToDevice));

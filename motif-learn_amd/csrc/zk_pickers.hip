@@ -406,7 +406,7 @@ extern "C" int zk_autocorr_mean(int device, const void* image_host, int dtype, i
   if ((rc = fft_load())) return rc;
   ZK_ON_DEVICE(device);
   const int ws = (int)window, N = 2 * ws;  // any N >= 2 ws - 1 turns the circular correlation into the linear one
-  const size_t es = dtype == ZK_F32 ? 4 : 8;
+  const size_t es = zk_elem_size(dtype);
   dev_buf d_img, d_org, d_stats, d_z, d_acc;
   if ((rc = d_img.alloc((size_t)H * W * es)) || (rc = d_org.alloc((size_t)n_windows * 8)) ||
       (rc = d_stats.alloc((size_t)n_windows * 16)) || (rc = d_acc.alloc((size_t)ws * ws * 8)))
@@ -501,7 +501,7 @@ extern "C" int zk_power_spectra(int device, const void* image_host, int dtype, i
   if ((rc = fft_load())) return rc;
   ZK_ON_DEVICE(device);
   const int n = (int)size;
-  const size_t es = dtype == ZK_F32 ? 4 : 8;
+  const size_t es = zk_elem_size(dtype);
   const long long total = (long long)n_windows * n * n;
   dev_buf d_img, d_org, d_win, d_z, d_out;
   if ((rc = d_img.alloc((size_t)H * W * es)) || (rc = d_org.alloc((size_t)n_windows * 8)) || (rc = d_win.alloc((size_t)n * 8)) ||
@@ -536,7 +536,7 @@ extern "C" int zk_denoise_fft(int device, const void* image_host, int dtype, int
   if ((rc = fft_load())) return rc;
   ZK_ON_DEVICE(device);
   const long long n = (long long)H * W;
-  const size_t es = dtype == ZK_F32 ? 4 : 8;
+  const size_t es = zk_elem_size(dtype);
   dev_buf d_img, d_spec, d_pow, d_hist, d_out;
   if ((rc = d_img.alloc((size_t)n * es)) || (rc = d_spec.alloc((size_t)n * 16)) || (rc = d_pow.alloc((size_t)n * 16)) ||
       (rc = d_hist.alloc(65537 * 4)) || (rc = d_out.alloc((size_t)n * 8)))
@@ -581,7 +581,7 @@ extern "C" int zk_wavelet_sigma(int device, const void* image_host, int dtype, i
   ZK_ON_DEVICE(device);
   const int oh = (int)((H + 3) / 2), ow = (int)((W + 3) / 2);
   const long long n = (long long)oh * ow;
-  const size_t es = dtype == ZK_F32 ? 4 : 8;
+  const size_t es = zk_elem_size(dtype);
   dev_buf d_img, d_d, d_hist;
   if ((rc = d_img.alloc((size_t)H * W * es)) || (rc = d_d.alloc((size_t)n * 8)) || (rc = d_hist.alloc(65536 * 4 + 8))) return rc;
   ZK_HIP(hipMemcpy(d_img.p, image_host, (size_t)H * W * es, hipMemcpyHostToDevice));

@@ -18,13 +18,12 @@
 // No atomics, and a row's sum does not depend on where the row lies in the batch: two runs, and two chunkings, agree bit for bit.
 #include <new>
 
-#include "zk_internal.h"
+#include "zk_ring.h"
 
 #define ZK_SYNTH_ROWS 64
 #define ZK_SYNTH_COLS 256
 #define ZK_SYNTH_KC 96                    // coefficients of a row held in LDS at a time
 #define ZK_SYNTH_PITCH (ZK_SYNTH_KC + 2)  // doubles; pitch = 2 mod 32: the 32 lanes (i, k < 2) of a half-wave read 32 different bank pairs
-#define ZK_SYNTH_SLOTS 3
 #define ZK_SYNTH_KEEP_BYTES ((size_t)32 << 20)  // device slots an object keeps between host-variant calls
 
 struct zk_synth {
@@ -34,14 +33,8 @@ struct zk_synth {
   int64_t n_pixels = 0;
   double* d_table = nullptr;  // (p_pad, n_pixels)
   size_t host_chunk = 0;      // bytes of coefficients + output per chunk of the host variant; 0 = default
-  // host variant: H2D on s_in -> kernel on stream -> D2H on s_out through ZK_SYNTH_SLOTS device slots
-  hipStream_t stream = nullptr, s_in = nullptr, s_out = nullptr;
-  void* d_in[ZK_SYNTH_SLOTS] = {};
-  size_t in_cap[ZK_SYNTH_SLOTS] = {};
-  void* d_out[ZK_SYNTH_SLOTS] = {};
-  size_t out_cap[ZK_SYNTH_SLOTS] = {};
-  hipEvent_t ev_in[ZK_SYNTH_SLOTS] = {}, ev_k[ZK_SYNTH_SLOTS] = {}, ev_out[ZK_SYNTH_SLOTS] = {};
-  bool out_busy[ZK_SYNTH_SLOTS] = {};
+  hipStream_t stream = nullptr;  // kernels of the host variant
+  zk_ring ring;                  // its staging (zk_ring.h): coefficients up, patches down
 };
 
 namespace {
@@ -150,26 +143,9 @@ int check_apply(const zk_synth* s, const void* coeffs, int64_t n_rows, int out_d
   return 0;
 }
 
-// the device slots of the host variant (re-created on demand)
-void release_slots(zk_synth* s) {
-  for (int k = 0; k < ZK_SYNTH_SLOTS; ++k) {
-    if (s->d_in[k]) (void)hipFree(s->d_in[k]);
-    if (s->d_out[k]) (void)hipFree(s->d_out[k]);
-    s->d_in[k] = s->d_out[k] = nullptr;
-    s->in_cap[k] = s->out_cap[k] = 0;
-  }
-}
-
 void release(zk_synth* s) {
-  release_slots(s);
-  for (int k = 0; k < ZK_SYNTH_SLOTS; ++k) {
-    if (s->ev_in[k]) (void)hipEventDestroy(s->ev_in[k]);
-    if (s->ev_k[k]) (void)hipEventDestroy(s->ev_k[k]);
-    if (s->ev_out[k]) (void)hipEventDestroy(s->ev_out[k]);
-  }
+  zk_ring_destroy(&s->ring);
   if (s->d_table) (void)hipFree(s->d_table);
-  if (s->s_in) (void)hipStreamDestroy(s->s_in);
-  if (s->s_out) (void)hipStreamDestroy(s->s_out);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -180,42 +156,9 @@ int build(zk_synth* s, const double* table_host) {
   ZK_HIP(hipMemcpy(s->d_table, table_host, live, hipMemcpyHostToDevice));
   if (all > live) ZK_HIP(hipMemset((char*)s->d_table + live, 0, all - live));
   ZK_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  ZK_HIP(hipStreamCreateWithFlags(&s->s_in, hipStreamNonBlocking));
-  ZK_HIP(hipStreamCreateWithFlags(&s->s_out, hipStreamNonBlocking));
-  for (int k = 0; k < ZK_SYNTH_SLOTS; ++k) {
-    ZK_HIP(hipEventCreateWithFlags(&s->ev_in[k], hipEventDisableTiming));
-    ZK_HIP(hipEventCreateWithFlags(&s->ev_k[k], hipEventDisableTiming));
-    ZK_HIP(hipEventCreateWithFlags(&s->ev_out[k], hipEventDisableTiming));
-  }
+  const int rc = zk_ring_create(&s->ring);
+  if (rc) return rc;
   ZK_HIP(hipDeviceSynchronize());  // the table is in place before any stream of any caller reads it
-  return 0;
-}
-
-// one chunk: coefficients up on s_in, kernel on the object's stream, and (a chunk later, so that a copy that blocks the calling
-// thread still runs under the next kernel) the patches down on s_out
-int chunk_in(zk_synth* s, int c, int slot, const double* coeffs_host, int64_t chunk, int64_t n, int out_dtype, size_t out_unit) {
-  if (s->out_busy[slot]) {  // the slot's previous download must have left d_out
-    ZK_HIP(hipEventSynchronize(s->ev_out[slot]));
-    s->out_busy[slot] = false;
-  }
-  const size_t in_unit = (size_t)s->n_funcs * sizeof(double);
-  int e = zk_ensure(&s->d_in[slot], &s->in_cap[slot], (size_t)chunk * in_unit);
-  if (!e) e = zk_ensure(&s->d_out[slot], &s->out_cap[slot], (size_t)chunk * out_unit);
-  if (e) return e;
-  if (c >= ZK_SYNTH_SLOTS) ZK_HIP(hipStreamWaitEvent(s->s_in, s->ev_k[slot], 0));  // the slot's previous kernel has read d_in
-  ZK_HIP(hipMemcpyAsync(s->d_in[slot], coeffs_host + (size_t)c * chunk * s->n_funcs, (size_t)n * in_unit, hipMemcpyHostToDevice, s->s_in));
-  ZK_HIP(hipEventRecord(s->ev_in[slot], s->s_in));
-  ZK_HIP(hipStreamWaitEvent(s->stream, s->ev_in[slot], 0));
-  if ((e = launch(s, (const double*)s->d_in[slot], n, out_dtype, s->d_out[slot], s->stream))) return e;
-  ZK_HIP(hipEventRecord(s->ev_k[slot], s->stream));
-  return 0;
-}
-
-int chunk_out(zk_synth* s, int c, int slot, void* out_host, int64_t chunk, int64_t n, size_t out_unit) {
-  ZK_HIP(hipStreamWaitEvent(s->s_out, s->ev_k[slot], 0));
-  ZK_HIP(hipMemcpyAsync((char*)out_host + (size_t)c * chunk * out_unit, s->d_out[slot], (size_t)n * out_unit, hipMemcpyDeviceToHost, s->s_out));
-  ZK_HIP(hipEventRecord(s->ev_out[slot], s->s_out));
-  s->out_busy[slot] = true;
   return 0;
 }
 
@@ -250,10 +193,8 @@ extern "C" int zk_synth_create(int device, int n_funcs, int64_t n_pixels, const 
 extern "C" int zk_synth_destroy(zk_synth* s) {
   if (!s) return 0;
   ZK_ON_DEVICE(s->device);
-  (void)hipStreamSynchronize(s->s_in);
   (void)hipStreamSynchronize(s->stream);
-  (void)hipStreamSynchronize(s->s_out);
-  release(s);
+  release(s);  // waits for the copy streams
   return 0;
 }
 
@@ -276,30 +217,22 @@ extern "C" int zk_synth_apply(zk_synth* s, const double* coeffs_host, int64_t n_
   if (rc) return rc;
   if (n_rows == 0) return 0;
   ZK_ON_DEVICE(s->device);
-  const size_t out_unit = (size_t)s->n_pixels * (out_dtype == ZK_F32 ? 4 : 8);
-  const size_t unit = (size_t)s->n_funcs * sizeof(double) + out_unit;
+  zk_ring* r = &s->ring;
+  const size_t in_unit = (size_t)s->n_funcs * sizeof(double), out_unit = (size_t)s->n_pixels * zk_elem_size(out_dtype);
   const size_t budget = s->host_chunk ? s->host_chunk : (size_t)256 << 20;
-  int64_t chunk = (int64_t)(budget / unit) & ~(int64_t)(ZK_SYNTH_ROWS - 1);  // whole row tiles
-  if (chunk < ZK_SYNTH_ROWS) chunk = ZK_SYNTH_ROWS;
-  if (chunk > n_rows) chunk = n_rows;
-  const int64_t n_chunks = (n_rows + chunk - 1) / chunk;
-  auto count = [&](int64_t c) { return n_rows - c * chunk < chunk ? n_rows - c * chunk : chunk; };
-  for (int k = 0; k < ZK_SYNTH_SLOTS; ++k) s->out_busy[k] = false;
-  rc = 0;
-  for (int64_t c = 0; c <= n_chunks && !rc; ++c) {
-    if (c < n_chunks) rc = chunk_in(s, (int)c, (int)(c % ZK_SYNTH_SLOTS), coeffs_host, chunk, count(c), out_dtype, out_unit);
-    if (c > 0 && !rc) rc = chunk_out(s, (int)(c - 1), (int)((c - 1) % ZK_SYNTH_SLOTS), out_host, chunk, count(c - 1), out_unit);
-  }
-  // every copy of the job has landed before the call returns, whatever happened
-  const hipError_t a = hipStreamSynchronize(s->s_in), b = hipStreamSynchronize(s->stream), d = hipStreamSynchronize(s->s_out);
+  const zk_chunks ch = zk_chunk_plan(budget, in_unit + out_unit, ZK_SYNTH_ROWS, n_rows);  // whole row tiles
+  rc = zk_ring_run(
+      r, s->stream, ch.n_chunks,
+      [&](int64_t c, int slot) -> int {
+        int e = zk_ring_slot(r, slot, (size_t)ch.chunk * in_unit, (size_t)ch.chunk * out_unit);
+        if (!e) e = zk_ring_up(r, s->stream, c, slot, r->d_in[slot], coeffs_host + (size_t)ch.first(c) * s->n_funcs, (size_t)ch.count(c) * in_unit);
+        return e ? e : launch(s, (const double*)r->d_in[slot], ch.count(c), out_dtype, r->d_out[slot], s->stream);
+      },
+      [&](int64_t c, int slot) -> int {
+        return zk_ring_down(r, slot, (char*)out_host + (size_t)ch.first(c) * out_unit, (size_t)ch.count(c) * out_unit);
+      });
   // an object keeps at most ZK_SYNTH_KEEP_BYTES of slots between calls (a notebook's repeated small calls allocate nothing); the
   // slots of a large job, up to three chunks, go back at once: callers hold one object per table, several at a time
-  size_t held = 0;
-  for (int k = 0; k < ZK_SYNTH_SLOTS; ++k) held += s->in_cap[k] + s->out_cap[k];
-  if (held > ZK_SYNTH_KEEP_BYTES) release_slots(s);
-  if (rc) return rc;
-  if (a != hipSuccess) return zk_hip_fail(a, "hipStreamSynchronize(copy-in)");
-  if (b != hipSuccess) return zk_hip_fail(b, "hipStreamSynchronize(kernel)");
-  if (d != hipSuccess) return zk_hip_fail(d, "hipStreamSynchronize(copy-out)");
-  return 0;
+  if (zk_ring_bytes(r) > ZK_SYNTH_KEEP_BYTES) zk_ring_free_slots(r);
+  return rc;
 }

@@ -34,8 +34,6 @@ namespace {
 constexpr int MAX_RANKS = 16;
 constexpr int SWEEP_BLOCKS = 1024;  // 4 workgroups per CU; a workgroup's share of a 2048^2 frame is 4096 elements
 
-size_t element_size(int dtype) { return dtype == ZK_F64 ? 8 : dtype == ZK_F32 ? 4 : dtype == ZK_U8 ? 1 : 2; }
-
 // Read-only sweep of p[0 .. n): f(value, have) once per element, 16 bytes per lane per request where the address allows (the
 // fewer than two vectors of elements off the 16-byte grid at either end are read one by one).  Every lane of a wave makes the same
 // number of calls, so f may use wave-wide operations: a lane past its last element calls with have = false.
@@ -196,7 +194,7 @@ __global__ __launch_bounds__(256) void stats_final_kernel(const stats_part* __re
 }
 
 unsigned sweep_blocks(long long n, int dtype) {
-  const long long per_block = 256LL * (16 / (long long)element_size(dtype));
+  const long long per_block = 256LL * (16 / (long long)zk_elem_size(dtype));
   return (unsigned)std::max<long long>(1, std::min<long long>((n + per_block - 1) / per_block, SWEEP_BLOCKS));
 }
 
@@ -499,7 +497,7 @@ int check_map(int op, const double* params, const void* out) {
 }
 
 int upload(dev_buf& d, const void* host, int dtype, int64_t n) {
-  const size_t bytes = (size_t)n * element_size(dtype);
+  const size_t bytes = (size_t)n * zk_elem_size(dtype);
   int rc;
   if ((rc = d.alloc(bytes))) return rc;
   ZK_HIP(hipMemcpy(d.p, host, bytes, hipMemcpyHostToDevice));

@@ -95,6 +95,26 @@ def test_chunking_changes_no_bit():
         assert out.shape == (0, 9, 9) and out.dtype == dt
 
 
+def test_slots_freed_after_a_large_job_are_created_again():
+    """Three full slots of 2048 rows (17 MiB each) are above what an object keeps between calls (32 MiB): the call frees them at
+    its end, and the next call, large or small, stages through new ones.  A fourth, partial chunk reuses slot 0 before that."""
+    table = ic.zps(32, 8)._synthesis_entry("lstsq", None)["table"]
+    p, x = table.shape
+    assert (p, x) == (45, 1024)
+    n = 3 * 2048 + 100
+    c = np.random.default_rng(11).standard_normal((n, p))
+    synth = _native.Synthesis.create(table)
+    try:
+        whole = synth.apply(c)                                          # one chunk at the default budget
+        within(whole, c @ table, ic.sum_bound(c, table), "one chunk")
+        synth.set_host_chunk(2048 * 8 * (p + x))
+        np.testing.assert_array_equal(synth.apply(c), whole)
+        synth.set_host_chunk(0)
+        np.testing.assert_array_equal(synth.apply(c[:100]), whole[:100])
+    finally:
+        synth.close()
+
+
 @pytest.mark.parametrize("size,n_max,n", [(9, 4, 257), (17, 8, 257), (32, 8, 257), (33, 10, 257), (64, 12, 17)])
 def test_round_trip_on_the_device(size, n_max, n):
     z = ic.zps(size, n_max)
