@@ -884,6 +884,55 @@ int zk_synth_set_host_chunk(zk_synth* s, int64_t chunk_bytes);   /* staging size
 int zk_synth_apply(zk_synth* s, const double* coeffs_host, int64_t n_rows, int out_dtype /* ZK_F32 | ZK_F64 */, void* out_host);
 int zk_synth_apply_dev(zk_synth* s, const double* coeffs_dev, int64_t n_rows, int out_dtype, void* out_dev, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Rotation alignment of moment rows to templates, and the per-row rotation (csrc/zk_align.hip; the reference has only the
+ * scalar-angle zmoments.rotate and never searches the angle).  Independent of zk_plan: any PAIRED label set -- every
+ * (n, m > 0) comes with (n, -m); full ZPs sets and zmoments.select()ed sets qualify -- with n <= 40.
+ *   rows      : (n_rows, n_poly) float64, C order, real moments with labels n, m (n_poly int32 each, any order);
+ *               pair k = (n, |m|) is the complex moment z_k = x_{n,+m} + i x_{n,-m}
+ *   templates : host, (n_templates, n_poly) float64 in the same real form, 1 <= n_templates <= 64
+ *   select    : host, (n_poly) int32 0 / 1 or NULL (all): the moments that count; both members of a pair alike
+ *   c_m       = sum over the selected pairs with |m_k| = m of z_k conj(t_k)
+ *   f(theta)  = sum_m Re(c_m exp(-i m theta)) = <rotate(z, theta), t> over the selected real moments, so that
+ *               |rotate(z, theta) - t|^2 = |z|^2 + |t|^2 - 2 f(theta); theta in the convention of zmoments.rotate
+ *               (Z^c_{n,m} -> Z^c_{n,m} exp(-i m theta)): rotating the row by `angle` brings it onto the template.
+ * Grid: f on theta_j = j * ((360 / symmetry) / n_theta) degrees, j < n_theta (numpy.linspace(0, 360 / symmetry, n_theta,
+ * endpoint=False)), 1 <= n_theta <= 4096, 1 <= symmetry <= 360; the first maximum wins.  trig_host (optional): the caller's
+ * (n_theta, 2 trig_m) table, row j = cos(m theta_j), m = 1 .. trig_m, then sin(m theta_j), with trig_m >= the largest
+ * selected |m|; NULL: computed by the library with libm.  Tables stay on the device, the eight most recently used per
+ * device: only the first call with a new option set uploads (and synchronises).
+ * Refinement: newton_iters (0 .. 16) Newton steps on f' from the grid maximum theta_0, a step only where f'' < 0, every
+ * iterate clamped to theta_0 +- one grid step, the result wrapped into [0, 360 / symmetry); it is kept only if f there is
+ * >= the grid maximum, else theta_0 stays: score >= max over the grid always.
+ *   angle : (n_rows, n_templates) float64 degrees;  score : (n_rows, n_templates) float64 = f(angle)
+ *   best  : (n_rows) int32: key ZK_ALIGN_DISTANCE: the first argmin_t fma(-2, score, w_t), w_t = |t|^2 over the selection;
+ *           ZK_ALIGN_COSINE: the first argmax_t score * w_t, w_t = 1 / |t|.  key_values_host (n_templates): the w_t, or NULL
+ *           (summed by the library in column order).  Any of the three outputs may be NULL.
+ * zk_rotate_rows: out[r] = row r rotated by angles[r] degrees, (a, b) -> (a cos m t + b sin m t, b cos m t - a sin m t) per
+ * (n, +-m) pair, m = 0 columns copied; out == rows (in place) is allowed and gives the same bits.
+ * Everything is checked before any device call; a refused argument is ZK_E_BADARG with a message.  n_rows == 0 succeeds and
+ * launches nothing.  No atomics: a row's results do not depend on the launch geometry, on its place in the batch or on the
+ * chunking.  The host variants move chunks of at most `chunk_bytes` of input + output (default 256 MiB,
+ * zk_align_set_host_chunk; at least 256 rows) through the staging ring of the device and return when the outputs are complete.
+ * The *_dev variants enqueue on exactly `hip_stream` (NULL = HIP's default stream) and do not synchronise (templates, labels
+ * and key values travel through a page-locked slot of the library's, four calls deep).  Calls are serialised per process.
+ * ------------------------------------------------------------------------------------------------------ */
+#define ZK_ALIGN_DISTANCE 0
+#define ZK_ALIGN_COSINE   1
+int zk_align_rows(int device, const double* rows_host, int64_t n_rows, int n_poly, const int32_t* n, const int32_t* m,
+                  const double* templates_host, int n_templates, const int32_t* select, int n_theta, int symmetry,
+                  int newton_iters, int key, const double* trig_host, int trig_m, const double* key_values_host,
+                  double* angle_out, double* score_out, int32_t* best_out);
+int zk_align_rows_dev(int device, const double* rows_dev, int64_t n_rows, int n_poly, const int32_t* n, const int32_t* m,
+                      const double* templates_host, int n_templates, const int32_t* select, int n_theta, int symmetry,
+                      int newton_iters, int key, const double* trig_host, int trig_m, const double* key_values_host,
+                      double* angle_dev, double* score_dev, int32_t* best_dev, void* hip_stream);
+int zk_align_set_host_chunk(int device, int64_t chunk_bytes);   /* staging size of the two host variants */
+int zk_rotate_rows(int device, const double* rows_host, int64_t n_rows, int n_poly, const int32_t* n, const int32_t* m,
+                   const double* angles_host, double* out_host);
+int zk_rotate_rows_dev(int device, const double* rows_dev, int64_t n_rows, int n_poly, const int32_t* n, const int32_t* m,
+                       const double* angles_dev, double* out_dev, void* hip_stream);
+
 /* Device memory for callers that have no allocator of their own (a NumPy / C user of the *_dev entry points). */
 int zk_device_malloc(int device, int64_t bytes, void** out_dev);
 int zk_device_free(int device, void* dev);

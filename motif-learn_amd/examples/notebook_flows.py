@@ -104,6 +104,16 @@ def main():
     print("         share of each motif carried by |m| in (0, 3, 6):", np.round(share, 2).tolist())
     print("         same patches from the host call:", np.array_equal(motifs, zps.inverse_transform(centres)))
 
+    # ---- the same classes with the rotation taken out: aligned k-means, sharp motifs ----------------------------------
+    from mtflearn_amd.clustering import kmeans_aligned
+    X = moments.numpy()
+    t = time.perf_counter()
+    a_labels, a_centres, a_angles, a_inertia, a_iter = kmeans_aligned(X, zps.n, zps.m, 4, init=centres)
+    a_motifs = zps.inverse_transform(a_centres)                            # beside `motifs`: one orientation per class
+    print(f"         aligned k-means from the plain centres: {a_iter} iterations in {1e3 * (time.perf_counter() - t):.1f} ms, class sizes"
+          f" {np.bincount(a_labels, minlength=4).tolist()}, aligned motifs {a_motifs.shape}; orientation per atom in [0, 360):"
+          f" {np.round(a_angles[:4], 1).tolist()} ...")
+
 
 if __name__ == "__main__":
     main()

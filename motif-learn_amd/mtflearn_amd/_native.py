@@ -22,6 +22,8 @@ ZK_I32 = 5                         # int32 key points (local_max): zk_voronoi_ce
 VORONOI_NEIGHBOURS, VORONOI_GRAPH = 0, 1                           # zk_voronoi_cells modes
 REFINE_BOX, REFINE_DISK = 0, 1                                     # zk_refine_points modes
 THRESHOLD_LI, THRESHOLD_OTSU = 0, 1                                # zk_com_refine thresholds
+ALIGN_DISTANCE, ALIGN_COSINE = 0, 1                                # zk_align_rows keys
+ALIGN_KEYS = {"distance": ALIGN_DISTANCE, "cosine": ALIGN_COSINE}
 KNN_RANGES, KNN_HIST, KNN_SIDES, KNN_GAPS = 0, 1, 2, 3             # zk_knn_stats ops
 PATH_AUTO, PATH_GENERIC, PATH_FOLDED, PATH_SEPARABLE, PATH_STREAM, PATH_DIRECT = 0, 1, 2, 3, 4, 5
 OP_POINTS, OP_MAPS = 1, 2
@@ -206,6 +208,15 @@ SYMBOLS = {
     "zk_synth_set_host_chunk": (c_int, [c_void_p, c_int64]),
     "zk_synth_apply": (c_int, [c_void_p, POINTER(c_double), c_int64, c_int, c_void_p]),
     "zk_synth_apply_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "zk_align_rows": (c_int, [c_int, c_void_p, c_int64, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), c_int,
+                              POINTER(c_int32), c_int, c_int, c_int, c_int, POINTER(c_double), c_int, POINTER(c_double), c_void_p,
+                              c_void_p, c_void_p]),
+    "zk_align_rows_dev": (c_int, [c_int, c_void_p, c_int64, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), c_int,
+                                  POINTER(c_int32), c_int, c_int, c_int, c_int, POINTER(c_double), c_int, POINTER(c_double), c_void_p,
+                                  c_void_p, c_void_p, c_void_p]),
+    "zk_align_set_host_chunk": (c_int, [c_int, c_int64]),
+    "zk_rotate_rows": (c_int, [c_int, c_void_p, c_int64, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p]),
+    "zk_rotate_rows_dev": (c_int, [c_int, c_void_p, c_int64, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
     "zk_device_malloc": (c_int, [c_int, c_int64, POINTER(c_void_p)]),
     "zk_device_free": (c_int, [c_int, c_void_p]),
     "zk_device_copy": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int]),
@@ -633,6 +644,133 @@ class Synthesis:
         device, enqueued on ``stream`` (no synchronisation)."""
         check(self._lib.zk_synth_apply_dev(self._h, c_void_p(coeffs_ptr), int(n_rows), int(code), c_void_p(out_ptr), c_void_p(stream)),
               "zk_synth_apply_dev")
+
+
+class AlignSpec:
+    """The host-side operands of one ``zk_align_rows`` option set, checked and laid out once: labels, templates ``(T, P)``, the
+    0 / 1 selection, the grid's cos / sin table (NumPy's, so that a NumPy statement of the search shares its bits) and the
+    ``T`` key values (``|t|^2`` or ``1 / |t|`` over the selection, NumPy's sums).  Everything the library would refuse is
+    a ``ValueError`` here, before any device call."""
+
+    def __init__(self, n, m, templates, select=None, n_theta=360, symmetry=1, newton_iters=3, key="distance"):
+        self.n = np.ascontiguousarray(n, dtype=np.int32).ravel()
+        self.m = np.ascontiguousarray(m, dtype=np.int32).ravel()
+        check_paired(self.n, self.m)
+        self.templates = np.ascontiguousarray(templates, dtype=np.float64)
+        if self.templates.ndim != 2 or self.templates.shape[1] != len(self.n):
+            raise ValueError(f"templates must be a (T, {len(self.n)}) matrix of real moments with the rows' labels")
+        if not 1 <= self.templates.shape[0] <= 64:
+            raise ValueError(f"align takes between 1 and 64 templates, not {self.templates.shape[0]}")
+        if int(n_theta) != n_theta or not 1 <= n_theta <= 4096:
+            raise ValueError(f"n_theta must be an integer between 1 and 4096, not {n_theta!r}")
+        if int(symmetry) != symmetry or not 1 <= symmetry <= 360:
+            raise ValueError(f"symmetry must be an integer between 1 and 360, not {symmetry!r}")
+        if int(newton_iters) != newton_iters or not 0 <= newton_iters <= 16:
+            raise ValueError(f"newton_iters must be an integer between 0 and 16, not {newton_iters!r}")
+        if key not in ALIGN_KEYS:
+            raise ValueError(f"key must be 'distance' or 'cosine', not {key!r}")
+        self.select = np.ones(len(self.n), dtype=np.int32) if select is None else np.ascontiguousarray(select, dtype=np.int32).ravel()
+        if self.select.shape != self.n.shape:
+            raise ValueError("the selection must have one entry per moment")
+        self.n_theta, self.symmetry, self.newton_iters, self.key = int(n_theta), int(symmetry), int(newton_iters), key
+        kept = self.select != 0
+        self.trig_m = int(np.abs(self.m[kept]).max()) if kept.any() else 0
+        self.theta = np.linspace(0, 360 / self.symmetry, self.n_theta, endpoint=False)
+        angles = np.multiply.outer(np.deg2rad(self.theta), np.arange(1, self.trig_m + 1))
+        self.trig = np.ascontiguousarray(np.hstack([np.cos(angles), np.sin(angles)]))       # (n_theta, 2 trig_m)
+        sq = (self.templates[:, kept] ** 2).sum(axis=1)
+        self.key_values = np.ascontiguousarray(sq if key == "distance" else 1.0 / np.sqrt(sq))
+
+    @property
+    def n_templates(self):
+        return self.templates.shape[0]
+
+    def _tail(self):
+        pi, pd = POINTER(c_int32), POINTER(c_double)
+        return (len(self.n), self.n.ctypes.data_as(pi), self.m.ctypes.data_as(pi), self.templates.ctypes.data_as(pd), self.n_templates,
+                self.select.ctypes.data_as(pi), self.n_theta, self.symmetry, self.newton_iters, ALIGN_KEYS[self.key],
+                self.trig.ctypes.data_as(pd) if self.trig_m else None, self.trig_m, self.key_values.ctypes.data_as(pd))
+
+
+def check_paired(n, m):
+    """The label set of the alignment kernels: ``0 <= |m| <= n <= 40``, no label twice, every ``(n, m)`` with its ``(n, -m)``."""
+    n, m = np.asarray(n), np.asarray(m)
+    if n.shape != m.shape or n.ndim != 1 or n.size == 0:
+        raise ValueError("`n` and `m` must be 1-D and of one length")
+    if (n < 0).any() or (n > 40).any() or (np.abs(m) > n).any():
+        raise ValueError("the alignment kernels take labels with 0 <= |m| <= n <= 40")
+    have = set(zip(n.tolist(), m.tolist()))
+    if len(have) != n.size:
+        raise ValueError("a label (n, m) occurs twice")
+    for nn, mm in have:
+        if (nn, -mm) not in have:
+            raise ValueError(f"the label set is not paired: (n, m) = ({nn}, {mm}) has no (n, -m) beside it "
+                             "(full ZPs sets and select()ed sets qualify)")
+
+
+def align_rows(rows, spec, device=None):
+    """``zk_align_rows``: host rows ``(N, P)`` float64 against ``spec`` (:class:`AlignSpec`) -> ``(angle (N, T), score (N, T),
+    best (N) int32)`` host arrays."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != len(spec.n):
+        raise ValueError(f"rows must be (N, {len(spec.n)})")
+    n, t = rows.shape[0], spec.n_templates
+    angle, score, best = np.empty((n, t)), np.empty((n, t)), np.empty(n, dtype=np.int32)
+    if n == 0:
+        return angle, score, best
+    require_device()
+    dev = default_device() if device is None else int(device)
+    check(load().zk_align_rows(dev, rows.ctypes.data_as(c_void_p), n, *spec._tail(), angle.ctypes.data_as(c_void_p),
+                               score.ctypes.data_as(c_void_p), best.ctypes.data_as(c_void_p)), "zk_align_rows")
+    return angle, score, best
+
+
+def align_rows_dev(device, rows_ptr, n_rows, spec, angle_ptr, score_ptr, best_ptr, stream=0):
+    """``zk_align_rows_dev``: rows and outputs on the device (an output pointer may be 0), enqueued on ``stream``."""
+    check(load().zk_align_rows_dev(int(device), c_void_p(rows_ptr), int(n_rows), *spec._tail(), c_void_p(angle_ptr), c_void_p(score_ptr),
+                                   c_void_p(best_ptr), c_void_p(stream)), "zk_align_rows_dev")
+
+
+def align_set_host_chunk(chunk_bytes, device=None):
+    """Bytes of input + output per chunk of :func:`align_rows` and :func:`rotate_rows` (0: the default of 256 MiB)."""
+    check(load().zk_align_set_host_chunk(default_device() if device is None else int(device), int(chunk_bytes)),
+          "zk_align_set_host_chunk")
+
+
+def _labels32(n, m):
+    n32, m32 = np.ascontiguousarray(n, dtype=np.int32).ravel(), np.ascontiguousarray(m, dtype=np.int32).ravel()
+    check_paired(n32, m32)
+    return n32, m32
+
+
+def rotate_rows(rows, n, m, angles, out=None, device=None):
+    """``zk_rotate_rows``: host rows ``(N, P)`` float64, each rotated by its own angle (degrees) -> ``(N, P)``; ``out`` may be
+    ``rows`` itself (in place)."""
+    n32, m32 = _labels32(n, m)
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    angles = np.ascontiguousarray(angles, dtype=np.float64).ravel()
+    if rows.ndim != 2 or rows.shape[1] != len(n32) or angles.shape[0] != rows.shape[0]:
+        raise ValueError(f"rows must be (N, {len(n32)}) and angles (N)")
+    if out is None:
+        out = np.empty_like(rows)
+    elif out.shape != rows.shape or out.dtype != np.float64 or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous float64 array of the rows' shape")
+    if rows.shape[0] == 0:
+        return out
+    require_device()
+    dev = default_device() if device is None else int(device)
+    pi = POINTER(c_int32)
+    check(load().zk_rotate_rows(dev, rows.ctypes.data_as(c_void_p), rows.shape[0], len(n32), n32.ctypes.data_as(pi), m32.ctypes.data_as(pi),
+                                angles.ctypes.data_as(c_void_p), out.ctypes.data_as(c_void_p)), "zk_rotate_rows")
+    return out
+
+
+def rotate_rows_dev(device, rows_ptr, n_rows, n, m, angles_ptr, out_ptr, stream=0):
+    """``zk_rotate_rows_dev``: everything on the device, enqueued on ``stream``; ``out_ptr`` may equal ``rows_ptr``."""
+    n32, m32 = _labels32(n, m)
+    pi = POINTER(c_int32)
+    check(load().zk_rotate_rows_dev(int(device), c_void_p(rows_ptr), int(n_rows), len(n32), n32.ctypes.data_as(pi), m32.ctypes.data_as(pi),
+                                    c_void_p(angles_ptr), c_void_p(out_ptr), c_void_p(stream)), "zk_rotate_rows_dev")
 
 
 def allgather_rows_plan(rank, world, n_planes, height, width, rows_per_rank, row_off, n_rows, algo=COMM_AUTO):

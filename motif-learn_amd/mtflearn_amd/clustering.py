@@ -29,7 +29,7 @@ import numpy as np
 from . import _native
 
 __all__ = ["kmeans_lbs", "gmm_lbs", "sort_lbs", "seg_lbs", "normalize_xy", "DeviceRows", "kmeans_fit", "gmm_fit_predict",
-           "gather_labels"]
+           "gather_labels", "kmeans_aligned"]
 
 _PD = POINTER(c_double)
 
@@ -476,6 +476,102 @@ def kmeans_fit(X, n_clusters, random_state=0, max_iter=300, tol=1e-4, comm=None)
     finally:
         if own:
             rows.close()
+
+
+def _aligned_select(m, m_select):
+    if m_select is None:
+        return None
+    return np.isin(np.abs(np.asarray(m)), np.unique(np.abs(np.atleast_1d(m_select)))).astype(np.int32)
+
+
+def kmeans_aligned(X, n, m, n_clusters, init=None, max_iter=50, tol=1e-4, random_state=None, m_select=None, symmetry=1):
+    """Rotation-invariant k-means of Zernike-moment rows: Lloyd iterations whose assignment is ``zmoments.align`` (the class
+    whose template is nearest after the best rotation, and that rotation) and whose update is the class mean of the rows
+    rotated by their own angles -- a host loop over ``zk_align_rows_dev``, ``zk_rotate_rows_dev`` and the per-class sums of
+    :class:`DeviceRows`; the matrix is uploaded once.
+
+    ``X``: ``(N, P)`` real moments with labels ``n``, ``m`` (a paired set, ``P <= 127``); ``init``: a ``(k, P)`` array of
+    starting templates, or None for ``k`` distinct rows drawn with ``random_state``; ``m_select`` / ``symmetry`` as in
+    ``zmoments.align`` (the class means are taken over all moments).  Stops by scikit-learn's rules as :func:`kmeans_fit`
+    states them: when no label changes, or when the squared centre shift summed over the classes is ``<= tol`` times the mean
+    column variance of ``X``; after the latter the labels are made consistent with the final templates.  An empty class keeps
+    its template.  Returns ``(labels int32 (N), templates (k, P), angles (N) degrees, inertia, n_iter)`` with ``inertia`` the
+    sum of ``|rotate(x, angle) - t|^2`` over the selected moments."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] == 0:
+        raise ValueError("X must be a non-empty (N, P) matrix of real moments")
+    n_rows, p = X.shape
+    if p > 127:
+        raise ValueError("kmeans_aligned takes at most 127 moments per row (the per-class sums of DeviceRows)")
+    if not isinstance(n_clusters, (int, np.integer)) or not 1 <= n_clusters <= 64 or n_clusters > n_rows:
+        raise ValueError(f"n_clusters must be an int between 1 and min(64, N), not {n_clusters!r}")
+    k = int(n_clusters)
+    select = _aligned_select(m, m_select)
+    if init is None:
+        rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+        templates = X[np.sort(rs.choice(n_rows, k, replace=False))].copy()
+    else:
+        templates = np.array(init, dtype=np.float64)
+        if templates.shape != (k, p):
+            raise ValueError(f"init must be a ({k}, {p}) array")
+    _native.AlignSpec(n, m, templates, select, 360, symmetry, 3, "distance")   # every refusal before the device is touched
+    tol_abs = float(np.mean(np.var(X, axis=0)) * tol)
+    kept = slice(None) if select is None else select != 0
+    x_sq = (X[:, kept] ** 2).sum(axis=1)
+    _native.require_device()
+    dev = _native.default_device()
+    lib = _native.load()
+    x_dev = _native.DeviceArray.from_numpy(X, dev)
+    y_dev = _native.DeviceArray((n_rows, p), np.float64, dev)
+    angle_dev = _native.DeviceArray((n_rows, k), np.float64, dev)
+    score_dev = _native.DeviceArray((n_rows, k), np.float64, dev)
+    best_dev = _native.DeviceArray((n_rows,), np.int32, dev)
+    own_dev = _native.DeviceArray((n_rows,), np.float64, dev)
+    rows = DeviceRows.adopt(y_dev.data_ptr(), n_rows, p, device=dev)
+    try:
+        labels_ptr = None
+        shift0 = np.zeros(p)
+
+        def assign(tm):
+            spec = _native.AlignSpec(n, m, tm, select, 360, symmetry, 3, "distance")
+            _native.align_rows_dev(dev, x_dev.data_ptr(), n_rows, spec, angle_dev.data_ptr(), score_dev.data_ptr(), best_dev.data_ptr())
+            angle, score, best = angle_dev.numpy(), score_dev.numpy(), best_dev.numpy()
+            at = np.arange(n_rows)
+            return best, np.ascontiguousarray(angle[at, best]), score[at, best], spec.key_values
+
+        labels = angles = own_score = key_values = None
+        n_iter, strict = 0, False
+        for n_iter in range(1, max_iter + 1):
+            new_labels, angles, own_score, key_values = assign(templates)
+            if labels is not None and np.array_equal(new_labels, labels):
+                strict = True
+                break
+            labels = new_labels
+            _native.check(lib.zk_device_copy(dev, c_void_p(own_dev.data_ptr()), angles.ctypes.data_as(c_void_p), angles.nbytes, 1), "zk_device_copy")
+            _native.rotate_rows_dev(dev, x_dev.data_ptr(), n_rows, n, m, own_dev.data_ptr(), y_dev.data_ptr())
+            _native.check(lib.zk_device_synchronize(dev), "zk_device_synchronize")      # the passes below run on the rows' own stream
+            if labels_ptr is None:
+                rows.lloyd(templates, update=False)     # one plain pass, for the label array it creates; align's labels replace its own
+                labels_ptr = lib.zk_rows_labels_dev(rows._h)
+            _native.check(lib.zk_device_copy(dev, c_void_p(labels_ptr), c_void_p(best_dev.data_ptr()), 4 * n_rows, 3), "zk_device_copy")
+            rows.resp_from_labels(k)
+            gram = rows.moments(0, shift0, count=k)                                     # (k, P+1, P+1): column sums and the count
+            sums, counts = gram[:, :p, p], gram[:, p, p]
+            new_templates = templates.copy()
+            filled = counts > 0
+            new_templates[filled] = sums[filled] / counts[filled][:, None]
+            shift_total = ((new_templates - templates) ** 2).sum()
+            templates = new_templates
+            if shift_total <= tol_abs:
+                break
+        if not strict:
+            labels, angles, own_score, key_values = assign(templates)
+        inertia = float((x_sq + key_values[labels] - 2.0 * own_score).sum())
+        return labels.astype(np.int32), templates, angles, inertia, n_iter
+    finally:
+        rows.close()
+        for a in (x_dev, y_dev, angle_dev, score_dev, best_dev, own_dev):
+            a.close()
 
 
 def gather_labels(labels, comm):

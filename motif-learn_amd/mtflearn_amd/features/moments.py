@@ -14,12 +14,17 @@ methods here are the small per-moment-axis contractions of SURVEY 8a rows 8-14.
 """
 from __future__ import annotations
 
+from collections import namedtuple
+
 import numpy as np
 
 __all__ = [
     "nm2j", "nm2j_complex", "check_array1d", "construct_complex_matrix",
-    "construct_real_matrix", "construct_rot_maps_matrix", "zmoments",
+    "construct_real_matrix", "construct_rot_maps_matrix", "zmoments", "AlignResult",
 ]
+
+# what zmoments.align returns: angle (N, T) degrees, score (N, T) = f(angle), best (N) int32
+AlignResult = namedtuple("AlignResult", ["angle", "score", "best"])
 
 
 def _require_integral(values, message):
@@ -247,6 +252,60 @@ class zmoments:
         if zc.data.ndim == 3:
             phase = phase[:, None, None]
         return zmoments._adopt(data=zc.data * phase, n=zc.n, m=zc.m, patch_size=self.patch_size)
+
+    # -- rotation alignment (no reference counterpart; csrc/zk_align.hip) --------------------
+    def _rank2_real(self, what):
+        if self.data.ndim != 2:
+            raise ValueError(f"{what} works on rank-2 (N, N_poly) moments; this container holds rank-{self.data.ndim} data "
+                             "(dense frames are out of scope)")
+        return self.to_real()
+
+    def _align_spec(self, templates, m_select=None, n_theta=360, symmetry=1, refine=True, key="distance"):
+        """The checked host operands of :meth:`align` (``_native.AlignSpec``) and the real form of the rows."""
+        from .. import _native
+        real = self._rank2_real("align")
+        if isinstance(templates, zmoments):
+            tm = templates._rank2_real("align (templates)")
+            if not (np.array_equal(tm.n, real.n) and np.array_equal(tm.m, real.m)):
+                raise ValueError("the templates must carry the labels of the rows")
+            tdata = tm.data
+        else:
+            tdata = np.asarray(templates)
+            if np.iscomplexobj(tdata):
+                raise ValueError("a complex template array needs its labels: pass a zmoments")
+            if tdata.ndim == 1:
+                tdata = tdata[None, :]
+        select = None if m_select is None else np.isin(np.abs(real.m), np.unique(np.abs(check_array1d(m_select)))).astype(np.int32)
+        spec = _native.AlignSpec(real.n, real.m, tdata, select, n_theta, symmetry, 3 if refine else 0, key)
+        return real, spec
+
+    def align(self, templates, m_select=None, n_theta=360, symmetry=1, refine=True, key="distance"):
+        """The rotation that best brings every row onto every template, on the GPU.
+
+        With ``z`` the complex form of a row and ``t`` of a template, ``f(theta) = <rotate(z, theta), t>`` over the real
+        moments whose ``|m|`` is in ``m_select`` (all by default), so that ``|rotate(z, theta) - t|^2 = |z|^2 + |t|^2 -
+        2 f(theta)``.  ``f`` is evaluated on ``linspace(0, 360 / symmetry, n_theta, endpoint=False)`` degrees (``symmetry = q``
+        for ``q``-fold templates, whose ``f`` has period ``360 / q``), the first maximum is taken and, with ``refine``, polished
+        by three Newton steps that never leave the two neighbouring grid cells and never lower ``f``.
+
+        Returns ``AlignResult(angle, score, best)``: ``angle (N, T)`` in degrees, in the convention of :meth:`rotate` --
+        ``self.rotate_each(angle[:, t])`` lies on template ``t`` -- ``score (N, T) = f(angle)`` and ``best (N)`` int32, the
+        first ``argmin_t (|t|^2 - 2 score)`` (``key="distance"``) or the first ``argmax_t score / |t|`` (``key="cosine"``), norms
+        over the selection.  ``templates``: a rank-2 :class:`zmoments` or a ``(T, P)`` real array with the rows' labels,
+        ``T <= 64``.  The label set must be paired (every ``(n, m)`` with its ``(n, -m)``) with ``n <= 40``; input is finite."""
+        from .. import _native
+        real, spec = self._align_spec(templates, m_select, n_theta, symmetry, refine, key)
+        return AlignResult(*_native.align_rows(real.data, spec))
+
+    def rotate_each(self, angles):
+        """Real moments of every row's pattern rotated by its own angle (degrees), on the GPU: row ``r`` is
+        ``self[r].rotate(angles[r])`` in real form.  :meth:`rotate` (one angle for all, complex form) stays as it is."""
+        from .. import _native
+        real = self._rank2_real("rotate_each")
+        angles = np.asarray(angles, dtype=np.float64)
+        if angles.shape != (real.data.shape[0],):
+            raise ValueError(f"angles must have shape ({real.data.shape[0]},), one per row")
+        return real._like(_native.rotate_rows(real.data, real.n, real.m, angles))
 
     def _prepared(self, m_unselect, p):
         picked = self.unselect(m_unselect)

@@ -498,6 +498,66 @@ def inverse_transform_device(zps, coeffs_dev, n_rows=None, method="lstsq", m_sel
     return out
 
 
+# align_device and rotate_rows_device are newer than the move out of mtflearn_amd.distributed: they are reached as
+# resident.align_device / resident.rotate_rows_device and are not part of __all__, which lists exactly the names that module
+# re-exports under their first address.
+def _resident_rows(rows, n_cols, what):
+    if not getattr(rows, "is_cuda", False):
+        raise ValueError(f"{what} must live on the GPU")
+    if not rows.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    if len(rows.shape) != 2 or rows.shape[1] != n_cols or _device.np_dtype(rows) != np.float64:
+        raise ValueError(f"{what} must be an (N, {n_cols}) float64 matrix of real Zernike moments")
+
+
+def align_device(rows, n, m, templates, m_select=None, n_theta=360, symmetry=1, refine=True, key="distance"):
+    """The resident twin of ``zmoments.align``: ``rows`` is an ``(N, P)`` float64 torch tensor or ``DeviceArray`` of real
+    moments with labels ``n``, ``m`` (e.g. what :func:`points_moments_device` returns, with ``zps.n``, ``zps.m``);
+    ``templates`` is a host ``(T, P)`` array (or a rank-2 real ``zmoments``) with the same labels -- small, and the library
+    derives its operand tables from it on the host.  Returns ``AlignResult(angle (N, T), score (N, T), best (N) int32)`` as
+    device arrays of ``rows``'s kind, enqueued on torch's current stream (a ``DeviceArray``: the default stream) without
+    synchronising, except for the table upload of the first call with a new option set.  Everything is checked before any
+    device call."""
+    from .features.moments import AlignResult, zmoments
+    n, m = np.asarray(n), np.asarray(m)
+    _resident_rows(rows, len(n), "rows")
+    tm = templates.to_real().data if isinstance(templates, zmoments) else np.asarray(templates)
+    probe = zmoments._adopt(np.zeros((1, len(n))), n, m)
+    if not np.array_equal(probe.n, n) or not np.array_equal(probe.m, m):
+        raise ValueError("n, m must be in (n, m) lexicographic order, as ZPs.n / ZPs.m are")
+    _, spec = probe._align_spec(tm, m_select, n_theta, symmetry, refine, key)
+    rows_n, t = int(rows.shape[0]), spec.n_templates
+    angle, score = _device.empty((rows_n, t), np.float64, rows), _device.empty((rows_n, t), np.float64, rows)
+    best = _device.empty((rows_n,), np.int32, rows)
+    if rows_n:
+        _native.align_rows_dev(rows.device.index, rows.data_ptr(), rows_n, spec, angle.data_ptr(), score.data_ptr(), best.data_ptr(),
+                               stream_ptr(rows))
+    return AlignResult(angle, score, best)
+
+
+def rotate_rows_device(rows, n, m, angles, out=None):
+    """The resident twin of ``zmoments.rotate_each``: every row of the ``(N, P)`` float64 device matrix rotated by its own
+    angle (``angles``: ``(N)`` float64 degrees on the same device, e.g. a column of :func:`align_device`'s ``angle`` made
+    contiguous).  ``out`` may be ``rows`` (in place).  Returns the rotated rows as a device array of ``rows``'s kind, enqueued
+    on torch's current stream without synchronising."""
+    n, m = np.asarray(n), np.asarray(m)
+    _resident_rows(rows, len(n), "rows")
+    rows_n = int(rows.shape[0])
+    if (not getattr(angles, "is_cuda", False) or not angles.is_contiguous() or tuple(angles.shape) != (rows_n,)
+            or _device.np_dtype(angles) != np.float64 or angles.device.index != rows.device.index):
+        raise ValueError(f"angles must be a contiguous ({rows_n},) float64 array on the device of rows")
+    if out is None:
+        out = _device.empty((rows_n, len(n)), np.float64, rows)
+    else:
+        _resident_rows(out, len(n), "out")
+        if int(out.shape[0]) != rows_n or out.device.index != rows.device.index:
+            raise ValueError("out must have the shape and the device of rows")
+    _native.check_paired(n, m)
+    if rows_n:
+        _native.rotate_rows_dev(rows.device.index, rows.data_ptr(), rows_n, n, m, angles.data_ptr(), out.data_ptr(), stream_ptr(rows))
+    return out
+
+
 def denoise_svd_device(image, patch_size, n_components, extraction_step=None, return_s=False):
     """:func:`mtflearn_amd.denoise_svd` of a frame resident on the GPU (a torch tensor or a
     :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` of float32 / float64 / uint8 / uint16 / int16).  Returns the float64
