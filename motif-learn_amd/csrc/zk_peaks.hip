@@ -3,6 +3,10 @@
 //
 //   candidates   skimage.feature.peak_local_max(image, min_distance=1, threshold_abs=t): pixels equal to the maximum of
 //                their 3 x 3 neighbourhood, strictly above t, off the 1-px border; none at all in a constant image
+//   NaN          neither the reference nor scikit-image defines it; the rule here (tests/local_max_oracle.py restates it):
+//                the minimum (the default threshold) and the constant-image test are taken over the non-NaN pixels, an image
+//                with no non-NaN pixel has no candidates, a NaN pixel is never a candidate (v > t is false) and a NaN
+//                neighbour never outranks a pixel (NaN > v is false): NaN acts as -inf in the 3 x 3 maximum, and only there
 //   suppression  filter_peaks_by_distance: candidates visited in descending intensity, a kept one drops every other
 //                candidate at Euclidean distance <= min_distance
 //

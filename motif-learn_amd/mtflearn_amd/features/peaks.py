@@ -63,6 +63,11 @@ def local_max(image, min_distance, threshold=None):
     reference's (``honeycomb_frame(512, seed=0)`` as uint8 0..255 at ``min_distance=5``: 811 tied pairs within reach, 3 437
     points here, 3 434 from the reference on one x86 host).  Without such ties the result is the reference's array.
 
+    NaN pixels (neither the reference nor scikit-image defines them): the default threshold ``image.min()`` and the
+    constant-image test are taken over the non-NaN pixels, and an image with no non-NaN pixel has no candidates; a NaN
+    pixel is never a candidate, and a NaN neighbour never exceeds a pixel -- in the 3 x 3 maximum, and only there, NaN
+    counts as ``-inf``.  ``+inf`` and ``-inf`` are ordinary values: equal infinities tie like any equal intensities.
+
     Accepts what :class:`ZPs` accepts (uint8 / uint16 / int16 cross to the device as they are and are widened there,
     exactly).  Runs on the GPU only: without a HIP device it raises ``RuntimeError``."""
     image = np.asarray(image)

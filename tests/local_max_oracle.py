@@ -1,6 +1,6 @@
 """Host restatement of ``local_max`` with the package's tie rule (equal intensities in raster order): the checker of
-tests/test_local_max_cpu.py and tests/test_gpu_local_max.py and the host side of tools/time_local_max.py.  It is the
-checker, never the product."""
+tests/test_local_max_cpu.py, tests/test_gpu_local_max.py and tests/test_gpu_local_max_kernels.py and the host side of
+tools/time_local_max.py.  It is the checker, never the product."""
 import numpy as np
 from scipy import ndimage
 from scipy.spatial import cKDTree
@@ -8,18 +8,62 @@ from scipy.spatial import cKDTree
 
 def candidate_mask(image, threshold=None):
     """3 x 3 maxima (``maximum_filter``, mode 'nearest') ``> threshold`` (NumPy's comparison; None: the minimum), off the
-    1-px border; none in a constant image (scikit-image's trivial-image rule)."""
+    1-px border; none in a constant image (scikit-image's trivial-image rule).
+
+    NaN (the package's own rule; neither the reference nor scikit-image defines one): the minimum and the constant-image
+    test are taken over the non-NaN pixels, an image with no non-NaN pixel has no candidates, a NaN pixel is never a
+    candidate and a NaN neighbour never exceeds a pixel (NaN counts as -inf in the 3 x 3 maximum, and only there)."""
     image = np.asarray(image)
     mask = np.zeros(image.shape, dtype=bool)
     if image.size == 0:
         return mask
-    mask = image == ndimage.maximum_filter(image, size=3, mode="nearest")
-    if mask.all():
-        mask[:] = False
-    mask &= image > (image.min() if threshold is None else threshold)
+    nan = np.isnan(image) if image.dtype.kind == "f" else np.zeros(image.shape, dtype=bool)
+    if nan.any():
+        valid = image[~nan]
+        if valid.size == 0 or valid.min() == valid.max():
+            return mask
+        lowest = valid.min()
+        mask = image == ndimage.maximum_filter(np.where(nan, image.dtype.type(-np.inf), image), size=3, mode="nearest")
+    else:
+        lowest = image.min()
+        mask = image == ndimage.maximum_filter(image, size=3, mode="nearest")
+        if mask.all():
+            mask[:] = False
+    with np.errstate(invalid="ignore"):
+        mask &= image > (lowest if threshold is None else threshold)
     mask[:1] = mask[-1:] = False
     mask[:, :1] = mask[:, -1:] = False
     return mask
+
+
+# ---- which suppression kernel the host takes (csrc/zk_peaks.hip: TILE_W, TILE_H, TILE_LDS_MAX and the disk of local_max_core)
+TILE_W, TILE_H, TILE_LDS_MAX = 64, 16, 60 * 1024
+
+
+def tile_lds_bytes(r, H, W):
+    """Dynamic LDS the tiled suppression kernel would need for radius ``r`` on an ``H x W`` frame, as the host computes it:
+    a ``TILE_W x TILE_H`` tile plus a halo of ``floor(r)`` clipped to the frame (``Rx = min(floor(r), W - 1)``, ``Ry``
+    likewise), 5 bytes per cell (int32 rank, one state byte), plus 4 bytes per offset of the inclusive disk
+    ``dx^2 + dy^2 <= r^2`` inside that halo, the centre excluded.  The host takes the tiled kernel while this is
+    ``<= TILE_LDS_MAX`` and one global round per launch otherwise."""
+    r = float(r)
+    Rx, Ry = int(min(np.floor(r), W - 1)), int(min(np.floor(r), H - 1))
+    LW, LH = TILE_W + 2 * Rx, TILE_H + 2 * Ry
+    dy, dx = np.mgrid[-Ry:Ry + 1, -Rx:Rx + 1].astype(np.int64)
+    n_off = int(((dx * dx + dy * dy).astype(np.float64) <= r * r).sum()) - 1
+    return LW * LH * 5 + 4 * n_off
+
+
+def plateaus(dtype, shape=(96, 112), seed=0):
+    """Integer frames full of ties: flat-topped blobs, equal peaks side by side, and a coarse random texture."""
+    rng = np.random.default_rng(seed)
+    hi = 250 if dtype == np.uint8 else 60000
+    img = rng.integers(0, 6, shape) * (hi // 10)
+    for _ in range(40):
+        y, x = rng.integers(2, shape[0] - 4), rng.integers(2, shape[1] - 4)
+        img[y:y + rng.integers(1, 4), x:x + rng.integers(1, 4)] = rng.choice([hi // 2, hi])
+    img[10, 10:40:2] = hi                   # a row of equal peaks 2 px apart
+    return img.astype(dtype)
 
 
 def candidates_by_priority(image, threshold=None):

@@ -29,16 +29,7 @@ def test_golden_cases(case):
     assert_same_rows(got, lmo.local_max_raster(img, r, t))
 
 
-def _plateaus(dtype, shape=(96, 112), seed=0):
-    """Integer frames full of ties: flat-topped blobs, equal peaks side by side, and a coarse random texture."""
-    rng = np.random.default_rng(seed)
-    hi = 250 if dtype == np.uint8 else 60000
-    img = rng.integers(0, 6, shape) * (hi // 10)
-    for _ in range(40):
-        y, x = rng.integers(2, shape[0] - 4), rng.integers(2, shape[1] - 4)
-        img[y:y + rng.integers(1, 4), x:x + rng.integers(1, 4)] = rng.choice([hi // 2, hi])
-    img[10, 10:40:2] = hi                   # a row of equal peaks 2 px apart
-    return img.astype(dtype)
+_plateaus = lmo.plateaus
 
 
 @pytest.mark.parametrize("dtype", [np.uint8, np.uint16])

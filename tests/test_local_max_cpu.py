@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 from scipy import ndimage
 
+import local_max_cases as lmc
 import local_max_oracle as lmo
 from mtflearn_amd.features import local_max
 from mtflearn_amd.features.peaks import _comparison_threshold
@@ -112,3 +113,86 @@ def test_fails_loudly_without_device():
         pytest.skip("a HIP device is visible")
     with pytest.raises(RuntimeError, match="no HIP device"):
         local_max(np.random.default_rng(0).random((32, 32)), 3)
+
+
+# ---- the oracle's additions (NaN rule, tile_lds_bytes) and the inputs of tests/test_gpu_local_max_kernels.py
+@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+def test_candidate_mask_still_gives_the_stored_candidates(case):
+    mask = lmo.candidate_mask(case["image"], case["t"])
+    np.testing.assert_array_equal(np.stack(np.nonzero(mask), axis=1).reshape(-1, 2), case["candidates"])
+
+
+def test_candidate_mask_nan_rule():
+    nan = np.nan
+    img = np.array([[0, 0, 0, 0, 0, 0, 0],
+                    [0, 3, nan, 1, 0, 2, 0],          # a NaN neighbour exceeds neither the 3 nor the 1; the 2 has one below
+                    [0, 0, 0, 0, 0, nan, 0],
+                    [0, nan, 0, 0, 0, 0, 0],
+                    [nan, 0, 0, 0, 0, 0, nan]], dtype=np.float64)
+    for dtype in (np.float32, np.float64):
+        mask = lmo.candidate_mask(img.astype(dtype))
+        assert sorted(zip(*np.nonzero(mask))) == [(1, 1), (1, 3), (1, 5)]
+        assert sorted(zip(*np.nonzero(lmo.candidate_mask(img.astype(dtype), 1)))) == [(1, 1), (1, 5)]
+        assert sorted(zip(*np.nonzero(lmo.candidate_mask(img.astype(dtype), -1)))) == [(1, 1), (1, 3), (1, 5), (3, 2), (3, 3), (3, 4), (3, 5)]
+    low = np.where(np.isnan(img), nan, -img - 1)      # negative everywhere: the default threshold is the non-NaN minimum, -4
+    assert sorted(zip(*np.nonzero(lmo.candidate_mask(low)))) == [(1, 4), (2, 1), (2, 2), (2, 3), (2, 4), (3, 2), (3, 3), (3, 4), (3, 5)]
+    assert not lmo.candidate_mask(np.full((5, 6), nan)).any()
+    const = np.full((5, 6), 0.5)
+    const[2, 2] = const[0, 3] = nan
+    assert not lmo.candidate_mask(const).any() and not lmo.candidate_mask(const, 0.0).any()
+    with np.errstate(all="raise"):                    # the NaN path raises no floating-point warning
+        lmo.candidate_mask(img)
+    assert lmo.local_max_raster(img, 2.0).tolist() == [[1, 1], [5, 1]]       # 1 at (3, 1) falls to the 3 two pixels away
+    assert lmo.local_max_raster(np.full((5, 6), nan), 2.0).shape == (0, 2)
+
+
+def test_tile_lds_bytes_restates_the_host_formula():
+    assert lmo.tile_lds_bytes(31, 96, 160) == 61140 == 126 * 78 * 5 + 4 * 3000
+    assert lmo.tile_lds_bytes(31, 96, 160) <= lmo.TILE_LDS_MAX == 61440 < lmo.tile_lds_bytes(31.4, 96, 160)
+    assert lmo.tile_lds_bytes(0, 96, 160) == 64 * 16 * 5
+    assert lmo.tile_lds_bytes(1, 96, 160) == 66 * 18 * 5 + 4 * 4
+    assert lmo.tile_lds_bytes(np.sqrt(2), 96, 160) == 66 * 18 * 5 + 4 * 8
+    assert lmo.tile_lds_bytes(8, 240, 256) == 80 * 32 * 5 + 4 * 196      # 197 lattice points in the closed disk of radius 8
+    for r in lmc.WIDE_RADII:
+        assert lmo.tile_lds_bytes(r, *lmc.FRAME) <= lmo.TILE_LDS_MAX
+    for r in lmc.CROSSOVER_RADII[1:] + (33.0, 45.5):
+        assert lmo.tile_lds_bytes(r, *lmc.FRAME) > lmo.TILE_LDS_MAX
+    for name, shape, r, tiled in lmc.CLIPPED:
+        assert (lmo.tile_lds_bytes(r, *shape) <= lmo.TILE_LDS_MAX) == tiled, name
+    assert lmo.tile_lds_bytes(40, 150, 20) == 60904 == (64 + 38) * (16 + 80) * 5 + 4 * lmc.disk_offsets(40, 19, 40)
+    assert lmo.tile_lds_bytes(40, 20, 150) == (64 + 80) * (16 + 38) * 5 + 4 * lmc.disk_offsets(40, 40, 19)
+    assert lmo.tile_lds_bytes(1000, 20, 20) == (64 + 38) * (16 + 38) * 5 + 4 * (39 * 39 - 1)
+    assert lmo.tile_lds_bytes(1e6, 40, 40) == (64 + 78) * (16 + 78) * 5 + 4 * (79 * 79 - 1)
+    assert lmo.tile_lds_bytes(17, 3, 200) == (64 + 34) * (16 + 4) * 5 + 4 * (34 + 4 * 33)
+
+
+FAMILIES = list(lmc.cpu_families())
+
+
+@pytest.mark.parametrize("k", range(len(FAMILIES)), ids=[f"{f[0]}_r{f[2]:g}_t{f[3]}_{f[1].dtype}" for f in FAMILIES])
+def test_both_checkers_agree_on_the_kernel_test_inputs(k):
+    _, img, r, t = FAMILIES[k]
+    pts = lmo.local_max_raster(img, r, t)
+    assert lmo.check_greedy(img, r, pts, t)
+    assert pts.dtype == np.int64 and pts.shape == (len(pts), 2)
+
+
+def test_kernel_test_inputs_hold_what_they_are_for():
+    for dtype in (np.float32, np.float64):
+        img = lmc.signed_zeros(dtype)
+        pts, vals = lmo.candidates_by_priority(img, -1.0)
+        zeros = pts[vals == 0]
+        assert len(zeros) > 1000 and np.signbit(img[zeros[:, 1], zeros[:, 0]]).any()
+        assert (np.diff(zeros[:, 1] * img.shape[1] + zeros[:, 0]) > 0).all()       # the tied zeros: raster order
+        assert len(lmo.candidates_by_priority(img)[0]) == 7
+    img, pairs = lmc.ulp_pairs()
+    for r in lmc.EDGE_RADII:
+        kept = set(map(tuple, lmo.local_max_raster(img, r).tolist()))
+        for big, small, apart in pairs:
+            assert big in kept and ((small in kept) == (apart > r)), (big, small, r)
+    frame = lmc.chain_frame("boustrophedon")
+    assert lmo.candidate_mask(frame).sum() == 23 * 64 == np.count_nonzero(frame)
+    assert frame[1, 127] + 1 == frame[3, 127] and frame[3, 1] + 1 == frame[5, 1]
+    assert sorted(lmc.chain_frame("permutation")[1:-1:2, 1:-1:2].ravel()) == list(range(1, 23 * 64 + 1))
+    for img in (lmc.all_negative(np.float32), lmc.all_negative(np.int16)):
+        assert img.max() < 0 and len(lmo.local_max_raster(img, 5)) > 10
