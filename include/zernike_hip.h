@@ -933,6 +933,50 @@ int zk_rotate_rows(int device, const double* rows_host, int64_t n_rows, int n_po
 int zk_rotate_rows_dev(int device, const double* rows_dev, int64_t n_rows, int n_poly, const int32_t* n, const int32_t* m,
                        const double* angles_dev, double* out_dev, void* hip_stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * mtflearn.eels (reference eels/_baseline_correction.py): the baseline of every spectrum of a spectrum image.
+ *
+ * The operand is (outer, length, inner) of `dtype` (the five image formats, widened exactly to float64 on the device): `length`
+ * is the energy axis and each of the outer * inner other indices is one spectrum.  outer == 1 is the native energy-major
+ * layout (E, H, W); any other operand is transposed on the device on the way in and out.  baseline (and signal = data -
+ * baseline, NULL to skip) are float64 in the operand's layout; iterations (NULL to skip) is (outer, inner) int32.
+ *
+ *   zk_eels_snip  v = log(log(sqrt(y + 1) + 1) + 1); for pp = 1 .. niter: v[e] = min(v[e], (v[e + pp] + v[e - pp]) / 2) on
+ *                 pp <= e < length - pp, every pass from the values of the pass before (a pass with 2 pp >= length changes
+ *                 nothing); baseline = (exp(exp(v) - 1) - 1)^2 - 1.  float64 throughout, niter >= 0.
+ *   zk_eels_pls   (W + lam D^T D) z = W y, D the differences of `order` (1 .. 3), by a band LDL^T per spectrum:
+ *     ZK_EELS_WHITTAKER  one solve with the caller's weights: (length) float64 used for every spectrum
+ *                        (weights_per_spectrum == 0) or one weight per sample in the operand's layout (!= 0);
+ *     ZK_EELS_ALS        order 2; w = 1, then `itermax` solves with w = param (y > z), 1 - param (y < z), 0 (y == z);
+ *     ZK_EELS_ARPLS      order 2; w = 1; per solve d = y - z, m / s the mean / population standard deviation of d[d < 0],
+ *                        wt = 1 / (1 + exp(2 (d - (2 s - m)) / s)); stop when |w - wt| / |w| < param, else w = wt;
+ *     ZK_EELS_AIRPLS     w = 1; solve i = 1 ..: dssn = |sum d[d < 0]|; stop when dssn < 0.001 sum |y| or i == itermax; else
+ *                        w = 0 where d >= 0, exp(i |d| / dssn) where d < 0, and w[0] = w[length - 1] = exp(i max d[d < 0] / dssn).
+ *   iterations: the solves a spectrum took (ALS: itermax).  Not pinned: non-finite samples, SNIP input below -1, a spectrum
+ *   without a negative residual; every loop is bounded by itermax.
+ *
+ * One spectrum per lane, no atomics: a spectrum's numbers depend neither on its neighbours nor on the chunking, and the host
+ * and the _dev form give the same bits.  The scratch planes (order + 1 float64 per sample and a few more) are cut over the
+ * spectra to stay under zk_eels_set_chunk's bytes (0: the default, 1 GiB; at least 64 spectra per chunk).  Everything is
+ * checked before any device call; a refused argument is ZK_E_BADARG with a message.  The _dev variants take device pointers
+ * (the weights included), run on hip_stream and synchronise it once their scratch is released.
+ * ------------------------------------------------------------------------------------------------------ */
+#define ZK_EELS_WHITTAKER 0
+#define ZK_EELS_ALS       1
+#define ZK_EELS_ARPLS     2
+#define ZK_EELS_AIRPLS    3
+int zk_eels_snip(int device, const void* data_host, int dtype, int64_t outer, int64_t length, int64_t inner, int niter,
+                 double* baseline_host, double* signal_host);
+int zk_eels_snip_dev(int device, const void* data_dev, int dtype, int64_t outer, int64_t length, int64_t inner, int niter,
+                     double* baseline_dev, double* signal_dev, void* hip_stream);
+int zk_eels_pls(int device, const void* data_host, int dtype, int64_t outer, int64_t length, int64_t inner, int mode, int order,
+                double lam, double param, int itermax, const double* weights_host, int weights_per_spectrum,
+                double* baseline_host, double* signal_host, int32_t* iterations_host);
+int zk_eels_pls_dev(int device, const void* data_dev, int dtype, int64_t outer, int64_t length, int64_t inner, int mode, int order,
+                    double lam, double param, int itermax, const double* weights_dev, int weights_per_spectrum,
+                    double* baseline_dev, double* signal_dev, int32_t* iterations_dev, void* hip_stream);
+int zk_eels_set_chunk(int device, int64_t scratch_bytes);   /* cap of the scratch planes of the four calls above */
+
 /* Device memory for callers that have no allocator of their own (a NumPy / C user of the *_dev entry points). */
 int zk_device_malloc(int device, int64_t bytes, void** out_dev);
 int zk_device_free(int device, void* dev);

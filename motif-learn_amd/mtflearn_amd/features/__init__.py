@@ -10,7 +10,15 @@ from .consumers import pca
 from .keypoints import KeyPoints, com_refine_points, refine_points
 from .peaks import local_max
 
+
+def baseline_correction(y, niter=10):
+    """The reference's ``features/_window_size.py`` holds a second copy of SNIP under this name: an alias of
+    :func:`mtflearn_amd.eels.baseline_snip`."""
+    from ..eels import baseline_snip
+    return baseline_snip(y, niter=niter)
+
+
 __all__ = ["ZPs", "zmoments", "construct_rot_maps_matrix", "construct_complex_matrix",
            "construct_real_matrix", "nm2j", "nm2j_complex", "check_array1d",
            "estimate_patch_size", "radial_profile", "autocorrelation", "estimate_n_max", "estimate_n_max_from_patch", "pca",
-           "KeyPoints", "refine_points", "com_refine_points", "local_max"]
+           "KeyPoints", "refine_points", "com_refine_points", "local_max", "baseline_correction"]

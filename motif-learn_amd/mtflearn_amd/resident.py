@@ -558,6 +558,35 @@ def rotate_rows_device(rows, n, m, angles, out=None):
     return out
 
 
+def baseline_device(data, method="snip", axis=0, return_signal=False, return_info=False, **method_kw):
+    """:mod:`mtflearn_amd.eels` on a spectrum cube resident on the GPU (a torch tensor or a
+    :class:`~mtflearn_amd._native.DeviceArray` of any rank >= 1, float32 / float64 / uint8 / uint16 / int16; ``axis`` is the energy
+    axis).  ``method``: ``"snip"``, ``"als"``, ``"arpls"`` or ``"airpls"``, its parameters as keywords under the reference's names.
+    Returns the float64 baseline as a device array of the cube's kind -- bit for bit the host function's -- or
+    ``(signal, baseline)`` with ``return_signal``; with ``return_info`` the int32 solves per spectrum (``None`` for SNIP and a
+    constant for ALS) are appended, on the device as well.  Cube and results never cross to the host; with ``return_info`` the
+    counts are not read here, so no ``RuntimeWarning`` about ``itermax`` is raised.  Runs on torch's current stream, which is
+    synchronised before the call returns.  Like :func:`align_device` it is newer than ``__all__`` and is reached as
+    ``resident.baseline_device`` (or ``distributed.baseline_device``)."""
+    from .eels import _call, _check_length, _layout, _method_spec
+    spec = _method_spec(method, method_kw)
+    shape = tuple(int(v) for v in data.shape)
+    layout = _layout(shape, axis)
+    _check_length(layout[1], spec["order"])
+    data, code = _device.resident_frame(data, "baseline_device", ndim=None)
+    baseline = _empty_f64(shape, data)
+    signal = _empty_f64(shape, data) if return_signal else None
+    ax = int(axis) % len(shape)
+    iterations = None if spec.get("snip") or not return_info else _device.empty(shape[:ax] + shape[ax + 1:], np.int32, data)
+    ptr = lambda a: c_void_p(a.data_ptr()) if a is not None else None
+    _call(_native.load(), data.device.index, spec, ptr(data), code, layout, None, 0, ptr(baseline), ptr(signal), ptr(iterations),
+          stream=stream_ptr(data))
+    out = (signal, baseline) if return_signal else (baseline,)
+    if return_info:
+        out += (iterations,)
+    return out if len(out) > 1 else out[0]
+
+
 def denoise_svd_device(image, patch_size, n_components, extraction_step=None, return_s=False):
     """:func:`mtflearn_amd.denoise_svd` of a frame resident on the GPU (a torch tensor or a
     :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` of float32 / float64 / uint8 / uint16 / int16).  Returns the float64
