@@ -977,6 +977,46 @@ int zk_eels_pls_dev(int device, const void* data_dev, int dtype, int64_t outer, 
                     double* baseline_dev, double* signal_dev, int32_t* iterations_dev, void* hip_stream);
 int zk_eels_set_chunk(int device, int64_t scratch_bytes);   /* cap of the scratch planes of the four calls above */
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Scan-jitter resampling (reference denoise/_noise_models.py:28-57, apply_scan_noise), and the library's general
+ * interpolation primitive (csrc/zk_interp.h).
+ *
+ *   out[z, y, x] = S_z(y + dy[z, x], x + dx[z, y])
+ *
+ * S_z is the B-spline interpolant of `order` (0: nearest, floor(c + 0.5); 1; 3) of frame z ALONE, extended by `mode` as
+ * scipy.ndimage.map_coordinates extends it; the coordinate sums are formed in float64 and so is everything after them.  The
+ * stack is (Z, H, W) of `dtype`; the result is float32 for ZK_F32, float64 for every other type (the integer formats are widened
+ * exactly).  dx is (Z, H) and dy is (Z, W), float64; no coordinate array exists on either side.
+ *   ZK_RESAMPLE_REFLECT        d c b a | a b c d | d c b a      ZK_RESAMPLE_GRID_WRAP       a b c d | a b c d | a b c d
+ *   ZK_RESAMPLE_MIRROR         d c b | a b c d | c b a          ZK_RESAMPLE_GRID_CONSTANT   0 0 0 0 | a b c d | 0 0 0 0
+ *   ZK_RESAMPLE_NEAREST        a a a a | a b c d | d d d d      ZK_RESAMPLE_CONSTANT        a coordinate outside [0, n - 1] on
+ *                                                                                           either axis gives 0 as a whole
+ * Taps are folded in the modulo form, so a shift of any number of image sizes is right.  Order 3 is offered for REFLECT,
+ * MIRROR and GRID_WRAP: its prefilter (pole sqrt(3) - 2, gain 6 per axis, rows then columns) starts each segment from 32
+ * samples of the extended signal, |pole|^32 < 1 ulp, i.e. it is the exact interpolant on an axis of any length -- where the
+ * reference's 3-D call differs (it also filters along z and, for REFLECT, starts from a series cut at the axis length).
+ *
+ * Frames are independent: a frame alone, in a stack, in another run length, and the host and _dev forms give the same bits.
+ * Order 3 needs two float64 planes per frame in flight (16 H W bytes).  zk_scan_resample streams whole frames through a staging
+ * ring, input + output + scratch of one run staying under zk_scan_resample_set_chunk's bytes (0: the default, 256 MiB; at
+ * least one frame).  zk_scan_resample_dev takes device pointers and runs on hip_stream; with scratch_dev (at least one frame's
+ * planes; runs are sized to scratch_bytes) or below order 3 it allocates nothing and does not synchronise, otherwise it takes
+ * its planes under the same cap and synchronises the stream before it releases them.  Everything is checked before any device
+ * call; a refused argument is ZK_E_BADARG with a message.  Not pinned: non-finite samples or shifts.
+ * ------------------------------------------------------------------------------------------------------ */
+#define ZK_RESAMPLE_REFLECT       0
+#define ZK_RESAMPLE_MIRROR        1
+#define ZK_RESAMPLE_NEAREST       2
+#define ZK_RESAMPLE_GRID_WRAP     3
+#define ZK_RESAMPLE_GRID_CONSTANT 4
+#define ZK_RESAMPLE_CONSTANT      5
+int zk_scan_resample(int device, const void* stack_host, int dtype, int64_t Z, int64_t H, int64_t W, const double* dx_host,
+                     const double* dy_host, int order, int mode, void* out_host);
+int zk_scan_resample_dev(int device, const void* stack_dev, int dtype, int64_t Z, int64_t H, int64_t W, const double* dx_dev,
+                         const double* dy_dev, int order, int mode, void* out_dev, void* scratch_dev, int64_t scratch_bytes,
+                         void* hip_stream);
+int zk_scan_resample_set_chunk(int device, int64_t budget_bytes);
+
 /* Device memory for callers that have no allocator of their own (a NumPy / C user of the *_dev entry points). */
 int zk_device_malloc(int device, int64_t bytes, void** out_dev);
 int zk_device_free(int device, void* dev);

@@ -3,6 +3,7 @@
 
   notebook 2 (batch):  key points -> patches -> ZPs.fit_transform(patches) -> rotation-invariant |Z_nm| -> rot_maps
   notebook 3 (dense):  ZPs.fit_transform(frame) -> rot_maps / mirror_map / |Z_nm| maps
+  jittered series:     rendered frames -> apply_scan_noise (scan distortion) -> denoise_svd, resident
   resident chain:      lattice rendered on the device -> denoise -> background removal -> local maxima -> moments at them
   refined chain:       the same key points -> sub-pixel centroids -> bond length -> Voronoi bonds -> polygons, all resident
   motifs:              k-means centres of the key-point moments -> ZPs.inverse_transform -> the motif each class stands for
@@ -72,6 +73,21 @@ def main():
     inner = keep[(keep.min(axis=1) >= 2 * size) & (keep.max(axis=1) < 1024 - 2 * size)]
     dist = np.hypot(inner[:, None, 0] - sites[None, :, 0], inner[:, None, 1] - sites[None, :, 1]).min(axis=1)
     print(f"         {len(inner)} interior peaks, farthest from a lattice site: {dist.max():.2f} px")
+
+    # ---- a jittered series of the same lattice: render -> scan noise -> denoise, the frames never on the host ------------
+    from mtflearn_amd.denoise import DenoiseSVD, _jitter, apply_scan_noise
+    from mtflearn_amd.resident import scan_noise_device
+    t = time.perf_counter()
+    frames = _native.DeviceArray((4, 1024, 1024), np.float32)             # the rendered frame is float32
+    for k in range(4):                                                     # four exposures of one lattice
+        _native.check(_native.load().zk_device_copy(0, frames[k].data_ptr(), dev.data_ptr(), dev.nbytes, 3), "zk_device_copy")
+    dx, dy = _jitter(7, frames.shape, 1.0, 0.3)                            # the reference's draws: Z (H + W) numbers go up
+    jittered = scan_noise_device(frames, _native.DeviceArray.from_numpy(dx), _native.DeviceArray.from_numpy(dy), order=3)
+    cleaned = [denoise_svd_device(jittered[k], size, n_components=8) for k in range(4)]
+    print(f"jitter : 4 frames -> scan noise (order 3) -> denoise_svd in {1e3 * (time.perf_counter() - t):.1f} ms, all resident")
+    host = apply_scan_noise(frames.numpy(), jx=1.0, jy=0.3, seed=7, order=3)   # reference: apply_scan_noise(frames, 1.0, 0.3, 7, 3)
+    print("         host call == resident call:", np.array_equal(host, jittered.numpy()),
+          "; DenoiseSVD on the host copy:", DenoiseSVD(host[0], 8, size, None).run().shape)
 
     # ---- the refined chain: key points -> centroids -> estimate_d -> bonds -> polygons, nothing but scalars on the host ------
     from mtflearn_amd.distributed import estimate_d_device, find_regions_device, refine_points_device, vnn_graph_device

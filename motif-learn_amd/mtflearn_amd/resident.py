@@ -587,6 +587,35 @@ def baseline_device(data, method="snip", axis=0, return_signal=False, return_inf
     return out if len(out) > 1 else out[0]
 
 
+def scan_noise_device(images, dx, dy, order=1, mode="reflect", out=None):
+    """The resampling of :func:`mtflearn_amd.denoise.apply_scan_noise` on a stack resident on the GPU: ``images`` ``(Z, H, W)``
+    float32 or float64, ``dx`` ``(Z, H)`` and ``dy`` ``(Z, W)`` float64 shifts, all torch tensors or all
+    :class:`~mtflearn_amd._native.DeviceArray` on one device.  Returns ``out[z, y, x] = S_z(y + dy[z, x], x + dx[z, y])`` in the
+    stack's dtype as a device array of its kind (``out``: a contiguous array of that shape and dtype to write into) -- bit for
+    bit the host function's numbers for the same shifts.  Runs on torch's current stream without a host copy; at order 3 the
+    stream is synchronised before the call returns (the two float64 scratch planes per frame are released then).  Like
+    :func:`baseline_device` it is newer than ``__all__`` and is reached as ``resident.scan_noise_device`` (or
+    ``distributed.scan_noise_device``)."""
+    from .denoise import _check_scan_order_mode, _check_scan_shape
+    order, mode_code = _check_scan_order_mode(order, mode)
+    z, h, w = shape = _check_scan_shape(tuple(images.shape))
+    images, code = _device.resident_frame(images, "scan_noise_device", floats_only=True, ndim=3)
+
+    def companion(array, name, want, dtype):
+        if (not getattr(array, "is_cuda", False) or not array.is_contiguous() or tuple(array.shape) != want
+                or _device.np_dtype(array) != dtype or is_native(array) != is_native(images) or array.device.index != images.device.index):
+            raise ValueError(f"{name} must be a contiguous {want} {np.dtype(dtype).name} array of the stack's kind on its device")
+        return array
+
+    companion(dx, "dx", (z, h), np.float64)
+    companion(dy, "dy", (z, w), np.float64)
+    out = _device.empty(shape, _device.np_dtype(images), images) if out is None else companion(out, "out", shape, _device.np_dtype(images))
+    ptr = lambda a: c_void_p(a.data_ptr())
+    _native.check(_native.load().zk_scan_resample_dev(images.device.index, ptr(images), code, z, h, w, ptr(dx), ptr(dy), order, mode_code,
+                                                      ptr(out), None, 0, c_void_p(stream_ptr(images))), "zk_scan_resample_dev")
+    return out
+
+
 def denoise_svd_device(image, patch_size, n_components, extraction_step=None, return_s=False):
     """:func:`mtflearn_amd.denoise_svd` of a frame resident on the GPU (a torch tensor or a
     :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` of float32 / float64 / uint8 / uint16 / int16).  Returns the float64
