@@ -1017,6 +1017,40 @@ int zk_scan_resample_dev(int device, const void* stack_dev, int dtype, int64_t Z
                          void* hip_stream);
 int zk_scan_resample_set_chunk(int device, int64_t budget_bytes);
 
+/* ------------------------------------------------------------------------------------------------------
+ * mtflearn.datasets.TMDImageSimulator (datasets/_tmd_simulator.py): a batch of float32 frames (batch, height, width), each the
+ * sum of its layers (species) in the order given.  Layer l belongs to frame layer_frame[l] (the layers of a frame are
+ * consecutive: layer_frame does not decrease; a frame without layers is zero), owns the points
+ * [point_offsets[l], point_offsets[l + 1]) of the (n, 3) float64 array of (x, y, scale), and has an amplitude and a half kernel
+ * w[0 .. r] = weights[weight_offsets[l] .. weight_offsets[l + 1]), centre first (r >= 0, at most 960).
+ *
+ *   delta image     float32: the scale of every point (rounded to float32) added at (rint(y), rint(x)) -- default rounding
+ *                   mode, as np.round -- in ascending point index with a float32 rounding per add, as np.add.at; a point
+ *                   whose pixel is off the frame is dropped.
+ *   blur            the column pass (axis 0), then the row pass, each in float64 in SciPy's order of operations for a
+ *                   symmetric kernel: t = c w[0], then t += (left + right) w[j] for j = r .. 1.
+ *     ZK_TMD_FFT        zeros outside the frame, a float64 intermediate, frame = float32(float64(frame) + amplitude * t):
+ *                       the exact fftconvolve(delta, amplitude * outer(g, g), 'same') for g[j] = w[|j|].
+ *     ZK_TMD_GAUSSIAN   'reflect' (d c b a | a b c d | d c b a, folded again when r >= n), each pass stored as float32,
+ *                       frame = frame + float32(amplitude) * t in float32: amplitude * scipy.ndimage.gaussian_filter(delta).
+ *
+ * masks, when not NULL, receives the delta images as (n_layers, height, width) float32.  With weights and weight_offsets both
+ * NULL there is no blur: only the masks are written and frames may be NULL.  dtype is ZK_F32.  No floating-point atomics, and
+ * a frame's result depends on its own layers only: alone, in a batch, from either entry point and on a second run the bits
+ * are the same.  The metadata and the points are host arrays in both forms; zk_tmd_render_dev takes frames and masks on the
+ * device, runs on hip_stream and synchronises it before it returns (its staging goes with the call).  Everything is checked
+ * before any device call; a refused argument is ZK_E_BADARG with a message.
+ * ------------------------------------------------------------------------------------------------------ */
+#define ZK_TMD_FFT      0
+#define ZK_TMD_GAUSSIAN 1
+int zk_tmd_render(int device, void* frames_host, void* masks_host, int dtype, int64_t batch, int64_t height, int64_t width,
+                  int64_t n_layers, const int32_t* layer_frame_host, const int64_t* point_offsets_host, const double* points_host,
+                  const double* amplitudes_host, const int64_t* weight_offsets_host, const double* weights_host, int mode);
+int zk_tmd_render_dev(int device, void* frames_dev, void* masks_dev, int dtype, int64_t batch, int64_t height, int64_t width,
+                      int64_t n_layers, const int32_t* layer_frame_host, const int64_t* point_offsets_host, const double* points_host,
+                      const double* amplitudes_host, const int64_t* weight_offsets_host, const double* weights_host, int mode,
+                      void* hip_stream);
+
 /* Device memory for callers that have no allocator of their own (a NumPy / C user of the *_dev entry points). */
 int zk_device_malloc(int device, int64_t bytes, void** out_dev);
 int zk_device_free(int device, void* dev);

@@ -4,6 +4,7 @@
   notebook 2 (batch):  key points -> patches -> ZPs.fit_transform(patches) -> rotation-invariant |Z_nm| -> rot_maps
   notebook 3 (dense):  ZPs.fit_transform(frame) -> rot_maps / mirror_map / |Z_nm| maps
   jittered series:     rendered frames -> apply_scan_noise (scan distortion) -> denoise_svd, resident
+  defect frames:       TMDImageSimulator stack in one call -> scan noise -> Poisson noise -> local_max, against pts / labels
   resident chain:      lattice rendered on the device -> denoise -> background removal -> local maxima -> moments at them
   refined chain:       the same key points -> sub-pixel centroids -> bond length -> Voronoi bonds -> polygons, all resident
   motifs:              k-means centres of the key-point moments -> ZPs.inverse_transform -> the motif each class stands for
@@ -88,6 +89,32 @@ def main():
     host = apply_scan_noise(frames.numpy(), jx=1.0, jy=0.3, seed=7, order=3)   # reference: apply_scan_noise(frames, 1.0, 0.3, 7, 3)
     print("         host call == resident call:", np.array_equal(host, jittered.numpy()),
           "; DenoiseSVD on the host copy:", DenoiseSVD(host[0], 8, size, None).run().shape)
+
+    # ---- labelled defect frames: simulators -> one device call -> scan noise -> shot noise -> key points against the labels ----
+    from mtflearn_amd.datasets import TMDImageSimulator, apply_poisson_noise  # reference: from mtflearn.datasets import ...
+    from mtflearn_amd.resident import tmd_frames_device
+    t = time.perf_counter()
+    sims = []
+    for k, theta in enumerate((0.0, 10.0, 20.0, 30.0)):
+        sim = TMDImageSimulator(size=(512, 512), a=30, theta=theta)
+        sim.add_random_vacancies('X', num_single=6, num_double=6, seed=k)
+        sim.add_random_dopants('TM', num_dopants=8, seed=k)
+        sims.append(sim)
+    stack = tmd_frames_device(sims, consistent_defects=True)               # (4, 512, 512) float32, resident; labels in sims[k].pts / .lbs
+    dx, dy = _jitter(3, stack.shape, 0.4, 0.2)
+    shaken = scan_noise_device(stack, _native.DeviceArray.from_numpy(dx), _native.DeviceArray.from_numpy(dy), order=1)
+    noisy = apply_poisson_noise(shaken.numpy(), counts_per_pixel=400, seed=1)  # the draw is NumPy's: host
+    found = local_max_device(_native.DeviceArray.from_numpy(noisy[0]), 6.0, 0.15).numpy()
+    print(f"defects: 4 simulators -> tmd_frames_device -> scan noise -> Poisson -> local_max in {1e3 * (time.perf_counter() - t):.1f} ms")
+    sim = sims[0]
+    names = sorted(set(sim.labels.tolist()))                               # lbs indexes the sorted labels of the whole lattice
+    inner = (sim.pts.min(axis=1) >= 8) & (sim.pts.max(axis=1) < 504)
+    near = np.hypot(sim.pts[inner, None, 0] - found[None, :, 0], sim.pts[inner, None, 1] - found[None, :, 1]).min(axis=1)
+    for name in names:
+        of_kind = sim.labels[inner] == name
+        print(f"         frame 0, {name:>2}: {int(of_kind.sum()):4d} interior sites, {int((near[of_kind] <= 2.0).sum()):4d} with a peak within 2 px"
+              + ("  (a double vacancy leaves nothing to find)" if name == "v2" else ""))
+    print("         defect counts of frame 0:", {str(k): int(v) for k, v in sim.get_defect_counts().items()}, "; lbs:", np.bincount(sim.lbs).tolist())
 
     # ---- the refined chain: key points -> centroids -> estimate_d -> bonds -> polygons, nothing but scalars on the host ------
     from mtflearn_amd.distributed import estimate_d_device, find_regions_device, refine_points_device, vnn_graph_device

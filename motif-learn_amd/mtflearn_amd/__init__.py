@@ -7,7 +7,8 @@
 ``remove_background_*`` and their parameter picker; ``mtflearn_amd.denoise``: ``denoise_svd`` / ``DenoiseSVD`` /
 ``denoise_svd_memory_view``, the reference's other two top-level names; ``mtflearn_amd.utils``: ``normalize_image`` /
 ``normalize_image_robust`` / ``standardize_image`` / ``percentile_clip`` / ``value_clip``; ``mtflearn_amd.datasets``:
-``HoneyCombLattice`` / ``add_tapered_gaussian`` / ``get_zps_test_image`` / ``get_zps_test_patches`` and the noise models;
+``HoneyCombLattice`` / ``add_tapered_gaussian`` / ``get_zps_test_image`` / ``get_zps_test_patches``, the noise models and
+``TMDImageSimulator``, the labelled defect frames;
 ``mtflearn_amd.graph``: ``find_regions`` / ``LatticeGraph`` / ``MotifsGraph``, the polygons of a lattice graph;
 ``mtflearn_amd.eels``: ``baseline_als`` / ``baseline_snip`` / ``baseline_arpls`` / ``baseline_airpls`` / ``WhittakerSmooth`` /
 ``remove_baseline`` over whole spectrum cubes); see DESIGN.md.

@@ -25,6 +25,7 @@ THRESHOLD_LI, THRESHOLD_OTSU = 0, 1                                # zk_com_refi
 ALIGN_DISTANCE, ALIGN_COSINE = 0, 1                                # zk_align_rows keys
 ALIGN_KEYS = {"distance": ALIGN_DISTANCE, "cosine": ALIGN_COSINE}
 EELS_WHITTAKER, EELS_ALS, EELS_ARPLS, EELS_AIRPLS = 0, 1, 2, 3      # zk_eels_pls modes
+TMD_FFT, TMD_GAUSSIAN = 0, 1                                       # zk_tmd_render modes
 RESAMPLE_MODES = {"reflect": 0, "mirror": 1, "nearest": 2, "grid-wrap": 3, "grid-constant": 4, "constant": 5}   # ZK_RESAMPLE_*
 KNN_RANGES, KNN_HIST, KNN_SIDES, KNN_GAPS = 0, 1, 2, 3             # zk_knn_stats ops
 PATH_AUTO, PATH_GENERIC, PATH_FOLDED, PATH_SEPARABLE, PATH_STREAM, PATH_DIRECT = 0, 1, 2, 3, 4, 5
@@ -230,6 +231,10 @@ SYMBOLS = {
     "zk_scan_resample_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                      c_void_p, c_int64, c_void_p]),
     "zk_scan_resample_set_chunk": (c_int, [c_int, c_int64]),
+    "zk_tmd_render": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_int]),
+    "zk_tmd_render_dev": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "zk_device_malloc": (c_int, [c_int, c_int64, POINTER(c_void_p)]),
     "zk_device_free": (c_int, [c_int, c_void_p]),
     "zk_device_copy": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int]),

@@ -7,10 +7,12 @@ The only way to a frame without microscope data, under the reference's names, si
 * ``get_zps_test_image`` / ``get_zps_test_patches`` (``_zps_test_data.py``);
 * ``generate_data_gn``                            (``_generate_data_gn.py``): n-fold blob patterns;
 * ``apply_poisson_noise`` / ``add_gaussian_noise`` / ``apply_poisson_gaussian_noise`` / ``estimate_counts_per_pixel_mle``
-  (``_noise_models.py``).
+  (``_noise_models.py``);
+* ``TMDImageSimulator``                           (``_tmd_simulator.py``): a rotated two-species lattice with labelled single and
+  double vacancies and dopants; per species a delta image and a blur (see below).
 
-Every pixel is drawn by ``zk_render_gaussians`` (``csrc/zk_datasets.hip``): the reference's float64 expressions, one rounding
-per operation, and -- because the reference adds point after point and a float32 frame rounds at every add -- every pixel's
+Every pixel of the first four is drawn by ``zk_render_gaussians`` (``csrc/zk_datasets.hip``): the reference's float64
+expressions, one rounding per operation, and -- because the reference adds point after point and a float32 frame rounds at every add -- every pixel's
 contributions in ascending point index with that same rounding.  What differs from NumPy is the device's ``exp`` (and
 ``t * t * t`` for ``t ** 3``): a float64 frame agrees to ``1e-12`` of its maximum, a float32 frame to one float32 spacing per
 contribution to the pixel.  Where the values make every contribution exact the result is the reference's bit for bit, and
@@ -22,18 +24,34 @@ The lattice coordinates are made on the host as whole arrays, with the reference
 The noise models are host code: the draw is NumPy's (``Generator.poisson`` / ``Generator.normal``) and is the whole cost, so
 there is nothing for the device to do that would still give the reference's noise for a seed.
 
+``TMDImageSimulator.simulate`` is ``zk_tmd_render`` (``csrc/zk_tmd.hip``).  The delta image of a species is NumPy's
+``np.add.at`` -- several atoms on one pixel are added in ascending index with a float32 rounding per add -- and is the
+reference's bit for bit.  With ``use_fft=False`` the blur is ``scipy.ndimage.gaussian_filter`` restated operation by operation
+(axis 0 then axis 1 in float64, each pass stored as float32, ``A *`` and the sum over species in float32): the reference's
+frame bit for bit for up to two species.  With ``use_fft=True`` it is the exact separable convolution the reference's
+``fftconvolve`` approximates in single precision, each species added as ``float32(float64(total) + blurred)``: half a float32
+spacing per species from the exact sum, where the reference is about ``1.5e-7`` of the peak away from it.  Its lattice, labels
+and defect draws are host code and the reference's numbers, bit for bit and in its order.
+
 Deviations from the reference:
 
 * points must be finite (the reference fails on ``int(nan)``), ``r_factor`` must be positive, and ``img`` must be float32 or
   float64;
-* the pixels of a point's box outside its disc, to which the reference adds ``0.0``, are left alone (a ``-0.0`` there stays).
+* the pixels of a point's box outside its disc, to which the reference adds ``0.0``, are left alone (a ``-0.0`` there stays);
+* ``TMDImageSimulator`` adds its species in order of first appearance in ``basis``; the reference walks a ``set``, whose order
+  changes from process to process (the same frame for up to two species, not for three);
+* ``TMDImageSimulator.simulate`` takes a keyword-only ``consistent_defects=False``: the reference uses a stored global site
+  index as an index into the species' own array, so the image dims another atom than the labels mark; ``True`` dims the
+  labelled one.  The default is the reference's behaviour;
+* ``TMDImageSimulator`` needs finite positions, ``species_params`` convertible with ``float()``, and kernels of radius 960 at
+  the most (``sigma`` up to 240 with ``use_fft=False``, 320 with ``use_fft=True``); ``matplotlib`` is imported by ``plot`` only.
 
-Left out: ``TMDImageSimulator`` and ``PerovskitesImageSimulator`` (another renderer: a delta image and a convolution), the
-lattice-constant tables, and ``generate_two_blobs``.  :mod:`mtflearn_amd.synthetic` is the project's own older host generator
+Left out: ``PerovskitesImageSimulator`` (an empty constructor in the reference), the lattice-constant tables, and
+``generate_two_blobs``.  :mod:`mtflearn_amd.synthetic` is the project's own older host generator
 and stays as it is.
 
 There is no CPU fallback: without a HIP device the rendering functions raise ``RuntimeError``.  Frames that should stay on the
-GPU come from ``render_gaussians_device`` / ``honeycomb_image_device`` of :mod:`mtflearn_amd.resident`.
+GPU come from ``render_gaussians_device`` / ``honeycomb_image_device`` / ``tmd_frames_device`` of :mod:`mtflearn_amd.resident`.
 """
 from __future__ import annotations
 
@@ -54,6 +72,7 @@ __all__ = [
     "add_gaussian_noise",
     "apply_poisson_gaussian_noise",
     "estimate_counts_per_pixel_mle",
+    "TMDImageSimulator",
 ]
 
 
@@ -323,6 +342,286 @@ class HoneyCombLattice:
         from .resident import honeycomb_image_device
         return honeycomb_image_device(self, sigma=sigma, intensity_A=intensity_A, intensity_B=intensity_B,
                                       normalize=normalize).numpy()
+
+
+# ----------------------------------------------------------------------------------------------- labelled defect frames
+def _tmd_render_args(layers, batch, shape, blur, use_fft):
+    """The arguments of ``zk_tmd_render`` after the two buffers, and the arrays they point into (to be kept alive by the
+    caller).  ``layers``: ``(frame, points (n, 3) float64 of (x, y, scale), amplitude, half kernel)`` in frame order."""
+    h, w = (int(v) for v in shape)
+    frame_of = np.ascontiguousarray([layer[0] for layer in layers], dtype=np.int32)
+    points = np.ascontiguousarray(np.concatenate([layer[1] for layer in layers]) if layers else np.zeros((0, 3)), dtype=np.float64)
+    point_offsets = np.concatenate([[0], np.cumsum([len(layer[1]) for layer in layers])]).astype(np.int64)
+    keep = [frame_of, points, point_offsets]
+    if blur:
+        amps = np.ascontiguousarray([layer[2] for layer in layers], dtype=np.float64)
+        weights = np.ascontiguousarray(np.concatenate([layer[3] for layer in layers]), dtype=np.float64)
+        weight_offsets = np.concatenate([[0], np.cumsum([len(layer[3]) for layer in layers])]).astype(np.int64)
+        keep += [amps, weights, weight_offsets]
+        tail = (_ptr(amps), _ptr(weight_offsets), _ptr(weights))
+    else:
+        tail = (None, None, None)
+    args = (_native.ZK_F32, int(batch), h, w, len(layers), _ptr(frame_of), _ptr(point_offsets), _ptr(points), *tail,
+            _native.TMD_FFT if use_fft else _native.TMD_GAUSSIAN)
+    return args, keep
+
+
+def _tmd_render_host(frames, masks, layers, blur, use_fft):
+    """``zk_tmd_render`` into C-contiguous float32 host arrays: ``frames`` ``(B, H, W)`` (None without blur) and ``masks``
+    ``(len(layers), H, W)`` (or None)."""
+    lib = _native.load()
+    _native.require_device()
+    shape = (frames if frames is not None else masks).shape
+    batch = shape[0] if frames is not None else max(layer[0] for layer in layers) + 1
+    args, keep = _tmd_render_args(layers, batch, shape[-2:], blur, use_fft)
+    _native.check(lib.zk_tmd_render(_native.default_device(), _ptr(frames), _ptr(masks), *args), "zk_tmd_render")
+    del keep
+
+
+def _tmd_render_device(frames, masks, layers, blur, use_fft):
+    """``zk_tmd_render_dev`` into resident float32 arrays (DeviceArrays or torch tensors) of the same shapes."""
+    first = frames if frames is not None else masks
+    batch = frames.shape[0] if frames is not None else max(layer[0] for layer in layers) + 1
+    args, keep = _tmd_render_args(layers, batch, tuple(first.shape)[-2:], blur, use_fft)
+    dev_ptr = lambda a: None if a is None else c_void_p(a.data_ptr())
+    _native.check(_native.load().zk_tmd_render_dev(first.device.index, dev_ptr(frames), dev_ptr(masks), *args,
+                                                   c_void_p(_device.stream_ptr(first))), "zk_tmd_render_dev")
+    del keep
+
+
+def _on_frame(points, shape):
+    """The rows of ``(n, 3)`` points whose pixel ``(rint(y), rint(x))`` is on the ``(H, W)`` frame, in order: the device drops
+    the others by the same predicate, so leaving them on the host changes no pixel."""
+    h, w = shape
+    x, y = np.rint(points[:, 0]), np.rint(points[:, 1])
+    return points[(x >= 0) & (x < w) & (y >= 0) & (y < h)]
+
+
+class TMDImageSimulator:
+    """
+    Atomic-resolution frames of a transition-metal dichalcogenide monolayer with labelled point defects: the reference's
+    ``TMDImageSimulator`` (``_tmd_simulator.py``), its constructor, attributes and methods.
+
+    Parameters
+    ----------
+    size : (height, width) of the frame in pixels.
+    a : lattice constant in pixels.
+    theta : rotation of the lattice in degrees.
+    species_params : ``{label: {'sigma': ..., 'A': ...}}``, the Gaussian of each species (a species without an entry gets
+        ``sigma = 2.0, A = 1.0``).
+    basis : ``[(dx, dy, label), ...]`` in fractions of the primitive vectors.
+    use_fft : ``True``: every species' delta image is convolved with a ``int(6 sigma) | 1`` square Gaussian window, zeros
+        outside the frame (the reference's ``fftconvolve``); ``False``: ``A * scipy.ndimage.gaussian_filter(delta, sigma)``.
+
+    The lattice, the labels and the defect draws are host code and the reference's numbers; ``simulate`` renders on the GPU
+    (:func:`mtflearn_amd.resident.tmd_frames_device` renders many simulators in one call and leaves the stack there).
+    """
+
+    def __init__(self, size=(512, 512), a=30, theta=0.0, species_params=None, basis=None, use_fft=True):
+        self.size = size
+        self.a = a
+        self.theta = theta
+        self.use_fft = use_fft
+        self.species_params = species_params or {'TM': {'sigma': 2.0, 'A': 1.0}, 'X': {'sigma': 1.5, 'A': 0.6}}
+        self.basis = basis or [(0.0, 0.0, 'TM'), (1 / 3, 1 / 3, 'X')]
+        self.vacancies = []
+        self.dopants = []
+        self._cached_coords = None
+        self.pts_all = None
+        self.pts = None
+        self.labels = None
+        self.lbs = None
+        self.filtered_indices = {}
+
+    def rotation_matrix(self):
+        theta = np.deg2rad(self.theta)
+        return np.array([[np.cos(theta), -np.sin(theta)], [np.sin(theta), np.cos(theta)]])
+
+    def _species(self):
+        """The species in order of first appearance in ``basis`` (the reference walks an unordered set)."""
+        return list(dict.fromkeys(b[2] for b in self.basis))
+
+    def generate_lattice(self):
+        """All sites, rotated: the reference's loops over ``(i, j)`` and the basis as whole arrays, ``i`` the slow index and
+        the basis entry the fastest, every element through the same operations in the same order.  Sets ``pts_all``, ``pts``,
+        ``labels``, ``lbs``, ``filtered_indices`` and returns ``{label: (n, 2) coordinates}``."""
+        self.defect_label_map = {}
+        a1 = self.a * np.array([1, 0])
+        a2 = self.a * np.array([0.5, np.sqrt(3) / 2])
+        R = self.rotation_matrix()
+        height, width = self.size
+        nx = int(width // self.a * 2) + 4
+        ny = int(height // (self.a * np.sqrt(3) / 2) * 2) + 4
+
+        i = np.repeat(np.arange(-nx, nx), 2 * ny)[:, None]
+        j = np.tile(np.arange(-ny, ny), 2 * nx)[:, None]
+        base = i * a1 + j * a2
+        d1 = np.array([dx * a1 for dx, _, _ in self.basis], dtype=np.float64)
+        d2 = np.array([dy * a2 for _, dy, _ in self.basis], dtype=np.float64)
+        pos = ((base[:, None, :] + d1[None]) + d2[None]).reshape(-1, 2)
+        # the one whole-array form found equal, bit for bit, to the reference's `R @ pos` per site
+        self.pts_all = np.ascontiguousarray(np.matmul(R, pos[:, :, None])[:, :, 0])
+
+        site_labels = np.tile(np.array([b[2] for b in self.basis]), len(base))
+        species = self._species()
+        index_of = {label: np.flatnonzero(site_labels == label) for label in species}
+        coords = {label: self.pts_all[index_of[label]] for label in species}
+        self._cached_coords = coords
+        self._index_of = index_of
+
+        mask = ((self.pts_all[:, 0] >= 0) & (self.pts_all[:, 0] < width) &
+                (self.pts_all[:, 1] >= 0) & (self.pts_all[:, 1] < height))
+        self.pts = self.pts_all[mask]
+
+        defect_labels = site_labels.copy()              # its string width is the longest species label's, as the reference's
+        for vac_label, vac_idx, scale in self.vacancies:
+            if scale == 0.5:
+                defect_labels[vac_idx] = 'v1'
+            elif scale == 0.0:
+                defect_labels[vac_idx] = 'v2'
+        for dop_label, dop_idx, dop_scale in self.dopants:
+            defect_labels[dop_idx] = 'D'
+        self.labels = defect_labels[mask]
+        _, inverse = np.unique(defect_labels, return_inverse=True)
+        self.lbs = inverse.reshape(-1)[mask].astype(int)
+
+        for label in species:
+            idx = index_of[label]
+            self.filtered_indices[label] = idx[mask[idx]].tolist()
+        return coords
+
+    def add_single_vacancy(self, label='X', index=None):
+        if index is not None:
+            self.vacancies.append((label, index, 0.5))
+
+    def add_double_vacancy(self, label='X', indices=None):
+        if indices is not None and len(indices) >= 1:
+            self.vacancies.append((label, indices[0], 0.0))
+
+    def add_random_vacancies(self, label='X', num_single=0, num_double=0, seed=None):
+        if self._cached_coords is None:
+            self.generate_lattice()
+        indices = self.filtered_indices.get(label, [])
+        if len(indices) == 0:
+            return
+        rng = np.random.default_rng(seed)
+        rng.shuffle(indices)                            # the list held in filtered_indices, in place
+        selected = 0
+        for _ in range(num_single):
+            if selected >= len(indices):
+                break
+            self.add_single_vacancy(label, indices[selected])
+            selected += 1
+        for _ in range(num_double):
+            if selected >= len(indices):
+                break
+            self.add_double_vacancy(label, [indices[selected]])
+            selected += 1
+
+    def add_random_dopants(self, label='TM', num_dopants=0, dopant_intensity=0.8, seed=None):
+        if self._cached_coords is None:
+            self.generate_lattice()
+        indices = self.filtered_indices.get(label, [])
+        if len(indices) == 0:
+            return
+        rng = np.random.default_rng(seed)
+        dopant_indices = rng.choice(indices, size=min(num_dopants, len(indices)), replace=False)
+        for idx in dopant_indices:
+            self.dopants.append((label, idx, dopant_intensity))
+
+    def place_atoms_delta(self, positions, scales):
+        """The float32 delta image of ``size``: ``scales[k]`` added at the rounded ``positions[k] = (x, y)``, in ascending
+        ``k``; on the GPU, through the renderer's entry point without a blur."""
+        positions = np.asarray(positions, dtype=np.float64).reshape(-1, 2)
+        scales = np.asarray(scales).astype(np.float32).astype(np.float64).reshape(-1)
+        points = np.column_stack([positions, scales[:len(positions)]])
+        if not np.isfinite(points).all():
+            raise ValueError("positions and scales must be finite")
+        h, w = (int(v) for v in self.size)
+        img = np.zeros((1, h, w), dtype=np.float32)
+        if img.size:
+            _tmd_render_host(None, img, [(0, _on_frame(points, (h, w)), 0.0, None)], False, True)
+        return img[0]
+
+    def gaussian_kernel(self, size, sigma, A):
+        r = np.arange(-size // 2 + 1, size // 2 + 1)
+        X, Y = np.meshgrid(r, r)
+        return A * np.exp(-(X ** 2 + Y ** 2) / (2 * sigma ** 2))
+
+    def _scales(self, label, n_atoms, consistent_defects):
+        """The float32 scales of a species' atoms.  The reference uses a stored *global* site index as an index into the
+        species' own array; ``consistent_defects`` maps it to the site's place in that array instead."""
+        scales = np.ones(n_atoms, dtype=np.float32)
+        own = self._index_of[label]
+
+        def place(index):
+            if not consistent_defects:
+                return index
+            at = int(np.searchsorted(own, index))
+            return at if at < len(own) and own[at] == index else -1
+
+        for vac_label, vac_idx, scale in self.vacancies:
+            if vac_label == label:
+                at = place(vac_idx)
+                if 0 <= at < n_atoms:
+                    scales[at] = scale
+        for dop_label, dop_idx, dop_scale in self.dopants:
+            if dop_label == label:
+                at = place(dop_idx)
+                if 0 <= at < n_atoms:
+                    scales[at] = dop_scale
+        return scales
+
+    def _layers(self, consistent_defects=False):
+        """``generate_lattice`` and then, per species in order of first appearance, ``(label, points (n, 3) of (x, y, scale)
+        on the frame, A, half kernel w[0..r])``."""
+        from .background import _gaussian_weights
+        coords = self.generate_lattice()
+        shape = tuple(int(v) for v in self.size)
+        layers = []
+        for label, atoms in coords.items():
+            scales = self._scales(label, len(atoms), consistent_defects)
+            p = self.species_params.get(label, {'sigma': 2.0, 'A': 1.0})
+            sigma = float(p['sigma'])
+            if self.use_fft:
+                radius = (int(6 * p['sigma']) | 1) // 2
+                weights = np.exp(-np.arange(radius + 1, dtype=np.float64) ** 2 / (2 * sigma ** 2))
+            else:
+                weights = _gaussian_weights(sigma)
+            points = _on_frame(np.column_stack([atoms, scales.astype(np.float64)]), shape)
+            layers.append((label, points, float(p['A']), weights))
+        return layers
+
+    def simulate(self, return_masks=False, *, consistent_defects=False):
+        """The float32 ``size`` frame (and, with ``return_masks``, ``{label: delta image}``), rendered on the GPU.
+
+        ``consistent_defects`` (keyword only, not in the reference): the reference dims the atom whose place in its species'
+        array equals the stored global site index -- another atom than the one the labels mark, often one off the frame.
+        ``True`` dims the labelled atom; the default is the reference's behaviour."""
+        from .resident import tmd_frames_device
+        out = tmd_frames_device([self], return_masks=return_masks, consistent_defects=consistent_defects)
+        if return_masks:
+            frames, masks = out
+            masks = masks.numpy()[0]
+            return frames.numpy()[0], {label: masks[k] for k, label in enumerate(self._species())}
+        return out.numpy()[0]
+
+    def plot(self, img):
+        import matplotlib.pyplot as plt
+        plt.figure(figsize=(6, 6))
+        plt.imshow(img, cmap='gray')
+        plt.title("Simulated Atomic-Resolution TMD Image")
+        plt.axis('off')
+        plt.show()
+
+    def get_defect_counts(self):
+        if self.labels is None:
+            raise ValueError("Run simulate() first to generate labels.")
+        unique, counts = np.unique(self.labels, return_counts=True)
+        return dict(zip(unique, counts))
+
+    def save(self, img, path):
+        np.save(path, img)
 
 
 # ----------------------------------------------------------------------------------------------- test data

@@ -264,6 +264,52 @@ def honeycomb_image_device(lattice, like=None, **to_image_kw):
     return img
 
 
+def tmd_frames_device(simulators, return_masks=False, out=None, consistent_defects=False):
+    """The frames of a sequence of :class:`mtflearn_amd.datasets.TMDImageSimulator` of one ``size`` and one ``use_fft``, in one
+    device call: the ``(B, H, W)`` float32 stack as a :class:`~mtflearn_amd._native.DeviceArray` on the default device, or
+    written into ``out`` (a contiguous float32 array of that shape, a DeviceArray or a torch tensor, on whose device and stream
+    the call then runs).  With ``return_masks`` also the delta images ``(B, S, H, W)`` of the same kind, species in order of
+    first appearance in ``basis`` (every simulator then needs the same number of species).  Every simulator's lattice is
+    generated (its ``pts``, ``labels`` and ``lbs`` are set); frame ``b`` is ``simulators[b].simulate()`` bit for bit, whatever
+    else is in the batch.  Only the atoms on the frame and the half kernels cross to the device; the stream is synchronised
+    before the call returns.  Newer than ``__all__``: reached as ``resident.tmd_frames_device``."""
+    from .datasets import _tmd_render_device
+    simulators = list(simulators)
+    if not simulators:
+        raise ValueError("tmd_frames_device needs at least one simulator")
+    h, w = (int(v) for v in simulators[0].size)
+    use_fft = bool(simulators[0].use_fft)
+    if h < 1 or w < 1:
+        raise ValueError("the frame size must be positive")
+    layers, counts = [], []
+    for b, sim in enumerate(simulators):
+        if tuple(int(v) for v in sim.size) != (h, w) or bool(sim.use_fft) != use_fft:
+            raise ValueError("the simulators of one call share one size and one use_fft")
+        own = sim._layers(consistent_defects)
+        counts.append(len(own))
+        layers += [(b,) + layer[1:] for layer in own]
+    if return_masks and len(set(counts)) != 1:
+        raise ValueError("return_masks needs the same number of species in every simulator")
+    shape = (len(simulators), h, w)
+    if out is None:
+        _native.load()
+        _native.require_device()
+        out = _native.DeviceArray(shape, np.float32, _native.default_device())
+    elif (not getattr(out, "is_cuda", False) or not out.is_contiguous() or tuple(out.shape) != shape
+          or _device.np_dtype(out) != np.float32):
+        raise ValueError(f"out must be a contiguous {shape} float32 array on the GPU")
+    masks = _device.empty((len(layers), h, w), np.float32, out) if return_masks else None
+    _tmd_render_device(out, masks, layers, True, use_fft)
+    if not return_masks:
+        return out
+    mask_shape = (len(simulators), counts[0], h, w)
+    if is_native(masks):
+        masks = _native.DeviceArray(mask_shape, np.float32, masks.device.index, _base=masks, _ptr=masks.data_ptr())
+    else:
+        masks = masks.view(mask_shape)
+    return out, masks
+
+
 def _as_dtype_device(array, np_dtype, what):
     """``array`` as a contiguous device array of ``np_dtype``: a torch tensor is converted on the device, a DeviceArray must
     already have the type."""
