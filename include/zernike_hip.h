@@ -933,6 +933,52 @@ int zk_rotate_rows(int device, const double* rows_host, int64_t n_rows, int n_po
 int zk_rotate_rows_dev(int device, const double* rows_dev, int64_t n_rows, int n_poly, const int32_t* n, const int32_t* m,
                        const double* angles_dev, double* out_dev, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * The same alignment for the PLANE layout of the dense path, and the frame route built on it: for every pixel of a frame, which
+ * template it looks like, at what rotation and how well (csrc/zk_align.hip; no reference counterpart).
+ *   planes : (n_poly, .) float64, moment j of pixel i at planes[j * plane_stride + i], plane_stride >= n_pixels (doubles)
+ *   angle, score : (n_templates, .) float64, template t of pixel i at [t * out_plane_stride + i], out_plane_stride >= n_pixels
+ *   best   : (n_pixels) int32;  norm2 : (n_pixels) float64 = sum_j s_j x_j^2 over the selected real moments, one fma chain in
+ *            ascending column order: with it score becomes a distance (norm2 + |t|^2 - 2 score) or a cosine
+ *            (score / sqrt(norm2 |t|^2)).  Any of the four outputs may be NULL.
+ * Options, grid, refinement and the best rule are those of zk_align_rows, and so are the bits: the two kernels instantiate one
+ * body on two operand layouts, so pixel i of the planes gets exactly what row i of the transposed matrix gets.  Refused with
+ * ZK_E_BADARG and a message, before any device call: plane_stride < n_pixels, out_plane_stride < n_pixels, and everything
+ * zk_align_rows refuses.  n_pixels == 0 succeeds and launches nothing.  No atomics: a pixel's results do not depend on the launch
+ * geometry, on its position, on the strides or on the banding.  zk_align_planes moves chunks of pixels (zk_align_set_host_chunk)
+ * through the device's staging ring, a chunk of the operand as n_poly strided pieces; zk_align_planes_dev enqueues on exactly
+ * `hip_stream` and does not synchronise (same page-locked slot and table cache as zk_align_rows_dev).
+ *
+ * zk_frame_align(_dev): output rows [row0, row0 + n_rows) of the maps of a frame, with the plan's labels (which must be a
+ * paired set).  The plan's dense transform -- whatever zk_transform_frame_dev resolves for it -- writes a band of rows into the
+ * plan's scratch matrix, the planes kernel turns the band into its part of the maps, band after band on one stream: the
+ * (n_poly, H, W) moments never exist.  A band holds at most 1 GiB of moments (zk_align_set_band_bytes(device, bytes): less; 0: the
+ * default), at least one row, whole multiples of 8 rows where it holds that many.  Zero-padded border positions are computed like
+ * any other, as the dense transform returns them.  Outputs: (n_templates, n_rows, W) with out_plane_stride >= n_rows * W between
+ * templates, (n_rows, W) for best and norm2; with out = full + row0 * W and out_plane_stride = H * W the band lands inside
+ * whole-frame maps.  The *_dev form takes ZK_F32 / ZK_F64 frames on the device, the host form also the narrow formats; calls on
+ * one plan share its scratch matrix and are not concurrent.
+ * ------------------------------------------------------------------------------------------------------ */
+int zk_align_planes(int device, const double* planes_host, int64_t n_pixels, int64_t plane_stride, int n_poly, const int32_t* n,
+                    const int32_t* m, const double* templates_host, int n_templates, const int32_t* select, int n_theta, int symmetry,
+                    int newton_iters, int key, const double* trig_host, int trig_m, const double* key_values_host,
+                    double* angle_out, double* score_out, int32_t* best_out, double* norm2_out, int64_t out_plane_stride);
+int zk_align_planes_dev(int device, const double* planes_dev, int64_t n_pixels, int64_t plane_stride, int n_poly, const int32_t* n,
+                        const int32_t* m, const double* templates_host, int n_templates, const int32_t* select, int n_theta,
+                        int symmetry, int newton_iters, int key, const double* trig_host, int trig_m, const double* key_values_host,
+                        double* angle_dev, double* score_dev, int32_t* best_dev, double* norm2_dev, int64_t out_plane_stride,
+                        void* hip_stream);
+int zk_frame_align(zk_plan* plan, const void* image_host, int dtype, int64_t height, int64_t width, int64_t row0, int64_t n_rows,
+                   const double* templates_host, int n_templates, const int32_t* select, int n_theta, int symmetry,
+                   int newton_iters, int key, const double* trig_host, int trig_m, const double* key_values_host,
+                   double* angle_host, double* score_host, int32_t* best_host, double* norm2_host, int64_t out_plane_stride);
+int zk_frame_align_dev(zk_plan* plan, const void* image_dev, int dtype, int64_t height, int64_t width, int64_t row0, int64_t n_rows,
+                       const double* templates_host, int n_templates, const int32_t* select, int n_theta, int symmetry,
+                       int newton_iters, int key, const double* trig_host, int trig_m, const double* key_values_host,
+                       double* angle_dev, double* score_dev, int32_t* best_dev, double* norm2_dev, int64_t out_plane_stride,
+                       void* hip_stream);
+int zk_align_set_band_bytes(int device, int64_t bytes);   /* moments per band of zk_frame_align; 0: the default */
+
 /* ---------------------------------------------------------------------------------------------------------
  * mtflearn.eels (reference eels/_baseline_correction.py): the baseline of every spectrum of a spectrum image.
  *

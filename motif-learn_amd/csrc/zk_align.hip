@@ -25,12 +25,32 @@
 //
 // The rows are read per lane at stride P (as zk_maps_rows_kernel does: the strided accesses are served by the caches; the
 // arithmetic per element read is 2 n_theta FMAs and more).
+//
+// zk_align_planes_kernel<NM, TB>: the same search for the plane layout of the dense path, one pixel per lane.
+//   planes    (P, .)  float64, moment j of pixel i at planes[j * plane_stride + i]: the 64 lanes of a wave read one contiguous
+//                     512-byte run per moment plane.  All offsets are 64-bit.
+//   outputs           plane-major, so that the stores coalesce: angle, score (T, .) with out_plane_stride between templates,
+//                     best (.) int32 and norm2 (.) = sum_j s_j x_j^2 over the selected real moments -- one fma chain in
+//                     ascending column order -- which turns score into a distance (norm2 + |t|^2 - 2 score) or a cosine
+//                     (score / sqrt(norm2 |t|^2)).  Any output may be NULL.
+// Both kernels instantiate ONE body (align_body) on an operand accessor: the c_m build in pair order, the table pass, the Newton
+// steps, the wrap, the re-evaluation and the best rule are the same operations in the same order, so a pixel gets the bits its
+// row would get.  Same NM / TB instances, same limits, same register budget (2 NM TB float64 accumulators, no scratch).
+//
+// zk_frame_align(_dev): frame -> maps.  The plan's dense transform (whatever zk_transform_frame_dev resolves) writes a band of
+// rows into the plan's scratch matrix (P, band, W), the planes kernel turns the band into its part of the maps, band after
+// band on one stream: the (P, H, W) moments never exist.  A band holds at most 1 GiB of moments (zk_align_set_band_bytes: less),
+// at least one row, whole multiples of 8 rows where it can (a block of the dense kernels).
 #include <cmath>
 #include <cstring>
 #include <mutex>
 #include <new>
 
 #include "zk_ring.h"
+
+// Nothing in this unit is contracted by the compiler: every fused multiply-add is written as __builtin_fma, every other
+// operation rounds on its own, so the rows and the planes kernel (one body, two operand layouts) give one pixel the same bits.
+#pragma clang fp contract(off)
 
 #define ZK_ALIGN_MAX_M 40
 #define ZK_ALIGN_MAX_T 64
@@ -73,24 +93,43 @@ __device__ __forceinline__ void align_eval(const double c0, const double (&cr)[N
   f2 = -h;
 }
 
-template <int NM, int TB>
-__global__ __launch_bounds__(256) void zk_align_kernel(const double* __restrict__ rows, long long n_rows, int P,
-                                                       const int32_t* __restrict__ starts, const int32_t* __restrict__ ia,
-                                                       const int32_t* __restrict__ ib, const double* __restrict__ tmpl,
-                                                       const double* __restrict__ keyval, int K, int T,
-                                                       const double* __restrict__ theta, const double* __restrict__ trig, int n_theta,
-                                                       double step_deg, double period, int newton, int key,
-                                                       double* __restrict__ angle, double* __restrict__ score,
-                                                       int32_t* __restrict__ best) {
-  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
-  const bool live = r < n_rows;
-  const double* __restrict__ row = rows + (live ? r : 0) * P;
+// What a launch reads besides the operand: the pair lists (bucket m is [starts[m], starts[m + 1])), the templates in pair form,
+// the key values, the grid and its table -- all wave-uniform -- and, for norm2, the selected columns in ascending order.
+struct align_params {
+  const int32_t *starts, *ia, *ib, *cols;
+  const double *tmpl, *keyval, *theta, *trig;
+  int K, T, n_theta, newton, key, n_cols;
+  double step_deg, period;
+};
+
+// The two operand layouts of the shared body.  at(j): moment j of the lane's unit; out(t): where its value for template t goes.
+struct rows_access {  // (N, P) rows -> (N, T) outputs
+  const double* __restrict__ row;
+  long long r;
+  int T;
+  __device__ __forceinline__ double at(int j) const { return row[j]; }
+  __device__ __forceinline__ size_t out(int t) const { return (size_t)(r * T + t); }
+};
+struct planes_access {  // (P, .) planes `stride` apart -> (T, .) planes `out_stride` apart
+  const double* __restrict__ px;  // plane 0 at the lane's pixel
+  size_t stride, out_stride;
+  long long i;
+  __device__ __forceinline__ double at(int j) const { return px[(size_t)j * stride]; }
+  __device__ __forceinline__ size_t out(int t) const { return (size_t)t * out_stride + (size_t)i; }
+};
+
+// Everything after the load, for both kernels.  Every multiply-add below is an explicit fma and every other operation is rounded
+// on its own (contraction is off for this unit, see the top): the two instantiations run the same operations in the same order.
+template <int NM, int TB, class A>
+__device__ __forceinline__ void align_body(const A& x, bool live, long long unit, const align_params& q, double* __restrict__ angle,
+                                           double* __restrict__ score, int32_t* __restrict__ best, double* __restrict__ norm2) {
+  const int T = q.T, K = q.K;
   double best_val = 0.0;
   int best_t = 0;
   for (int t0 = 0; t0 < T; t0 += TB) {
     const double* tp[TB];
 #pragma unroll
-    for (int u = 0; u < TB; ++u) tp[u] = tmpl + (size_t)(t0 + u < T ? t0 + u : T - 1) * K * 2;  // past T: the last one again, not written
+    for (int u = 0; u < TB; ++u) tp[u] = q.tmpl + (size_t)(t0 + u < T ? t0 + u : T - 1) * K * 2;  // past T: the last one again, not written
     double c0[TB], cr[TB][NM], ci[TB][NM];
 #pragma unroll
     for (int u = 0; u < TB; ++u) {
@@ -98,15 +137,15 @@ __global__ __launch_bounds__(256) void zk_align_kernel(const double* __restrict_
 #pragma unroll
       for (int m = 0; m < NM; ++m) cr[u][m] = ci[u][m] = 0.0;
     }
-    for (int k = starts[0]; k < starts[1]; ++k) {
-      const double a = row[ia[k]];
+    for (int k = q.starts[0]; k < q.starts[1]; ++k) {
+      const double a = x.at(q.ia[k]);
 #pragma unroll
       for (int u = 0; u < TB; ++u) c0[u] = __builtin_fma(a, tp[u][2 * k], c0[u]);
     }
 #pragma unroll
     for (int m = 1; m <= NM; ++m)
-      for (int k = starts[m]; k < starts[m + 1]; ++k) {
-        const double a = row[ia[k]], b = row[ib[k]];
+      for (int k = q.starts[m]; k < q.starts[m + 1]; ++k) {
+        const double a = x.at(q.ia[k]), b = x.at(q.ib[k]);
 #pragma unroll
         for (int u = 0; u < TB; ++u) {
           const double tr = tp[u][2 * k], ti = tp[u][2 * k + 1];  // z conj(t) = (a tr + b ti) + i (b tr - a ti)
@@ -123,8 +162,8 @@ __global__ __launch_bounds__(256) void zk_align_kernel(const double* __restrict_
       fmax[u] = 0.0;
       jmax[u] = 0;
     }
-    for (int j = 0; j < n_theta; ++j) {
-      const double* __restrict__ tj = trig + (size_t)j * (2 * NM);
+    for (int j = 0; j < q.n_theta; ++j) {
+      const double* __restrict__ tj = q.trig + (size_t)j * (2 * NM);
       double fc[TB], fs[TB];
 #pragma unroll
       for (int u = 0; u < TB; ++u) {
@@ -154,21 +193,21 @@ __global__ __launch_bounds__(256) void zk_align_kernel(const double* __restrict_
 #pragma unroll
     for (int u = 0; u < TB; ++u) {
       const int t = t0 + u;
-      const double th0 = theta[jmax[u]];
+      const double th0 = q.theta[jmax[u]];
       double ang = th0, sc = fmax[u];
-      if (newton > 0) {
-        const double lo = th0 - step_deg, hi = th0 + step_deg;
+      if (q.newton > 0) {
+        const double lo = th0 - q.step_deg, hi = th0 + q.step_deg;
         double th = th0;
-        for (int it = 0; it < newton; ++it) {
+        for (int it = 0; it < q.newton; ++it) {
           double f, f1, f2;
           align_eval<NM, true>(c0[u], cr[u], ci[u], th, f, f1, f2);
           if (f2 < 0.0) {
-            const double next = th - (f1 / f2) * R2D;
+            const double next = __builtin_fma(-(f1 / f2), R2D, th);  // th - (f1 / f2) R2D, one rounding
             th = next < lo ? lo : next > hi ? hi : next == next ? next : th;
           }
         }
-        if (th < 0.0) th += period;
-        if (th >= period) th -= period;
+        if (th < 0.0) th += q.period;
+        if (th >= q.period) th -= q.period;
         double f, f1, f2;
         align_eval<NM, false>(c0[u], cr[u], ci[u], th, f, f1, f2);
         if (f >= fmax[u]) {
@@ -177,17 +216,48 @@ __global__ __launch_bounds__(256) void zk_align_kernel(const double* __restrict_
         }
       }
       if (t < T) {
-        if (live && angle) angle[r * T + t] = ang;
-        if (live && score) score[r * T + t] = sc;
-        const double val = key == 0 ? __builtin_fma(-2.0, sc, keyval[t]) : sc * keyval[t];
-        if (t == 0 || (key == 0 ? val < best_val : val > best_val)) {
+        if (live && angle) angle[x.out(t)] = ang;
+        if (live && score) score[x.out(t)] = sc;
+        const double val = q.key == 0 ? __builtin_fma(-2.0, sc, q.keyval[t]) : sc * q.keyval[t];
+        if (t == 0 || (q.key == 0 ? val < best_val : val > best_val)) {
           best_val = val;
           best_t = t;
         }
       }
     }
   }
-  if (live && best) best[r] = best_t;
+  if (live && best) best[unit] = best_t;
+  if (norm2) {  // sum_j s_j x_j^2: one chain over the selected columns, ascending
+    double sq = 0.0;
+    for (int c = 0; c < q.n_cols; ++c) {
+      const double v = x.at(q.cols[c]);
+      sq = __builtin_fma(v, v, sq);
+    }
+    if (live) norm2[unit] = sq;
+  }
+}
+
+template <int NM, int TB>
+__global__ __launch_bounds__(256) void zk_align_kernel(const double* __restrict__ rows, long long n_rows, int P, align_params q,
+                                                       double* __restrict__ angle, double* __restrict__ score,
+                                                       int32_t* __restrict__ best) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  const bool live = r < n_rows;
+  const rows_access x{rows + (live ? r : 0) * P, r, q.T};
+  align_body<NM, TB>(x, live, r, q, angle, score, best, nullptr);
+}
+
+// One pixel per lane: a wave reads one contiguous 512-byte run per moment plane.  A lane past the end reads pixel 0 and writes
+// nothing.  All offsets are 64-bit.
+template <int NM, int TB>
+__global__ __launch_bounds__(256) void zk_align_planes_kernel(const double* __restrict__ planes, long long n_pixels, long long plane_stride,
+                                                              align_params q, double* __restrict__ angle, double* __restrict__ score,
+                                                              int32_t* __restrict__ best, double* __restrict__ norm2,
+                                                              long long out_plane_stride) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const bool live = i < n_pixels;
+  const planes_access x{planes + (live ? i : 0), (size_t)plane_stride, (size_t)out_plane_stride, i};
+  align_body<NM, TB>(x, live, i, q, angle, score, best, norm2);
 }
 
 __global__ __launch_bounds__(256) void zk_rotate_rows_kernel(const double* rows, long long n_rows, int P, const int32_t* __restrict__ starts,
@@ -283,6 +353,7 @@ struct align_state {
   hipStream_t stream = nullptr;  // kernels of the host variants
   zk_ring ring;                  // their staging (zk_ring.h)
   size_t host_chunk = 0;
+  size_t band_bytes = 0;         // moments per band of zk_frame_align; 0 = 1 GiB
   std::vector<align_table> tables;
   align_slot slots[ZK_ALIGN_SLOTS];
   int next = 0;
@@ -345,38 +416,62 @@ int take_slot(align_state* s, size_t bytes, align_slot** out) {
   return 0;
 }
 
-// what a launch reads besides the rows
+// what a launch reads besides the operand
 struct align_job {
-  int P = 0, K = 0, T = 0, NM = 0, n_theta = 0, newton = 0, key = 0, m_top = 0;
+  int P = 0, K = 0, T = 0, NM = 0, n_theta = 0, newton = 0, key = 0, m_top = 0, n_cols = 0;
   double step = 0.0, period = 0.0;
-  const int32_t *starts = nullptr, *ia = nullptr, *ib = nullptr;
+  const int32_t *starts = nullptr, *ia = nullptr, *ib = nullptr, *cols = nullptr;
   const double *tmpl = nullptr, *keyval = nullptr, *theta = nullptr, *trig = nullptr;
   align_slot* slot = nullptr;
+  align_params params() const {
+    return {starts, ia, ib, cols, tmpl, keyval, theta, trig, K, T, n_theta, newton, key, n_cols, step, period};
+  }
 };
 
 const int NM_INSTANCES[] = {2, 4, 6, 8, 10, 12, 16, 24, 40};
 
+// one launch; `pl` (planes) selects the layout: planes of plane_stride, outputs of out_stride and norm2, or rows of P
+struct align_operand {
+  const double* data;
+  bool planes;
+  int64_t plane_stride, out_stride;
+  double* norm2;
+};
+
 template <int NM, int TB>
-int launch_align_one(const align_job& j, const double* rows, int64_t n, double* angle, double* score, int32_t* best, hipStream_t s) {
-  hipLaunchKernelGGL((zk_align_kernel<NM, TB>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, rows, (long long)n, j.P, j.starts, j.ia,
-                     j.ib, j.tmpl, j.keyval, j.K, j.T, j.theta, j.trig, j.n_theta, j.step, j.period, j.newton, j.key, angle, score, best);
+int launch_align_one(const align_job& j, const align_operand& o, int64_t n, double* angle, double* score, int32_t* best, hipStream_t s) {
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (o.planes)
+    hipLaunchKernelGGL((zk_align_planes_kernel<NM, TB>), grid, dim3(256), 0, s, o.data, (long long)n, (long long)o.plane_stride, j.params(),
+                       angle, score, best, o.norm2, (long long)o.out_stride);
+  else
+    hipLaunchKernelGGL((zk_align_kernel<NM, TB>), grid, dim3(256), 0, s, o.data, (long long)n, j.P, j.params(), angle, score, best);
   ZK_HIP(hipGetLastError());
   return 0;
 }
 
-int launch_align(const align_job& j, const double* rows, int64_t n, double* angle, double* score, int32_t* best, hipStream_t s) {
+int launch_align_any(const align_job& j, const align_operand& o, int64_t n, double* angle, double* score, int32_t* best, hipStream_t s) {
   switch (j.NM) {
-    case 2: return launch_align_one<2, 4>(j, rows, n, angle, score, best, s);
-    case 4: return launch_align_one<4, 4>(j, rows, n, angle, score, best, s);
-    case 6: return launch_align_one<6, 4>(j, rows, n, angle, score, best, s);
-    case 8: return launch_align_one<8, 4>(j, rows, n, angle, score, best, s);
-    case 10: return launch_align_one<10, 4>(j, rows, n, angle, score, best, s);
-    case 12: return launch_align_one<12, 4>(j, rows, n, angle, score, best, s);
-    case 16: return launch_align_one<16, 2>(j, rows, n, angle, score, best, s);
-    case 24: return launch_align_one<24, 2>(j, rows, n, angle, score, best, s);
-    case 40: return launch_align_one<40, 1>(j, rows, n, angle, score, best, s);
+    case 2: return launch_align_one<2, 4>(j, o, n, angle, score, best, s);
+    case 4: return launch_align_one<4, 4>(j, o, n, angle, score, best, s);
+    case 6: return launch_align_one<6, 4>(j, o, n, angle, score, best, s);
+    case 8: return launch_align_one<8, 4>(j, o, n, angle, score, best, s);
+    case 10: return launch_align_one<10, 4>(j, o, n, angle, score, best, s);
+    case 12: return launch_align_one<12, 4>(j, o, n, angle, score, best, s);
+    case 16: return launch_align_one<16, 2>(j, o, n, angle, score, best, s);
+    case 24: return launch_align_one<24, 2>(j, o, n, angle, score, best, s);
+    case 40: return launch_align_one<40, 1>(j, o, n, angle, score, best, s);
   }
   return zk_fail(ZK_E_BADARG, "align: no kernel instance");
+}
+
+int launch_align(const align_job& j, const double* rows, int64_t n, double* angle, double* score, int32_t* best, hipStream_t s) {
+  return launch_align_any(j, align_operand{rows, false, 0, 0, nullptr}, n, angle, score, best, s);
+}
+
+int launch_align_planes(const align_job& j, const double* planes, int64_t n, int64_t plane_stride, double* angle, double* score,
+                        int32_t* best, double* norm2, int64_t out_stride, hipStream_t s) {
+  return launch_align_any(j, align_operand{planes, true, plane_stride, out_stride, norm2}, n, angle, score, best, s);
 }
 
 // the device table of an option set: looked up by value, uploaded (blocking) on the first call with it only
@@ -437,8 +532,13 @@ int find_table(align_state* s, int NM, int n_theta, int symmetry, const double* 
 
 // pair lists (and templates, key values) into a slot, on their way to the device on `stream`
 int upload_blob(align_state* s, const align_pairs& pr, const double* tmpl_pairs, const double* keyval, int T, hipStream_t stream,
-                align_job* job) {
-  const size_t K = (size_t)pr.K, ints = ZK_ALIGN_STARTS + 2 * ((K + 1) & ~(size_t)1);
+                align_job* job, bool with_cols = false) {
+  std::vector<int32_t> cols;  // the selected columns, ascending (norm2 of the planes kernel); none for the other callers
+  if (with_cols)
+    for (size_t jc = 0; jc < pr.sel.size(); ++jc)
+      if (pr.sel[jc]) cols.push_back((int32_t)jc);
+  const size_t C = cols.size(), cpad = (C + 1) & ~(size_t)1;
+  const size_t K = (size_t)pr.K, ints = ZK_ALIGN_STARTS + 2 * ((K + 1) & ~(size_t)1) + cpad;
   const size_t bytes = ints * sizeof(int32_t) + ((size_t)T * K * 2 + (size_t)T) * sizeof(double);
   align_slot* sl = nullptr;
   const int rc = take_slot(s, bytes, &sl);
@@ -448,6 +548,7 @@ int upload_blob(align_state* s, const align_pairs& pr, const double* tmpl_pairs,
   memcpy(hi, pr.starts.data(), ZK_ALIGN_STARTS * sizeof(int32_t));
   if (K) memcpy(hi + ZK_ALIGN_STARTS, pr.ia.data(), K * sizeof(int32_t));
   if (K) memcpy(hi + ZK_ALIGN_STARTS + kpad, pr.ib.data(), K * sizeof(int32_t));
+  if (C) memcpy(hi + ZK_ALIGN_STARTS + 2 * kpad, cols.data(), C * sizeof(int32_t));
   double* hd = (double*)(hi + ints);
   if (T && K) memcpy(hd, tmpl_pairs, (size_t)T * K * 2 * sizeof(double));
   if (T) memcpy(hd + (size_t)T * K * 2, keyval, (size_t)T * sizeof(double));
@@ -456,6 +557,8 @@ int upload_blob(align_state* s, const align_pairs& pr, const double* tmpl_pairs,
   job->starts = di;
   job->ia = di + ZK_ALIGN_STARTS;
   job->ib = di + ZK_ALIGN_STARTS + kpad;
+  job->cols = di + ZK_ALIGN_STARTS + 2 * kpad;
+  job->n_cols = (int)C;
   job->tmpl = (const double*)(di + ints);
   job->keyval = job->tmpl + (size_t)T * K * 2;
   job->slot = sl;
@@ -513,7 +616,7 @@ int check_align(const void* rows, int64_t n_rows, int P, const int32_t* n, const
 }
 
 int prepare_align(align_state* s, const align_args& a, int P, int T, int n_theta, int symmetry, int newton, int key, const double* trig_host,
-                  int trig_m, hipStream_t stream, align_job* job) {
+                  int trig_m, hipStream_t stream, align_job* job, bool with_cols = false) {
   job->P = P;
   job->K = a.pairs.K;
   job->T = T;
@@ -525,7 +628,15 @@ int prepare_align(align_state* s, const align_args& a, int P, int T, int n_theta
   job->step = job->period / (double)n_theta;
   int rc = find_table(s, a.NM, n_theta, symmetry, trig_host, trig_m, &job->theta, &job->trig);
   if (rc) return rc;
-  return upload_blob(s, a.pairs, a.tmpl_pairs.data(), a.keyval.data(), T, stream, job);
+  return upload_blob(s, a.pairs, a.tmpl_pairs.data(), a.keyval.data(), T, stream, job, with_cols);
+}
+
+// what the planes entry points refuse on top of check_align
+int check_planes(int64_t n_pixels, int64_t plane_stride, int64_t out_plane_stride) {
+  if (plane_stride < n_pixels) return zk_fail(ZK_E_BADARG, "align: plane_stride is smaller than n_pixels");
+  if (out_plane_stride < n_pixels) return zk_fail(ZK_E_BADARG, "align: out_plane_stride is smaller than n_pixels");
+  if (n_pixels > (int64_t)0x7fffffff * 256) return zk_fail(ZK_E_BADARG, "align: more than 2^39 pixels in one call");
+  return 0;
 }
 
 int check_rotate(const void* rows, int64_t n_rows, int P, const int32_t* n, const int32_t* m, const void* angles, const void* out,
@@ -620,6 +731,155 @@ extern "C" int zk_align_rows(int device, const double* rows_host, int64_t n_rows
   job.slot->used = false;  // the job has drained
   if (zk_ring_bytes(r) > ((size_t)32 << 20)) zk_ring_free_slots(r);  // a large job's slots go back at once (as zk_synth_apply)
   return rc;
+}
+
+extern "C" int zk_align_set_band_bytes(int device, int64_t bytes) {
+  if (bytes < 0) return zk_fail(ZK_E_BADARG, "bad arguments");
+  int rc = check_device(device);
+  if (rc) return rc;
+  ZK_ON_DEVICE(device);
+  std::lock_guard<std::mutex> lock(g_mu);
+  align_state* s = nullptr;
+  if ((rc = get_state(device, &s))) return rc;
+  s->band_bytes = (size_t)bytes;
+  return 0;
+}
+
+extern "C" int zk_align_planes_dev(int device, const double* planes_dev, int64_t n_pixels, int64_t plane_stride, int n_poly, const int32_t* n,
+                                   const int32_t* m, const double* templates_host, int n_templates, const int32_t* select, int n_theta,
+                                   int symmetry, int newton_iters, int key, const double* trig_host, int trig_m,
+                                   const double* key_values_host, double* angle_dev, double* score_dev, int32_t* best_dev, double* norm2_dev,
+                                   int64_t out_plane_stride, void* hip_stream) {
+  align_args a;
+  int rc = check_align(planes_dev, n_pixels, n_poly, n, m, templates_host, n_templates, select, n_theta, symmetry, newton_iters, key,
+                       trig_host, trig_m, key_values_host, &a);
+  if (rc) return rc;
+  if ((rc = check_planes(n_pixels, plane_stride, out_plane_stride))) return rc;
+  if (n_pixels == 0) return 0;
+  if ((rc = check_device(device))) return rc;
+  ZK_ON_DEVICE(device);
+  std::lock_guard<std::mutex> lock(g_mu);
+  align_state* s = nullptr;
+  if ((rc = get_state(device, &s))) return rc;
+  const hipStream_t stream = (hipStream_t)hip_stream;  // exactly the caller's stream
+  align_job job;
+  if ((rc = prepare_align(s, a, n_poly, n_templates, n_theta, symmetry, newton_iters, key, trig_host, trig_m, stream, &job, true))) return rc;
+  rc = launch_align_planes(job, planes_dev, n_pixels, plane_stride, angle_dev, score_dev, best_dev, norm2_dev, out_plane_stride, stream);
+  const int rd = slot_done(&job, stream);
+  return rc ? rc : rd;
+}
+
+extern "C" int zk_align_planes(int device, const double* planes_host, int64_t n_pixels, int64_t plane_stride, int n_poly, const int32_t* n,
+                               const int32_t* m, const double* templates_host, int n_templates, const int32_t* select, int n_theta,
+                               int symmetry, int newton_iters, int key, const double* trig_host, int trig_m, const double* key_values_host,
+                               double* angle_out, double* score_out, int32_t* best_out, double* norm2_out, int64_t out_plane_stride) {
+  align_args a;
+  int rc = check_align(planes_host, n_pixels, n_poly, n, m, templates_host, n_templates, select, n_theta, symmetry, newton_iters, key,
+                       trig_host, trig_m, key_values_host, &a);
+  if (rc) return rc;
+  if ((rc = check_planes(n_pixels, plane_stride, out_plane_stride))) return rc;
+  if (n_pixels == 0) return 0;
+  if ((rc = check_device(device))) return rc;
+  ZK_ON_DEVICE(device);
+  std::lock_guard<std::mutex> lock(g_mu);
+  align_state* s = nullptr;
+  if ((rc = get_state(device, &s))) return rc;
+  align_job job;
+  if ((rc = prepare_align(s, a, n_poly, n_templates, n_theta, symmetry, newton_iters, key, trig_host, trig_m, s->stream, &job, true))) return rc;
+  zk_ring* r = &s->ring;
+  const size_t T = (size_t)n_templates, in_unit = (size_t)n_poly * sizeof(double), out_unit = (T * 2 + 1) * sizeof(double) + sizeof(int32_t);
+  const size_t budget = s->host_chunk ? s->host_chunk : (size_t)256 << 20;
+  const zk_chunks ch = zk_chunk_plan(budget, in_unit + out_unit, 256, n_pixels);
+  // a slot's input: (P, chunk) planes; its output: angle (T, chunk) | score (T, chunk) | norm2 (chunk) | best (chunk)
+  const size_t line = (size_t)ch.chunk * sizeof(double), plane = T * line;
+  rc = zk_ring_run(
+      r, s->stream, ch.n_chunks,
+      [&](int64_t c, int slot) -> int {
+        int e = zk_ring_slot(r, slot, (size_t)n_poly * line, 2 * plane + line + (size_t)ch.chunk * sizeof(int32_t));
+        if (!e)  // a chunk of a (P, .) operand: P pieces, one per plane
+          e = zk_ring_up_2d(r, s->stream, c, slot, r->d_in[slot], line, planes_host + ch.first(c), (size_t)plane_stride * sizeof(double),
+                            (size_t)ch.count(c) * sizeof(double), (size_t)n_poly);
+        char* o = (char*)r->d_out[slot];
+        return e ? e : launch_align_planes(job, (const double*)r->d_in[slot], ch.count(c), ch.chunk, (double*)o, (double*)(o + plane),
+                                           (int32_t*)(o + 2 * plane + line), (double*)(o + 2 * plane), ch.chunk, s->stream);
+      },
+      [&](int64_t c, int slot) -> int {
+        const char* o = (const char*)r->d_out[slot];
+        const size_t first = (size_t)ch.first(c), w = (size_t)ch.count(c) * sizeof(double), op = (size_t)out_plane_stride * sizeof(double);
+        if (angle_out) ZK_HIP(hipMemcpy2DAsync(angle_out + first, op, o, line, w, T, hipMemcpyDeviceToHost, r->s_out));
+        if (score_out) ZK_HIP(hipMemcpy2DAsync(score_out + first, op, o + plane, line, w, T, hipMemcpyDeviceToHost, r->s_out));
+        if (norm2_out) ZK_HIP(hipMemcpyAsync(norm2_out + first, o + 2 * plane, w, hipMemcpyDeviceToHost, r->s_out));
+        if (best_out)
+          ZK_HIP(hipMemcpyAsync(best_out + first, o + 2 * plane + line, (size_t)ch.count(c) * sizeof(int32_t), hipMemcpyDeviceToHost, r->s_out));
+        return 0;
+      });
+  job.slot->used = false;  // the job has drained
+  if (zk_ring_bytes(r) > ((size_t)32 << 20)) zk_ring_free_slots(r);
+  return rc;
+}
+
+// ---- frame -> maps
+// everything zk_frame_align(_dev) refuses, before any device call; fills `a` when given
+static int frame_align_check(const zk_plan* p, const void* image, int dtype, bool narrow_ok, int64_t H, int64_t W, int64_t row0,
+                             int64_t n_rows, const double* templates, int T, const int32_t* select, int n_theta, int symmetry, int newton,
+                             int key, const double* trig_host, int trig_m, const double* key_values, int64_t out_plane_stride,
+                             align_args* a) {
+  if (!p) return zk_fail(ZK_E_BADARG, "null plan");
+  if (narrow_ok ? (dtype < ZK_F32 || dtype > ZK_I16) : (dtype != ZK_F32 && dtype != ZK_F64))
+    return zk_fail(ZK_E_BADARG, narrow_ok ? "dtype must be ZK_F32, ZK_F64, ZK_U8, ZK_U16 or ZK_I16" : "dtype must be ZK_F32 or ZK_F64");
+  if (H <= 0 || W <= 0 || H > 0x3fffffff || W > 0x3fffffff) return zk_fail(ZK_E_BADARG, "bad frame shape");
+  if (row0 < 0 || n_rows < 0 || row0 + n_rows > H) return zk_fail(ZK_E_BADARG, "row band outside the frame");
+  const int rc = check_align(image, n_rows * W, p->n_poly, p->n.data(), p->m.data(), templates, T, select, n_theta, symmetry, newton, key,
+                             trig_host, trig_m, key_values, a);
+  return rc ? rc : check_planes(n_rows * W, n_rows * W, out_plane_stride);
+}
+
+int zk_frame_align_check(const zk_plan* p, const void* image, int dtype, int64_t H, int64_t W, int64_t row0, int64_t n_rows,
+                         const double* templates, int T, const int32_t* select, int n_theta, int symmetry, int newton, int key,
+                         const double* trig_host, int trig_m, const double* key_values, int64_t out_plane_stride) {
+  align_args a;
+  return frame_align_check(p, image, dtype, true, H, W, row0, n_rows, templates, T, select, n_theta, symmetry, newton, key, trig_host, trig_m,
+                           key_values, out_plane_stride, &a);
+}
+
+extern "C" int zk_frame_align_dev(zk_plan* p, const void* image_dev, int dtype, int64_t H, int64_t W, int64_t row0, int64_t n_rows,
+                                  const double* templates_host, int n_templates, const int32_t* select, int n_theta, int symmetry,
+                                  int newton_iters, int key, const double* trig_host, int trig_m, const double* key_values_host,
+                                  double* angle_dev, double* score_dev, int32_t* best_dev, double* norm2_dev, int64_t out_plane_stride,
+                                  void* hip_stream) {
+  align_args a;
+  int rc = frame_align_check(p, image_dev, dtype, false, H, W, row0, n_rows, templates_host, n_templates, select, n_theta, symmetry,
+                             newton_iters, key, trig_host, trig_m, key_values_host, out_plane_stride, &a);
+  if (rc) return rc;
+  if (n_rows == 0) return 0;
+  if ((rc = check_device(p->device))) return rc;
+  ZK_ON_PLAN_DEVICE(p);
+  std::lock_guard<std::mutex> lock(g_mu);
+  align_state* s = nullptr;
+  if ((rc = get_state(p->device, &s))) return rc;
+  const hipStream_t stream = (hipStream_t)hip_stream;  // exactly the caller's stream
+  // rows per band: what the byte limit holds, at least one, whole blocks of the dense kernels (8 rows) where there are that many
+  const size_t row_bytes = (size_t)p->n_poly * (size_t)W * sizeof(double);
+  const size_t limit = s->band_bytes && s->band_bytes < ((size_t)1 << 30) ? s->band_bytes : (size_t)1 << 30;
+  int64_t band = (int64_t)(limit / row_bytes);
+  if (band < 1) band = 1;
+  if (band >= n_rows) band = n_rows;
+  else if (band > 8) band &= ~(int64_t)7;
+  if ((rc = zk_ensure((void**)&p->d_scratch, &p->d_scratch_bytes, (size_t)band * row_bytes))) return rc;
+  align_job job;
+  if ((rc = prepare_align(s, a, p->n_poly, n_templates, n_theta, symmetry, newton_iters, key, trig_host, trig_m, stream, &job, true))) return rc;
+  for (int64_t b0 = 0; b0 < n_rows && !rc; b0 += band) {
+    const int64_t nb = n_rows - b0 < band ? n_rows - b0 : band, off = b0 * W;
+    const long long keep = p->out_plane;
+    p->out_plane = 0;  // the scratch matrix is compact: (P, nb, W)
+    rc = zk_transform_frame_dev(p, image_dev, dtype, H, W, row0 + b0, nb, p->d_scratch, hip_stream);
+    p->out_plane = keep;
+    if (!rc)
+      rc = launch_align_planes(job, p->d_scratch, nb * W, nb * W, angle_dev ? angle_dev + off : nullptr, score_dev ? score_dev + off : nullptr,
+                               best_dev ? best_dev + off : nullptr, norm2_dev ? norm2_dev + off : nullptr, out_plane_stride, stream);
+  }
+  const int rd = slot_done(&job, stream);
+  return rc ? rc : rd;
 }
 
 extern "C" int zk_rotate_rows_dev(int device, const double* rows_dev, int64_t n_rows, int n_poly, const int32_t* n, const int32_t* m,

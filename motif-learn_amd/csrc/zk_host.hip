@@ -293,6 +293,48 @@ extern "C" int zk_frame_maps(zk_plan* p, const void* image_host, int dtype, int6
 }
 
 // ------------------------------------------------------------------------------------------------------
+// rotation-aligned template maps (zk_align.hip): the frame goes up once, the maps of rows [row0, row0 + n_rows) come down a
+// row band at a time; a slot holds angle (T, band, W) | score (T, band, W) | norm2 (band, W) | best (band, W)
+// ------------------------------------------------------------------------------------------------------
+extern "C" int zk_frame_align(zk_plan* p, const void* image_host, int dtype, int64_t H, int64_t W, int64_t row0, int64_t n_rows,
+                              const double* templates_host, int n_templates, const int32_t* select, int n_theta, int symmetry,
+                              int newton_iters, int key, const double* trig_host, int trig_m, const double* key_values_host,
+                              double* angle_host, double* score_host, int32_t* best_host, double* norm2_host, int64_t out_plane_stride) {
+  int rc = zk_frame_align_check(p, image_host, dtype, H, W, row0, n_rows, templates_host, n_templates, select, n_theta, symmetry, newton_iters,
+                                key, trig_host, trig_m, key_values_host, out_plane_stride);
+  if (rc) return rc;
+  if (n_rows == 0) return 0;
+  ZK_ON_PLAN_DEVICE(p);
+  zk_host_ring* h;
+  if ((rc = ring_get(p, &h))) return rc;
+  zk_ring* r = &h->ring;
+  if ((rc = frame_up(p, h, image_host, dtype, H, W, 0))) return zk_ring_drain(r, p->stream, rc);
+  const size_t T = (size_t)n_templates, px_bytes = (2 * T + 1) * sizeof(double) + sizeof(int32_t);
+  const zk_chunks band = zk_chunk_plan(chunk_bytes(p), px_bytes * W, 8, n_rows);
+  const size_t line = (size_t)band.chunk * W * sizeof(double), plane = T * line;
+  return zk_ring_run(
+      r, p->stream, band.n_chunks,
+      [&](int64_t c, int slot) -> int {
+        const int e = zk_ring_slot(r, slot, 0, 2 * plane + line + (size_t)band.chunk * W * sizeof(int32_t));
+        char* o = (char*)r->d_out[slot];
+        return e ? e : zk_frame_align_dev(p, h->d_frame, kernel_dtype(dtype), H, W, row0 + band.first(c), band.count(c), templates_host,
+                                          n_templates, select, n_theta, symmetry, newton_iters, key, trig_host, trig_m, key_values_host,
+                                          (double*)o, (double*)(o + plane), (int32_t*)(o + 2 * plane + line), (double*)(o + 2 * plane),
+                                          band.chunk * W, p->stream);
+      },
+      [&](int64_t c, int slot) -> int {
+        const char* o = (const char*)r->d_out[slot];
+        const size_t first = (size_t)band.first(c) * W, n = (size_t)band.count(c) * W, w = n * sizeof(double),
+                     op = (size_t)out_plane_stride * sizeof(double);
+        if (angle_host) ZK_HIP(hipMemcpy2DAsync(angle_host + first, op, o, line, w, T, hipMemcpyDeviceToHost, r->s_out));
+        if (score_host) ZK_HIP(hipMemcpy2DAsync(score_host + first, op, o + plane, line, w, T, hipMemcpyDeviceToHost, r->s_out));
+        if (norm2_host) ZK_HIP(hipMemcpyAsync(norm2_host + first, o + 2 * plane, w, hipMemcpyDeviceToHost, r->s_out));
+        if (best_host) ZK_HIP(hipMemcpyAsync(best_host + first, o + 2 * plane + line, n * sizeof(int32_t), hipMemcpyDeviceToHost, r->s_out));
+        return 0;
+      });
+}
+
+// ------------------------------------------------------------------------------------------------------
 // moments at key points: frame and point list go up once, the moments come down in chunks
 // ------------------------------------------------------------------------------------------------------
 extern "C" int zk_transform_points(zk_plan* p, const void* image_host, int dtype, int64_t H, int64_t W,

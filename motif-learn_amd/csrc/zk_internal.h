@@ -156,6 +156,11 @@ static inline int zk_ensure(void** buf, size_t* have, size_t need) {
 void zk_host_release(zk_plan* p);  // frees the staging ring
 int zk_complex_count(int n_max);   // number of (n, |m|) pairs (zk_api.hip)
 
+// what zk_frame_align refuses, before the frame goes up (zk_align.hip; dtype: any of the host formats)
+int zk_frame_align_check(const zk_plan* p, const void* image, int dtype, int64_t H, int64_t W, int64_t row0, int64_t n_rows,
+                         const double* templates, int T, const int32_t* select, int n_theta, int symmetry, int newton, int key,
+                         const double* trig_host, int trig_m, const double* key_values, int64_t out_plane_stride);
+
 // profiling brackets (zk_api.hip)
 int zk_prof_begin(zk_plan* p, hipStream_t s);
 int zk_prof_end(zk_plan* p, hipStream_t s);

@@ -154,6 +154,16 @@ static inline int zk_ring_up(zk_ring* r, hipStream_t kernel, int64_t c, int slot
   return 0;
 }
 
+// as zk_ring_up for `rows` pieces of `width` bytes each, `spitch` bytes apart on the host and `dpitch` in the slot
+static inline int zk_ring_up_2d(zk_ring* r, hipStream_t kernel, int64_t c, int slot, void* dst, size_t dpitch, const void* src, size_t spitch,
+                                size_t width, size_t rows) {
+  if (c >= ZK_RING_SLOTS) ZK_HIP(hipStreamWaitEvent(r->s_in, r->ev_k[slot], 0));
+  ZK_HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, hipMemcpyHostToDevice, r->s_in));
+  ZK_HIP(hipEventRecord(r->ev_in[slot], r->s_in));
+  ZK_HIP(hipStreamWaitEvent(kernel, r->ev_in[slot], 0));
+  return 0;
+}
+
 // the slot's d_out down in one piece
 static inline int zk_ring_down(zk_ring* r, int slot, void* dst, size_t bytes) {
   ZK_HIP(hipMemcpyAsync(dst, r->d_out[slot], bytes, hipMemcpyDeviceToHost, r->s_out));

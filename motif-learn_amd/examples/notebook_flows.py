@@ -8,6 +8,7 @@
   resident chain:      lattice rendered on the device -> denoise -> background removal -> local maxima -> moments at them
   refined chain:       the same key points -> sub-pixel centroids -> bond length -> Voronoi bonds -> polygons, all resident
   motifs:              k-means centres of the key-point moments -> ZPs.inverse_transform -> the motif each class stands for
+  matching:            kmeans_aligned templates -> ZPs.align_maps -> cosine map from score, norm2, |t| -> local_max
 
 Only the import line differs from the reference (`from mtflearn import ZPs`).  Needs an MI355X.
 Run:  python motif-learn_amd/examples/notebook_flows.py
@@ -156,6 +157,20 @@ def main():
     print(f"         aligned k-means from the plain centres: {a_iter} iterations in {1e3 * (time.perf_counter() - t):.1f} ms, class sizes"
           f" {np.bincount(a_labels, minlength=4).tolist()}, aligned motifs {a_motifs.shape}; orientation per atom in [0, 360):"
           f" {np.round(a_angles[:4], 1).tolist()} ...")
+
+    # ---- finding the motifs: the aligned centres as templates, every pixel of the frame matched against them -----------------
+    from mtflearn_amd.features import local_max
+    t = time.perf_counter()
+    found_maps = zps.align_maps(clean.numpy(), a_centres, key="cosine")    # angle / score (4, H, W), best (H, W), norm2 (H, W)
+    t_norm2 = (a_centres ** 2).sum(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):                   # cosine of a pixel's moments with its best template, rotated
+        cosine = np.take_along_axis(found_maps.score, found_maps.best[None].astype(np.int64), axis=0)[0] / np.sqrt(
+            found_maps.norm2 * t_norm2[found_maps.best])
+    cosine = np.where(np.isfinite(cosine) & zps._valid_mask(*cosine.shape), cosine, 0.0)
+    sites_found = local_max(cosine, 5.0, threshold=0.9)                    # (N, 2) (x, y): where a learned motif sits
+    print(f"match  : align_maps of {cosine.shape} against {a_centres.shape[0]} templates -> cosine map -> local_max in"
+          f" {1e3 * (time.perf_counter() - t):.1f} ms; {len(sites_found)} matches above 0.9, per class"
+          f" {np.bincount(found_maps.best[sites_found[:, 1], sites_found[:, 0]], minlength=a_centres.shape[0]).tolist()}")
 
 
 if __name__ == "__main__":

@@ -218,6 +218,19 @@ SYMBOLS = {
                                   POINTER(c_int32), c_int, c_int, c_int, c_int, POINTER(c_double), c_int, POINTER(c_double), c_void_p,
                                   c_void_p, c_void_p, c_void_p]),
     "zk_align_set_host_chunk": (c_int, [c_int, c_int64]),
+    "zk_align_planes": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), c_int,
+                                POINTER(c_int32), c_int, c_int, c_int, c_int, POINTER(c_double), c_int, POINTER(c_double), c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_int64]),
+    "zk_align_planes_dev": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), c_int,
+                                    POINTER(c_int32), c_int, c_int, c_int, c_int, POINTER(c_double), c_int, POINTER(c_double), c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "zk_frame_align": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, POINTER(c_double), c_int,
+                               POINTER(c_int32), c_int, c_int, c_int, c_int, POINTER(c_double), c_int, POINTER(c_double), c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_int64]),
+    "zk_frame_align_dev": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, POINTER(c_double), c_int,
+                                   POINTER(c_int32), c_int, c_int, c_int, c_int, POINTER(c_double), c_int, POINTER(c_double), c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "zk_align_set_band_bytes": (c_int, [c_int, c_int64]),
     "zk_rotate_rows": (c_int, [c_int, c_void_p, c_int64, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p]),
     "zk_rotate_rows_dev": (c_int, [c_int, c_void_p, c_int64, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
     "zk_eels_snip": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),
@@ -430,6 +443,7 @@ class Plan:
         self.device = int(device)
         n32 = np.ascontiguousarray(n, dtype=np.int32)
         m32 = np.ascontiguousarray(m, dtype=np.int32)
+        self.n, self.m = n32, m32          # the labels of the moment axis (what the alignment maps pair up)
         require_device()
         handle = c_void_p()
         check(lib.zk_plan_create(self.size, self.n_poly, n32.ctypes.data_as(POINTER(c_int32)),
@@ -753,6 +767,112 @@ def align_set_host_chunk(chunk_bytes, device=None):
     """Bytes of input + output per chunk of :func:`align_rows` and :func:`rotate_rows` (0: the default of 256 MiB)."""
     check(load().zk_align_set_host_chunk(default_device() if device is None else int(device), int(chunk_bytes)),
           "zk_align_set_host_chunk")
+
+
+def _out_ptr(array):
+    return c_void_p(array.ctypes.data) if array is not None else None
+
+
+def align_planes(planes, spec, n_pixels=None, out=None, device=None):
+    """``zk_align_planes``: host planes ``(P, S)`` float64 -- moment ``j`` of pixel ``i`` at ``planes[j, i]``, the first
+    ``n_pixels`` (default ``S``) of every plane count, so ``S`` is the plane stride -- against ``spec`` (:class:`AlignSpec`) ->
+    ``(angle (T, n_pixels), score (T, n_pixels), best (n_pixels) int32, norm2 (n_pixels))`` host arrays.  ``out``: the four
+    arrays to write into instead, ``angle`` and ``score`` C-contiguous ``(T, S_out)`` with one ``S_out >= n_pixels`` (the output
+    plane stride; columns past ``n_pixels`` are left alone), ``best`` / ``norm2`` of at least ``n_pixels`` entries; an entry may be
+    ``None`` (that output is not computed).  Everything is checked here, before any device call."""
+    planes = np.asarray(planes)
+    if planes.ndim != 2 or planes.shape[0] != len(spec.n) or planes.dtype != np.float64 or not planes.flags.c_contiguous:
+        raise ValueError(f"planes must be a C-contiguous ({len(spec.n)}, S) float64 matrix, one plane per moment")
+    stride = planes.shape[1]
+    n = stride if n_pixels is None else int(n_pixels)
+    if n < 0:
+        raise ValueError("n_pixels must not be negative")
+    if stride < n:
+        raise ValueError(f"plane_stride ({stride}) is smaller than n_pixels ({n})")
+    t = spec.n_templates
+    if out is None:
+        out = (np.empty((t, n)), np.empty((t, n)), np.empty(n, dtype=np.int32), np.empty(n))
+    angle, score, best, norm2 = out
+    out_stride = _check_plane_outputs(angle, score, best, norm2, t, n)
+    if n == 0:
+        return angle, score, best, norm2
+    require_device()
+    dev = default_device() if device is None else int(device)
+    check(load().zk_align_planes(dev, planes.ctypes.data_as(c_void_p), n, stride, *spec._tail(), _out_ptr(angle), _out_ptr(score),
+                                 _out_ptr(best), _out_ptr(norm2), out_stride), "zk_align_planes")
+    return angle, score, best, norm2
+
+
+def _check_plane_outputs(angle, score, best, norm2, t, n):
+    """The output plane stride of host outputs of :func:`align_planes` (``n`` when neither map is wanted)."""
+    stride = None
+    for name, a in (("angle", angle), ("score", score)):
+        if a is None:
+            continue
+        if a.ndim != 2 or a.shape[0] != t or a.dtype != np.float64 or not a.flags.c_contiguous:
+            raise ValueError(f"{name} must be a C-contiguous ({t}, S_out) float64 array")
+        if stride is not None and a.shape[1] != stride:
+            raise ValueError("angle and score must share one plane stride")
+        stride = a.shape[1]
+    stride = n if stride is None else stride
+    if stride < n:
+        raise ValueError(f"out_plane_stride ({stride}) is smaller than n_pixels ({n})")
+    for name, a, dt in (("best", best, np.int32), ("norm2", norm2, np.float64)):
+        if a is not None and (a.ndim != 1 or a.shape[0] < n or a.dtype != dt or not a.flags.c_contiguous):
+            raise ValueError(f"{name} must be a C-contiguous {np.dtype(dt).name} vector of at least {n} entries")
+    return stride
+
+
+def align_planes_dev(device, planes_ptr, n_pixels, plane_stride, spec, angle_ptr, score_ptr, best_ptr, norm2_ptr, out_plane_stride,
+                     stream=0):
+    """``zk_align_planes_dev``: planes and outputs on the device (an output pointer may be 0), enqueued on ``stream``."""
+    if plane_stride < n_pixels:
+        raise ValueError(f"plane_stride ({plane_stride}) is smaller than n_pixels ({n_pixels})")
+    if out_plane_stride < n_pixels:
+        raise ValueError(f"out_plane_stride ({out_plane_stride}) is smaller than n_pixels ({n_pixels})")
+    check(load().zk_align_planes_dev(int(device), c_void_p(planes_ptr), int(n_pixels), int(plane_stride), *spec._tail(), c_void_p(angle_ptr),
+                                     c_void_p(score_ptr), c_void_p(best_ptr), c_void_p(norm2_ptr), int(out_plane_stride),
+                                     c_void_p(stream)), "zk_align_planes_dev")
+
+
+def _check_plan_labels(plan, spec):
+    if len(spec.n) != plan.n_poly:
+        raise ValueError(f"the templates carry {len(spec.n)} moments but the plan has {plan.n_poly}")
+
+
+def frame_align(plan, image, spec, row0=0, n_rows=None):
+    """``zk_frame_align``: host frame ``(H, W)`` (one of the element types of ``ZPs.transform``) -> the maps of its output rows
+    ``[row0, row0 + n_rows)``: ``(angle (T, n_rows, W), score (T, n_rows, W), best (n_rows, W) int32, norm2 (n_rows, W))`` host
+    arrays.  ``plan``: the :class:`Plan` whose dense transform feeds the search; ``spec`` carries the plan's labels."""
+    _check_plan_labels(plan, spec)
+    h, w = image.shape
+    n_rows = h - row0 if n_rows is None else int(n_rows)
+    if row0 < 0 or n_rows < 0 or row0 + n_rows > h:
+        raise ValueError("row band outside the frame")
+    t = spec.n_templates
+    angle, score = pinned.empty((t, n_rows, w)), pinned.empty((t, n_rows, w))
+    best, norm2 = np.empty((n_rows, w), dtype=np.int32), pinned.empty((n_rows, w))
+    if n_rows * w:
+        check(plan._lib.zk_frame_align(plan._h, image.ctypes.data_as(c_void_p), dtype_code(image.dtype), h, w, int(row0), n_rows,
+                                       *spec._tail()[3:], _out_ptr(angle), _out_ptr(score), _out_ptr(best), _out_ptr(norm2), n_rows * w),
+              "zk_frame_align")
+    return angle, score, best, norm2
+
+
+def frame_align_dev(plan, image_ptr, code, height, width, row0, n_rows, spec, angle_ptr, score_ptr, best_ptr, norm2_ptr,
+                    out_plane_stride, stream=0):
+    """``zk_frame_align_dev``: frame and outputs on the device (an output pointer may be 0), enqueued on ``stream``."""
+    _check_plan_labels(plan, spec)
+    check(plan._lib.zk_frame_align_dev(plan._h, c_void_p(image_ptr), int(code), int(height), int(width), int(row0), int(n_rows),
+                                       *spec._tail()[3:], c_void_p(angle_ptr), c_void_p(score_ptr), c_void_p(best_ptr), c_void_p(norm2_ptr),
+                                       int(out_plane_stride), c_void_p(stream)), "zk_frame_align_dev")
+
+
+def align_set_band_bytes(band_bytes, device=None):
+    """Bytes of moments per row band of :func:`frame_align` / :func:`frame_align_dev` (0: the default of 1 GiB; never less than
+    one row)."""
+    check(load().zk_align_set_band_bytes(default_device() if device is None else int(device), int(band_bytes)),
+          "zk_align_set_band_bytes")
 
 
 def _labels32(n, m):

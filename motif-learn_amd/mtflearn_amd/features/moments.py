@@ -20,11 +20,13 @@ import numpy as np
 
 __all__ = [
     "nm2j", "nm2j_complex", "check_array1d", "construct_complex_matrix",
-    "construct_real_matrix", "construct_rot_maps_matrix", "zmoments", "AlignResult",
+    "construct_real_matrix", "construct_rot_maps_matrix", "zmoments", "AlignResult", "AlignMaps",
 ]
 
 # what zmoments.align returns: angle (N, T) degrees, score (N, T) = f(angle), best (N) int32
 AlignResult = namedtuple("AlignResult", ["angle", "score", "best"])
+# what zmoments.align_map / ZPs.align_maps return: angle (T, H, W) degrees, score (T, H, W), best (H, W) int32, norm2 (H, W)
+AlignMaps = namedtuple("AlignMaps", ["angle", "score", "best", "norm2"])
 
 
 def _require_integral(values, message):
@@ -257,13 +259,19 @@ class zmoments:
     def _rank2_real(self, what):
         if self.data.ndim != 2:
             raise ValueError(f"{what} works on rank-2 (N, N_poly) moments; this container holds rank-{self.data.ndim} data "
-                             "(dense frames are out of scope)")
+                             "(dense frames: align_map)")
         return self.to_real()
 
-    def _align_spec(self, templates, m_select=None, n_theta=360, symmetry=1, refine=True, key="distance"):
-        """The checked host operands of :meth:`align` (``_native.AlignSpec``) and the real form of the rows."""
+    def _align_spec(self, templates, m_select=None, n_theta=360, symmetry=1, refine=True, key="distance", dense=False):
+        """The checked host operands of :meth:`align` / :meth:`align_map` (``_native.AlignSpec``) and the real form of the data."""
         from .. import _native
-        real = self._rank2_real("align")
+        if dense:
+            if self.data.ndim != 3:
+                raise ValueError(f"align_map works on rank-3 (N_poly, H, W) moments of a dense frame; this container holds "
+                                 f"rank-{self.data.ndim} data (rows of moments: align)")
+            real = self.to_real()
+        else:
+            real = self._rank2_real("align")
         if isinstance(templates, zmoments):
             tm = templates._rank2_real("align (templates)")
             if not (np.array_equal(tm.n, real.n) and np.array_equal(tm.m, real.m)):
@@ -296,6 +304,24 @@ class zmoments:
         from .. import _native
         real, spec = self._align_spec(templates, m_select, n_theta, symmetry, refine, key)
         return AlignResult(*_native.align_rows(real.data, spec))
+
+    def align_map(self, templates, m_select=None, n_theta=360, symmetry=1, refine=True, key="distance"):
+        """:meth:`align` for the rank-3 ``(N_poly, H, W)`` moments of a dense frame, on the GPU: for every pixel, the rotation
+        that best brings its moments onto every template, how well, and which template wins.
+
+        Options and arithmetic are those of :meth:`align` (a pixel gets the bits its moment vector would get as a row).  Returns
+        ``AlignMaps(angle (T, H, W), score (T, H, W), best (H, W) int32, norm2 (H, W))``; ``norm2`` is the sum of squares of the
+        pixel's selected real moments, which turns ``score`` into a distance ``norm2 + |t|^2 - 2 score`` or a cosine
+        ``score / sqrt(norm2 |t|^2)`` -- the map to threshold and hand to ``local_max``.  Positions whose window touched the
+        zero padding are computed like any other (see :attr:`valid_mask`).  ``ZPs.align_maps(image, templates)`` gives the
+        same maps without the ``(N_poly, H, W)`` array ever existing."""
+        from .. import _native
+        real, spec = self._align_spec(templates, m_select, n_theta, symmetry, refine, key, dense=True)
+        p, h, w = real.data.shape
+        planes = np.ascontiguousarray(real.data, dtype=np.float64).reshape(p, h * w)
+        angle, score, best, norm2 = _native.align_planes(planes, spec)
+        t = spec.n_templates
+        return AlignMaps(angle.reshape(t, h, w), score.reshape(t, h, w), best.reshape(h, w), norm2.reshape(h, w))
 
     def rotate_each(self, angles):
         """Real moments of every row's pattern rotated by its own angle (degrees), on the GPU: row ``r`` is

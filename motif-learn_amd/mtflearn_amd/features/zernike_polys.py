@@ -310,6 +310,34 @@ class ZPs(BaseEstimator, TransformerMixin):
         out["valid_mask"] = self._valid_mask(height, width)   # same convention as zmoments.valid_mask
         return out
 
+    def _align_spec(self, templates, m_select=None, n_theta=360, symmetry=1, refine=True, key="distance"):
+        """The checked host operands (``_native.AlignSpec``) of an alignment against this set's labels."""
+        probe = zmoments._adopt(np.zeros((1, len(self.n))), self.n, self.m, patch_size=self.size)
+        return probe._align_spec(templates, m_select, n_theta, symmetry, refine, key)[1]
+
+    def align_maps(self, image, templates, m_select=None, n_theta=360, symmetry=1, refine=True, key="distance"):
+        """Frame -> rotation-aligned template maps on the GPU (extension; not in the reference API): for every pixel, which
+        template its window looks like, at what rotation, and how well.
+
+        The same maps, bit for bit, as ``self.transform(image).align_map(templates, ...)`` -- see ``zmoments.align_map`` for the
+        options and the returned ``AlignMaps(angle (T, H, W), score (T, H, W), best (H, W) int32, norm2 (H, W))`` -- but the
+        ``(N_poly, H, W)`` moments never exist: the dense kernel writes a band of rows into a device scratch matrix (at most
+        1 GiB) and the alignment kernel turns the band into its rows of the maps.  ``templates``: a rank-2 ``zmoments`` of this
+        set (e.g. ``kmeans_aligned`` centres) or a ``(T, P)`` real array, ``T <= 64``."""
+        from .moments import AlignMaps
+        image = np.asarray(image)
+        if image.ndim != 2:
+            raise ValueError("align_maps needs a 2D image.")
+        height, width = image.shape
+        if height < self.size or width < self.size:
+            raise ValueError(
+                f"For FFT convolution, image size ({height}x{width}) must be at least "
+                f"as large as polynomial size ({self.size}x{self.size})")
+        spec = self._align_spec(templates, m_select, n_theta, symmetry, refine, key)
+        operand = self._device_operand(image)
+        with self._lock:
+            return AlignMaps(*_native.frame_align(self._device_plan(), operand, spec))
+
     def _rows_options(self, n_folds, p, m_unselect, theta, mirror):
         if m_unselect is None:
             m_unselect = (0, 1)

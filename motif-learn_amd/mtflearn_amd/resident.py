@@ -581,6 +581,88 @@ def align_device(rows, n, m, templates, m_select=None, n_theta=360, symmetry=1, 
     return AlignResult(angle, score, best)
 
 
+def _resident_align_spec(n, m, templates, m_select, n_theta, symmetry, refine, key):
+    """``(n, m, AlignSpec)`` of a resident alignment call: labels in (n, m) order, host templates, every refusal a ValueError."""
+    from .features.moments import zmoments
+    n, m = np.asarray(n), np.asarray(m)
+    tm = templates.to_real().data if isinstance(templates, zmoments) else np.asarray(templates)
+    probe = zmoments._adopt(np.zeros((1, len(n))), n, m)
+    if not np.array_equal(probe.n, n) or not np.array_equal(probe.m, m):
+        raise ValueError("n, m must be in (n, m) lexicographic order, as ZPs.n / ZPs.m are")
+    return n, m, probe._align_spec(tm, m_select, n_theta, symmetry, refine, key)[1]
+
+
+def _check_map(array, shape, dtype, like, name):
+    if (not getattr(array, "is_cuda", False) or not array.is_contiguous() or tuple(array.shape) != tuple(shape)
+            or _device.np_dtype(array) != dtype or is_native(array) != is_native(like) or array.device.index != like.device.index):
+        raise ValueError(f"{name} must be a contiguous {tuple(shape)} {np.dtype(dtype).name} array of the operand's kind on its device")
+    return array
+
+
+def align_planes_device(planes, n, m, templates, m_select=None, n_theta=360, symmetry=1, refine=True, key="distance", out=None):
+    """The resident twin of ``zmoments.align_map``: ``planes`` is a ``(P, ...)`` float64 torch tensor or ``DeviceArray`` of real
+    moments, moment-major -- e.g. the ``(P, n_rows, W)`` that :func:`frame_moments_device` returns -- with labels ``n``, ``m``;
+    ``templates`` is a host ``(T, P)`` array (or a rank-2 real ``zmoments``).  Returns ``AlignMaps(angle (T, ...), score (T, ...),
+    best (...) int32, norm2 (...))`` as device arrays of ``planes``'s kind (``out``: four such arrays to write into), enqueued on
+    torch's current stream without synchronising, except for the table upload of the first call with a new option set.
+    Everything is checked before any device call.  Like :func:`align_device` it is newer than ``__all__``."""
+    from .features.moments import AlignMaps
+    n, m, spec = _resident_align_spec(n, m, templates, m_select, n_theta, symmetry, refine, key)
+    if not getattr(planes, "is_cuda", False):
+        raise ValueError("planes must live on the GPU")
+    if not planes.is_contiguous():
+        raise ValueError("planes must be contiguous")
+    if len(planes.shape) < 2 or planes.shape[0] != len(n) or _device.np_dtype(planes) != np.float64:
+        raise ValueError(f"planes must be a ({len(n)}, ...) float64 array of real Zernike moments, one plane per moment")
+    rest = tuple(int(v) for v in planes.shape[1:])
+    pixels, t = int(np.prod(rest, dtype=np.int64)), spec.n_templates
+    shapes = ((t,) + rest, (t,) + rest, rest, rest)
+    dtypes = (np.float64, np.float64, np.int32, np.float64)
+    if out is None:
+        out = tuple(_device.empty(s, d, planes) for s, d in zip(shapes, dtypes))
+    else:
+        out = tuple(_check_map(a, s, d, planes, name) for a, s, d, name in zip(out, shapes, dtypes, AlignMaps._fields))
+    if pixels:
+        _native.align_planes_dev(planes.device.index, planes.data_ptr(), pixels, pixels, spec, *(a.data_ptr() for a in out), pixels,
+                                 stream_ptr(planes))
+    return AlignMaps(*out)
+
+
+def align_maps_device(plan: "_native.Plan", image, templates, m_select=None, n_theta=360, symmetry=1, refine=True, key="distance",
+                      row0=0, n_rows=None, full=None):
+    """The resident twin of ``ZPs.align_maps``, in the idiom of :func:`frame_maps_device`: the alignment maps of output rows
+    ``[row0, row0 + n_rows)`` of a float32 / float64 frame ``(H, W)`` resident on the GPU.  Returns ``AlignMaps(angle (T, n_rows, W),
+    score (T, n_rows, W), best (n_rows, W) int32, norm2 (n_rows, W))`` on the device; with ``full = (angle, score, best, norm2)``
+    (whole-frame arrays ``(T, H, W)`` / ``(H, W)``, entries ``None`` where not wanted) the band is written in place into them and
+    ``full`` is returned.  The moments pass through the plan's scratch matrix a band at a time and never exist as a whole.  Runs on
+    torch's current stream without synchronising, except for the table upload of the first call with a new option set; calls on one
+    plan share its scratch matrix and belong on one stream."""
+    from .features.moments import AlignMaps
+    _check_operand(plan, image, "image")
+    code = _device.code(image, FLOATS)
+    _, _, spec = _resident_align_spec(plan.n, plan.m, templates, m_select, n_theta, symmetry, refine, key)
+    if len(image.shape) != 2:
+        raise ValueError(f"align_maps_device needs a 2D image, not {len(image.shape)}-D")
+    h, w = (int(v) for v in image.shape)
+    n_rows = h - row0 if n_rows is None else int(n_rows)
+    if row0 < 0 or n_rows < 0 or row0 + n_rows > h:
+        raise ValueError("row band outside the frame")
+    t, stream = spec.n_templates, stream_ptr(image)
+    dtypes = (np.float64, np.float64, np.int32, np.float64)
+    if full is not None:
+        shapes = ((t, h, w), (t, h, w), (h, w), (h, w))
+        for a, s, d, name in zip(full, shapes, dtypes, AlignMaps._fields):
+            if a is not None:
+                _check_map(a, s, d, image, name)
+        ptr = lambda a, size: a.data_ptr() + row0 * w * size if a is not None else 0
+        _native.frame_align_dev(plan, image.data_ptr(), code, h, w, row0, n_rows, spec, ptr(full[0], 8), ptr(full[1], 8), ptr(full[2], 4),
+                                ptr(full[3], 8), h * w, stream)
+        return full
+    out = tuple(_device.empty(s, d, image) for s, d in zip(((t, n_rows, w), (t, n_rows, w), (n_rows, w), (n_rows, w)), dtypes))
+    _native.frame_align_dev(plan, image.data_ptr(), code, h, w, row0, n_rows, spec, *(a.data_ptr() for a in out), n_rows * w, stream)
+    return AlignMaps(*out)
+
+
 def rotate_rows_device(rows, n, m, angles, out=None):
     """The resident twin of ``zmoments.rotate_each``: every row of the ``(N, P)`` float64 device matrix rotated by its own
     angle (``angles``: ``(N)`` float64 degrees on the same device, e.g. a column of :func:`align_device`'s ``angle`` made
