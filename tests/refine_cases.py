@@ -4,7 +4,8 @@
 for what it exercises in csrc/zk_refine.hip.  ``point_sets()`` maps a name to float64 ``(N, 2)`` points for the neighbour
 distances and the thresholds; ``LI_SETS`` are the jittered ones Li's iteration is pinned on (on a perfect lattice the gaps
 between distinct distances are rounding noise and the published loop need not end).  The key points of the 512^2 frame are
-detected on the CPU by tests/make_golden_refine.py and stored in the golden file; ``frame_512()`` regenerates the frame."""
+detected on the CPU by tests/make_golden_refine.py and stored in the golden file; ``frame_512()`` regenerates the frame.
+The point sets here are near-uniform; tests/point_cases.py has the ones that reach the edges of the neighbour search."""
 import functools
 
 import numpy as np

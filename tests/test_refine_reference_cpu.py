@@ -2,7 +2,9 @@
 reproduces tests/golden/estimate_d_golden.npz, the host ``center_of_mass_refine`` reproduces tests/golden/refine_golden.npz, the
 sequential row-major float64 statement of the centroid sums is bit-equal to the SciPy route on every refine case (the
 summation-order claim of csrc/zk_refine.hip, proven before any kernel runs), and the histogram rule stated for the kernel gives
-``np.histogram``'s counts on every sample of every point set."""
+``np.histogram``'s counts on every sample of every point set.  For tests/test_gpu_points_kernels.py: the brute-force neighbour
+distances it holds the device to agree with scikit-learn on every set of tests/point_cases.py, and the histogram rule gives
+``np.histogram``'s counts on the matrices with values planted on the bin edges, where both of its corrections are taken."""
 import os
 import re
 
@@ -10,6 +12,7 @@ import numpy as np
 import pytest
 
 import make_golden_refine as mg
+import point_cases as pc
 import refine_cases as rc
 import thresholds_reference as ref
 from conftest import ROOT
@@ -84,6 +87,34 @@ def test_the_kernels_histogram_rule_gives_numpys_counts(estimate_golden, name):
         assert np.array_equal(estimate_golden[f"{name}/otsu_counts"][c], want), (name, k)
     first = dd[:, 1].min()                               # rows ascend: one pass gives the eleven ranges
     assert all(dd[:, 1:k].min() == first and dd[:, 1:k].max() == dd[:, k - 1].max() for k in ref.KS)
+
+
+@pytest.mark.parametrize("name", pc.KNN_NAMES)
+def test_brute_force_distances_of_the_edge_sets_agree_with_scikit_learn(name):
+    from sklearn.neighbors import NearestNeighbors
+    pts = pc.knn_sets()[name]
+    k = min(12, len(pts))
+    got, want = pc.knn_reference(pts, k), NearestNeighbors(n_neighbors=k, algorithm="ball_tree").fit(pts).kneighbors(pts)[0]
+    assert got.shape == want.shape and np.all(np.abs(got - want) <= 1e-12 * np.abs(want)), name       # zeros exact
+    assert not got[:, 0].any() and np.all(np.diff(got, axis=1) >= 0)
+
+
+@pytest.mark.parametrize("kind", pc.HIST_KINDS)
+def test_the_histogram_rule_takes_both_corrections_on_the_planted_edges(kind):
+    dd, lasts, edges = pc.hist_matrix(257, kind), pc.hist_lasts(kind), pc.hist_edges(kind)
+    down = up = folded = 0
+    for c, k in enumerate(ref.KS):
+        d = dd[:, 1:k].ravel()
+        want, want_edges = np.histogram(d, bins=256, range=(0.0, lasts[c]))
+        assert np.array_equal(want_edges, edges[c]) and want.sum() == len(d)
+        assert np.array_equal(ref.kernel_bin_rule(d, 0.0, lasts[c]), want), (kind, k)
+        idx = ((d / lasts[c]) * 256.0).astype(np.int64)
+        folded += int((idx == 256).sum())
+        idx[idx == 256] = 255
+        down += int((d < edges[c][idx]).sum())
+        up += int(((d >= edges[c][idx + 1]) & (idx != 255)).sum())
+    print(f"{kind}: {down} values one bin down, {up} one bin up, {folded} folded from 256 into 255")
+    assert folded > 0 and (kind != "uneven" or (down > 0 and up > 0))      # with edges that are exact, the first index is right
 
 
 def test_li_cases_are_jittered_and_stop_clear_of_the_tolerance_boundary(estimate_golden):

@@ -2,6 +2,10 @@
 (tests/make_golden_vnn.py) on every case of tests/vnn_cases.py, the generator against the committed file, ``add_corner_points``
 against the restated formula, and the argument errors that are raised before any launch.
 
+For tests/test_gpu_points_kernels.py, which holds the device to the oracle alone: on the Voronoi sets and the wheels of
+tests/point_cases.py the oracle's cells are qhull's, the sets keep the generator's margins at ``dmax = 1.3 a``, and what the two
+differ by in ridge length stays within a hundredth of the stored tolerance (``d0_new``, printed, recorded in DESIGN.md).
+
 The generator is run once per module (``built``); its conditioning asserts (ridges, ``dmax`` and ``threshold`` margins of 1e-6)
 run with it."""
 import os
@@ -10,6 +14,7 @@ import numpy as np
 import pytest
 
 import make_golden_vnn as gen
+import point_cases as pc
 import vnn_cases as vc
 import vnn_oracle as oracle
 from conftest import ROOT
@@ -65,6 +70,31 @@ def test_oracle_equals_qhull(built, committed, name):
     assert np.array_equal(graph_ijs, committed[f"{name}/ijs"])
     both = {tuple(r) for r in graph_ijs.tolist()}
     assert all((j, i) in both for i, j in both)
+
+
+def new_sets():
+    out = dict(pc.voronoi_sets())
+    out.update({f"wheel_{s}": pc.wheel(s) for s in pc.WHEEL_SPOKES})
+    return out
+
+
+@pytest.mark.parametrize("name", tuple(new_sets()))
+def test_oracle_equals_qhull_on_the_edge_sets(committed, name):
+    pts = new_sets()[name]
+    n = len(pts)
+    rows, orows = gen.qhull_rows(pts), oracle.rows(pts)
+    assert [[r[0] for r in row] for row in rows] == [[r[0] for r in row] for row in orows]
+    a = gen.median_edge(orows, n)
+    assert a == np.median(oracle.neighbours_from_rows(orows, n)[2])
+    dmax = pc.DMAX_FACTOR * a
+    assert gen.conditioned(orows, n, pc.THRESHOLD, dmax, a) is None and gen.conditioned(rows, n, pc.THRESHOLD, dmax, a) is None
+    d0_new = max(abs(r[1] - o[1]) / a for row, orow in zip(rows, orows) for r, o in zip(row, orow))
+    print(f"{name}: {n} points, a = {a:.4g}, d0_new = {d0_new:.3g} (tol_rel {float(committed['tol_rel']):.3g})")
+    assert 100 * d0_new <= float(committed["tol_rel"]), name
+    assert max(abs(r[2] - o[2]) / np.spacing(r[2]) for row, orow in zip(rows, orows) for r, o in zip(row, orow)) <= 1
+    assert np.array_equal(gen.reference_graph(rows, n, pc.THRESHOLD, dmax)[0], oracle.graph_from_rows(orows, n, pc.THRESHOLD, dmax)[0])
+    if name.startswith("wheel_"):
+        assert sum(j < n for j, _, _ in rows[0]) == n - 1 == int(name[6:])          # the hub's cell has one side per spoke
 
 
 def test_add_corner_points_is_the_restated_formula():

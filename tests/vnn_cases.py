@@ -3,7 +3,8 @@ Each case is named for what it exercises in csrc/zk_voronoi.hip; tests/make_gold
 one (ridges, ``dmax`` and ``threshold`` margins) before it stores what SciPy's qhull gives.
 
 ``one_way`` has no threshold of its own here: the generator searches ``ONE_WAY_THRESHOLDS`` for the first one at which a pair
-is kept in one direction only, asserts that there is one, and stores it in the golden file (``one_way/threshold``)."""
+is kept in one direction only, asserts that there is one, and stores it in the golden file (``one_way/threshold``).
+tests/point_cases.py has the sets past these: a strip, a blob in a halo, a density step, and the wheels around the vertex cap."""
 import functools
 
 import numpy as np
