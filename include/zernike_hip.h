@@ -16,6 +16,9 @@
  *   zk_autocorr_mean, zk_polar_profile        <- estimate_patch_size, radial_profile  (_patch_size.py:48-100, 221-302)
  *   zk_power_spectra, zk_denoise_fft          <- _get_cumulative_energy, denoise_fft   (_estimate_n_max.py:8-86,
  *                                                                                      denoise/_denoise_fft.py:4-47)
+ *   zk_circular_autocorr, zk_char_length      <- compute_autocorrelation, get_characteristic_length (_window_size.py:16-46)
+ *   zk_char_length_fft                        <- get_characteristic_length_fft                      (_window_size.py:65-80)
+ *   zk_shifted_magnitude, zk_angular_average  <- fft_power_spectrum, angular_average                (_fft_related.py:4-66)
  *   zk_comm_*, zk_allgather_rows              (no counterpart: the multi-GPU exchange of north_star)
  *
  * Conventions
@@ -369,6 +372,47 @@ int zk_denoise_fft(int device, const void* image_host, int dtype, int64_t height
  * non-zero |db2 diagonal detail coefficients| (PyWavelets dwtn, mode 'symmetric') / 0.6745 -- restated from scikit-image /
  * PyWavelets, which are not installed here (parity unpinned).  Coefficients and the median's order statistics on the device. */
 int zk_wavelet_sigma(int device, const void* image_host, int dtype, int64_t height, int64_t width, double* sigma_out);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Window-size estimators and the angular spectrum average (reference features/_window_size.py, _fft_related.py): what a
+ * user runs before ZPs to choose `size`, here for a whole stack (batch, height, width) of ZK_F32 / ZK_F64 frames in one
+ * call -- 1 .. 65535 frames of at most 16384 x 16384, any height and width.  Host buffers in, host buffers out, blocking;
+ * hipFFT as above.  All arithmetic is float64.
+ *
+ *   zk_circular_autocorr  <- compute_autocorrelation (_window_size.py:16-27): |fftshift(ifft2(F conj F))| of every frame,
+ *                            standardised first when asked (a constant frame fails with the reference's message): the
+ *                            CIRCULAR autocorrelation, not the zero-padded one of zk_autocorr_mean.  out (batch, h, w).
+ *   zk_shifted_magnitude  <- fft_power_spectrum (_fft_related.py:4-7): |fftshift(fft2(frame))| (the magnitude, as in the
+ *                            reference), log(. + 1) of it with use_log (get_characteristic_length_fft's map).
+ *   zk_char_length_fft    <- get_characteristic_length_fft (_window_size.py:65-80) up to `ind`: the shifted (log) magnitude,
+ *                            its first maximum in C order (numpy.argmax) as centre (i, j), the 360-angle MEAN polar profile
+ *                            of zk_polar_profile about it cut to [0:min(i, radii)], minus its SNIP baseline (niter sweeps),
+ *                            scipy.ndimage.uniform_filter1d(size) with reflected edges, and the first maximum of that:
+ *                            ind (batch), -1 for an empty profile (the caller returns height / ind).
+ *   zk_char_length        <- get_characteristic_length (_window_size.py:36-46): scipy.signal.correlate(f, f, 'same', 'fft')
+ *                            of the (standardised) frame -- the path of zk_autocorr_mean, rectangular -- its first maximum
+ *                            as centre, the cut mean polar profile, and the first peak of scipy.signal.find_peaks without
+ *                            conditions (plateaus at their midpoint): peaks (batch), -1 where there is none.
+ *                          Both: centres (batch, 2) int32 (row, col), profiles (batch, zk_polar_radii(h, w)) with zeros
+ *                            from the cut on, smoothed (the filtered profile, same layout); each may be NULL.
+ *   zk_angular_average    <- angular_average (_fft_related.py:12-66) of float64 maps: per frame and bin, the SUM and the
+ *                            COUNT of the pixels with edges[i] <= theta < edges[i + 1], theta = degrees(atan2(dy, dx)) mod
+ *                            360 about (h / 2, w / 2), inside r <= min(h / 2, w / 2) with use_mask.  edges: the caller's
+ *                            numpy.linspace(0, 360, num_bins + 1) (num_bins + 1 increasing values); membership is NumPy's
+ *                            (the multiples of 45 degrees are exact), counts are exact, sums are float64 atomics and vary
+ *                            in their last bits with the order of arrival.  The mean is sum / count on the caller's side.
+ * ------------------------------------------------------------------------------------------------------ */
+int zk_circular_autocorr(int device, const void* images_host, int dtype, int64_t batch, int64_t height, int64_t width,
+                         int standardize, double* out_host);
+int zk_shifted_magnitude(int device, const void* images_host, int dtype, int64_t batch, int64_t height, int64_t width,
+                         int use_log, double* out_host);
+int zk_char_length_fft(int device, const void* images_host, int dtype, int64_t batch, int64_t height, int64_t width, int niter,
+                       int size, int use_log, int32_t* centres_host, double* profiles_host, double* smoothed_host,
+                       int32_t* ind_host);
+int zk_char_length(int device, const void* images_host, int dtype, int64_t batch, int64_t height, int64_t width,
+                   int standardize, int32_t* centres_host, double* profiles_host, int32_t* peaks_host);
+int zk_angular_average(int device, const double* spectra_host, int64_t batch, int64_t height, int64_t width,
+                       const double* edges_host, int64_t num_bins, int use_mask, double* sums_host, int64_t* counts_host);
 
 /* ------------------------------------------------------------------------------------------------------
  * Key-point detection: the device side of local_max (reference features/_local_max_v2.py), the step ahead of

@@ -17,24 +17,14 @@
 #include <mutex>
 #include <vector>
 
-#include <hipfft/hipfft.h>  // types and prototypes only; nothing here links against libhipfft
-
 #include "zk_internal.h"
+#include "zk_pickers.h"
 #include "zk_scratch.h"
 
-namespace {
+zk_fft_api zk_fft;
 
-struct fft_api {
-  void* handle = nullptr;
-  decltype(&hipfftPlanMany) PlanMany = nullptr;
-  decltype(&hipfftExecZ2Z) ExecZ2Z = nullptr;
-  decltype(&hipfftSetStream) SetStream = nullptr;
-  decltype(&hipfftDestroy) Destroy = nullptr;
-};
-fft_api g_fft;
-
-int fft_load() {
-  if (g_fft.handle) return 0;
+int zk_fft_load() {
+  if (zk_fft.handle) return 0;
   void* h = dlopen("libhipfft.so.0", RTLD_NOW | RTLD_NOLOAD | RTLD_GLOBAL);
   if (!h) h = dlopen("libhipfft.so", RTLD_NOW | RTLD_NOLOAD | RTLD_GLOBAL);
   if (!h) {
@@ -54,7 +44,7 @@ int fft_load() {
   if (!h) h = dlopen("libhipfft.so.0", RTLD_NOW | RTLD_GLOBAL);
   if (!h) h = dlopen("/opt/rocm/lib/libhipfft.so.0", RTLD_NOW | RTLD_GLOBAL);
   if (!h) return zk_fail(ZK_E_FFT, std::string("cannot load libhipfft: ") + (dlerror() ? dlerror() : "?"));
-  fft_api a;
+  zk_fft_api a;
   a.handle = h;
 #define ZK_SYM(field, name)                                  \
   a.field = (decltype(a.field))dlsym(h, name);               \
@@ -64,69 +54,55 @@ int fft_load() {
   ZK_SYM(SetStream, "hipfftSetStream");
   ZK_SYM(Destroy, "hipfftDestroy");
 #undef ZK_SYM
-  g_fft = a;
+  zk_fft = a;
   return 0;
 }
-
-#define ZK_FFT(call)                                                                         \
-  do {                                                                                       \
-    const hipfftResult zk_f_ = (call);                                                       \
-    if (zk_f_ != HIPFFT_SUCCESS) return zk_fail(ZK_E_FFT, std::string(#call) + " failed with hipfftResult " + std::to_string((int)zk_f_)); \
-  } while (0)
 
 // Batched 2-D complex plans are kept between calls (round 3): building one costs milliseconds even when rocFFT has its
 // kernels already, and the pickers are called with the same shapes over and over (every window batch of one frame size, every
 // patch set of one size).  A plan in use is checked out of the cache and goes back when its holder dies; the cache keeps the
 // four most recently returned ones and destroys what falls out.
-struct fft_cached {
-  int device, ny, nx, batch;
-  hipfftHandle h;
-};
 static std::mutex g_fft_cache_mutex;
-static std::vector<fft_cached> g_fft_cache;  // most recently returned last
+static std::vector<zk_fft_cached> g_fft_cache;  // most recently returned last
 
-struct fft_plan {
-  hipfftHandle h = 0;
-  bool live = false;
-  fft_cached key = {};
-  ~fft_plan() {
-    if (!live) return;
-    hipfftHandle drop = 0;
-    bool have_drop = false;
-    {
-      std::lock_guard<std::mutex> lock(g_fft_cache_mutex);
-      g_fft_cache.push_back(key);
-      if (g_fft_cache.size() > 4) {
-        drop = g_fft_cache.front().h;
-        have_drop = true;
-        g_fft_cache.erase(g_fft_cache.begin());
+zk_fft_plan::~zk_fft_plan() {
+  if (!live) return;
+  hipfftHandle drop = 0;
+  bool have_drop = false;
+  {
+    std::lock_guard<std::mutex> lock(g_fft_cache_mutex);
+    g_fft_cache.push_back(key);
+    if (g_fft_cache.size() > 4) {
+      drop = g_fft_cache.front().h;
+      have_drop = true;
+      g_fft_cache.erase(g_fft_cache.begin());
+    }
+  }
+  if (have_drop) (void)zk_fft.Destroy(drop);
+}
+
+int zk_fft_plan::make(int ny, int nx, int batch) {
+  int device = 0;
+  ZK_HIP(hipGetDevice(&device));
+  {
+    std::lock_guard<std::mutex> lock(g_fft_cache_mutex);
+    for (size_t i = g_fft_cache.size(); i-- > 0;)
+      if (g_fft_cache[i].device == device && g_fft_cache[i].ny == ny && g_fft_cache[i].nx == nx && g_fft_cache[i].batch == batch) {
+        key = g_fft_cache[i];
+        h = key.h;
+        live = true;
+        g_fft_cache.erase(g_fft_cache.begin() + (long)i);
+        return 0;
       }
-    }
-    if (have_drop) (void)g_fft.Destroy(drop);
   }
-  int make(int ny, int nx, int batch) {
-    int device = 0;
-    ZK_HIP(hipGetDevice(&device));
-    {
-      std::lock_guard<std::mutex> lock(g_fft_cache_mutex);
-      for (size_t i = g_fft_cache.size(); i-- > 0;)
-        if (g_fft_cache[i].device == device && g_fft_cache[i].ny == ny && g_fft_cache[i].nx == nx && g_fft_cache[i].batch == batch) {
-          key = g_fft_cache[i];
-          h = key.h;
-          live = true;
-          g_fft_cache.erase(g_fft_cache.begin() + (long)i);
-          return 0;
-        }
-    }
-    int n[2] = {ny, nx};
-    ZK_FFT(g_fft.PlanMany(&h, 2, n, nullptr, 1, ny * nx, nullptr, 1, ny * nx, HIPFFT_Z2Z, batch));
-    key = fft_cached{device, ny, nx, batch, h};
-    live = true;
-    return 0;
-  }
-};
+  int n[2] = {ny, nx};
+  ZK_FFT(zk_fft.PlanMany(&h, 2, n, nullptr, 1, ny * nx, nullptr, 1, ny * nx, HIPFFT_Z2Z, batch));
+  key = zk_fft_cached{device, ny, nx, batch, h};
+  live = true;
+  return 0;
+}
 
-typedef hipfftDoubleComplex cplx;
+namespace {
 
 __device__ __forceinline__ double block_sum(double v, double* sh) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
@@ -139,43 +115,67 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
   return t;
 }
 
-// mean and population standard deviation of each window (reference standardize_image, _patch_size.py:9-19);
-// one block per window, two passes (mean first: the windows are positive images, E[x^2] - mean^2 would cancel)
+// the block's minimum (sign -1) or maximum (sign +1) of v; NaN is passed over
+__device__ __forceinline__ double block_extreme(double v, double sign, double* sh) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const double u = __shfl_down(v, o);
+    v = sign * u > sign * v ? u : v;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) sh[wave] = v;
+  __syncthreads();
+  double t = sh[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) t = sign * sh[w] > sign * t ? sh[w] : t;
+  return t;
+}
+
+// mean and population standard deviation of each (wh, ww) window (reference standardize_image, _patch_size.py:9-19);
+// one block per window, two passes (mean first: the windows are positive images, E[x^2] - mean^2 would cancel).  The first
+// pass carries the window's min and max: a window whose samples are all equal has the standard deviation 0 exactly, whatever
+// the rounding of its mean leaves in the second pass (the refusal of a constant image must not hang on that).
 template <typename T>
 __global__ __launch_bounds__(256) void window_stats_kernel(const T* __restrict__ img, int W, const int32_t* __restrict__ org,
-                                                           int ws, double* __restrict__ stats) {
+                                                           int wh, int ww, double* __restrict__ stats) {
   __shared__ double sh[4];
   const int b = blockIdx.x;
   const T* base = img + (long long)org[2 * b] * W + org[2 * b + 1];
-  const int n = ws * ws;
-  double s = 0.0;
-  for (int t = threadIdx.x; t < n; t += 256) s += (double)base[(long long)(t / ws) * W + t % ws];
+  const int n = wh * ww;
+  double s = 0.0, lo = INFINITY, hi = -INFINITY;
+  for (int t = threadIdx.x; t < n; t += 256) {
+    const double v = (double)base[(long long)(t / ww) * W + t % ww];
+    s += v;
+    lo = v < lo ? v : lo;
+    hi = v > hi ? v : hi;
+  }
   const double mean = block_sum(s, sh) / (double)n;
+  lo = block_extreme(lo, -1.0, sh);
+  hi = block_extreme(hi, 1.0, sh);
   double q = 0.0;
   for (int t = threadIdx.x; t < n; t += 256) {
-    const double d = (double)base[(long long)(t / ws) * W + t % ws] - mean;
+    const double d = (double)base[(long long)(t / ww) * W + t % ww] - mean;
     q += d * d;
   }
   const double var = block_sum(q, sh) / (double)n;
   if (threadIdx.x == 0) {
     stats[2 * b] = mean;
-    stats[2 * b + 1] = sqrt(var);
+    stats[2 * b + 1] = lo == hi ? 0.0 : sqrt(var);
   }
 }
 
 // window (optionally standardised, optionally multiplied by an outer-product window function) into the top-left corner of
-// an N x N complex field, zero elsewhere
+// an Ny x Nx complex field, zero elsewhere (a window function goes with square windows only)
 template <typename T>
-__global__ __launch_bounds__(256) void fill_kernel(const T* __restrict__ img, int W, const int32_t* __restrict__ org, int ws,
-                                                   const double* __restrict__ stats, const double* __restrict__ win, int N,
+__global__ __launch_bounds__(256) void fill_kernel(const T* __restrict__ img, int W, const int32_t* __restrict__ org, int wh, int ww,
+                                                   const double* __restrict__ stats, const double* __restrict__ win, int Ny, int Nx,
                                                    cplx* __restrict__ out, long long total) {
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   if (t >= total) return;
-  const long long per = (long long)N * N;
+  const long long per = (long long)Ny * Nx;
   const int b = (int)(t / per);
-  const int r = (int)((t - b * per) / N), c = (int)(t - b * per - (long long)r * N);
+  const int r = (int)((t - b * per) / Nx), c = (int)(t - b * per - (long long)r * Nx);
   double v = 0.0;
-  if (r < ws && c < ws) {
+  if (r < wh && c < ww) {
     v = (double)img[(long long)(org[2 * b] + r) * W + org[2 * b + 1] + c];
     if (stats) v = (v - stats[2 * b]) / stats[2 * b + 1];
     if (win) v *= win[r] * win[c];
@@ -192,16 +192,22 @@ __global__ __launch_bounds__(256) void power_kernel(cplx* __restrict__ z, long l
   z[t].y = 0.0;
 }
 
-// acc[i][j] += sum_b Re ac_b[(i - ws/2) mod N][(j - ws/2) mod N] * scale: the 'same' crop of the linear autocorrelation
-// (scipy.signal.correlate mode='same': lags -(ws/2) .. ws - 1 - ws/2, zero lag at index ws/2)
-__global__ __launch_bounds__(256) void crop_accumulate_kernel(const cplx* __restrict__ z, int B, int N, int ws, double scale,
-                                                              double* __restrict__ acc) {
+// acc[i][j] += sum_b Re ac_b[(i - wh/2) mod Ny][(j - ww/2) mod Nx] * scale: the 'same' crop of the linear autocorrelation
+// (scipy.signal.correlate mode='same': along an axis of n samples lags -(n/2) .. n - 1 - n/2, zero lag at index n/2).
+// per_window: grid.y runs over the windows and map b goes to acc[b] instead of into the sum.
+__global__ __launch_bounds__(256) void crop_accumulate_kernel(const cplx* __restrict__ z, int B, int Ny, int Nx, int wh, int ww,
+                                                              double scale, double* __restrict__ acc, int per_window) {
   const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= ws * ws) return;
-  const int i = t / ws, j = t - i * ws;
-  const int r = (i - ws / 2 + N) % N, c = (j - ws / 2 + N) % N;
+  if (t >= wh * ww) return;
+  const int i = t / ww, j = t - i * ww;
+  const int r = (i - wh / 2 + Ny) % Ny, c = (j - ww / 2 + Nx) % Nx;
+  if (per_window) {
+    const int b = blockIdx.y;
+    acc[(long long)b * wh * ww + t] = z[((long long)b * Ny + r) * Nx + c].x * scale;
+    return;
+  }
   double s = 0.0;
-  for (int b = 0; b < B; ++b) s += z[((long long)b * N + r) * N + c].x;
+  for (int b = 0; b < B; ++b) s += z[((long long)b * Ny + r) * Nx + c].x;
   acc[t] += s * scale;
 }
 
@@ -251,13 +257,20 @@ __global__ __launch_bounds__(256) void minmax_kernel(const double* __restrict__ 
 //     row = x / k_r * sin(a / k_a) + center_row, col = x / k_r * cos(a / k_a) + center_col,  k_a = 360 / 2 pi, k_r = R / radius
 //   bilinear between floor / ceil neighbours, pixels outside the array count as 0, result clipped to the input's [min, max]
 //   (values equal to the fill value 0 are kept when 0 lies outside that range).
-// One thread per (item, radius); the 360 angles are aggregated in the thread: method 0 mean, 1 max, 2 sum.
-__global__ __launch_bounds__(128) void polar_profile_kernel(const double* __restrict__ data, int h, int w, int ci, int cj, int R,
-                                                            double radius, int method, const double* __restrict__ mm,
-                                                            double* __restrict__ out) {
+// One thread per (item, radius); the 360 angles are aggregated in the thread: method 0 mean, 1 max, 2 sum.  Every item has
+// its own centre (centres[2 b], centres[2 b + 1]); with `cut`, item b keeps the radii below min(centre row, R) -- the
+// reference's line[0:i] (features/_window_size.py:32) -- and the rest of its row is 0.
+__global__ __launch_bounds__(128) void polar_profile_kernel(const double* __restrict__ data, int h, int w,
+                                                            const int32_t* __restrict__ centres, int cut, int R, double radius,
+                                                            int method, const double* __restrict__ mm, double* __restrict__ out) {
   const int x = blockIdx.x * 128 + threadIdx.x;
   const int b = blockIdx.y;
   if (x >= R) return;
+  const int ci = centres[2 * b], cj = centres[2 * b + 1];
+  if (cut && x >= ci) {
+    out[(long long)b * R + x] = 0.0;
+    return;
+  }
   const double* img = data + (long long)b * h * w;
   const double lo = mm[2 * b], hi = mm[2 * b + 1];
   const bool keep_fill = !(lo <= 0.0 && 0.0 <= hi);
@@ -394,6 +407,57 @@ int check_image(int dtype, int64_t H, int64_t W, const void* p) {
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------
+template <typename T>
+static void launch_window_stats(const void* d_img, int64_t W, const int32_t* d_org, int n, int wh, int ww, double* d_stats) {
+  hipLaunchKernelGGL(window_stats_kernel<T>, dim3(n), dim3(256), 0, 0, (const T*)d_img, (int)W, d_org, wh, ww, d_stats);
+}
+
+int zk_window_stats_dev(const void* d_img, int dtype, int64_t W, const int32_t* d_org, int n_windows, int wh, int ww, double* d_stats) {
+  if (dtype == ZK_F32) launch_window_stats<float>(d_img, W, d_org, n_windows, wh, ww, d_stats);
+  else launch_window_stats<double>(d_img, W, d_org, n_windows, wh, ww, d_stats);
+  ZK_HIP(hipGetLastError());
+  return 0;
+}
+
+int zk_autocorr_same_dev(const void* d_img, int dtype, int64_t W, const int32_t* d_org, int n_windows, int wh, int ww,
+                         const double* d_stats, double* d_out, int per_window) {
+  int rc;
+  const int Ny = 2 * wh, Nx = 2 * ww;  // any N >= 2 n - 1 turns the circular correlation into the linear one
+  // batches of at most ~1 GiB of complex field
+  int B = (int)std::max<long long>(1, ((long long)1 << 30) / ((long long)Ny * Nx * 16));
+  B = std::min(std::min(B, n_windows), 65535);
+  dev_buf d_z;
+  if ((rc = d_z.alloc((size_t)B * Ny * Nx * 16))) return rc;
+  zk_fft_plan plan, plan_tail;
+  if ((rc = plan.make(Ny, Nx, B))) return rc;
+  const double scale = 1.0 / ((double)Ny * Nx * (per_window ? 1 : n_windows));
+  for (int first = 0; first < n_windows; first += B) {
+    const int nb = std::min(B, n_windows - first);
+    zk_fft_plan* use = &plan;
+    if (nb != B) {
+      if ((rc = plan_tail.make(Ny, Nx, nb))) return rc;
+      use = &plan_tail;
+    }
+    const long long total = (long long)nb * Ny * Nx;
+    const double* st = d_stats ? d_stats + 2 * first : nullptr;
+    if (dtype == ZK_F32)
+      hipLaunchKernelGGL(fill_kernel<float>, dim3(blocks_of(total)), dim3(256), 0, 0, (const float*)d_img, (int)W, d_org + 2 * first, wh,
+                         ww, st, (const double*)nullptr, Ny, Nx, d_z.as<cplx>(), total);
+    else
+      hipLaunchKernelGGL(fill_kernel<double>, dim3(blocks_of(total)), dim3(256), 0, 0, (const double*)d_img, (int)W, d_org + 2 * first,
+                         wh, ww, st, (const double*)nullptr, Ny, Nx, d_z.as<cplx>(), total);
+    ZK_HIP(hipGetLastError());
+    ZK_FFT(zk_fft.ExecZ2Z(use->h, d_z.as<cplx>(), d_z.as<cplx>(), HIPFFT_FORWARD));
+    hipLaunchKernelGGL(power_kernel, dim3(blocks_of(total)), dim3(256), 0, 0, d_z.as<cplx>(), total);
+    ZK_FFT(zk_fft.ExecZ2Z(use->h, d_z.as<cplx>(), d_z.as<cplx>(), HIPFFT_BACKWARD));
+    hipLaunchKernelGGL(crop_accumulate_kernel, dim3(blocks_of((long long)wh * ww), per_window ? nb : 1), dim3(256), 0, 0, d_z.as<cplx>(),
+                       nb, Ny, Nx, wh, ww, scale, per_window ? d_out + (size_t)first * wh * ww : d_out, per_window);
+    ZK_HIP(hipGetLastError());
+  }
+  ZK_HIP(hipDeviceSynchronize());  // the transforms' field is freed on return
+  return 0;
+}
+
 extern "C" int zk_autocorr_mean(int device, const void* image_host, int dtype, int64_t H, int64_t W, int64_t window,
                                 const int32_t* origins_yx, int n_windows, int standardize, double* out_host) {
   int rc = check_image(dtype, H, W, image_host);
@@ -403,11 +467,11 @@ extern "C" int zk_autocorr_mean(int device, const void* image_host, int dtype, i
   for (int b = 0; b < n_windows; ++b)
     if (origins_yx[2 * b] < 0 || origins_yx[2 * b] + window > H || origins_yx[2 * b + 1] < 0 || origins_yx[2 * b + 1] + window > W)
       return zk_fail(ZK_E_BADARG, "window outside the image");
-  if ((rc = fft_load())) return rc;
+  if ((rc = zk_fft_load())) return rc;
   ZK_ON_DEVICE(device);
-  const int ws = (int)window, N = 2 * ws;  // any N >= 2 ws - 1 turns the circular correlation into the linear one
+  const int ws = (int)window;
   const size_t es = zk_elem_size(dtype);
-  dev_buf d_img, d_org, d_stats, d_z, d_acc;
+  dev_buf d_img, d_org, d_stats, d_acc;
   if ((rc = d_img.alloc((size_t)H * W * es)) || (rc = d_org.alloc((size_t)n_windows * 8)) ||
       (rc = d_stats.alloc((size_t)n_windows * 16)) || (rc = d_acc.alloc((size_t)ws * ws * 8)))
     return rc;
@@ -415,47 +479,15 @@ extern "C" int zk_autocorr_mean(int device, const void* image_host, int dtype, i
   ZK_HIP(hipMemcpy(d_org.p, origins_yx, (size_t)n_windows * 8, hipMemcpyHostToDevice));
   ZK_HIP(hipMemset(d_acc.p, 0, (size_t)ws * ws * 8));
   if (standardize) {
-    if (dtype == ZK_F32)
-      hipLaunchKernelGGL(window_stats_kernel<float>, dim3(n_windows), dim3(256), 0, 0, d_img.as<float>(), (int)W,
-                         d_org.as<int32_t>(), ws, d_stats.as<double>());
-    else
-      hipLaunchKernelGGL(window_stats_kernel<double>, dim3(n_windows), dim3(256), 0, 0, d_img.as<double>(), (int)W,
-                         d_org.as<int32_t>(), ws, d_stats.as<double>());
-    ZK_HIP(hipGetLastError());
+    if ((rc = zk_window_stats_dev(d_img.p, dtype, W, d_org.as<int32_t>(), n_windows, ws, ws, d_stats.as<double>()))) return rc;
     std::vector<double> st((size_t)2 * n_windows);
     ZK_HIP(hipMemcpy(st.data(), d_stats.p, st.size() * 8, hipMemcpyDeviceToHost));
     for (int b = 0; b < n_windows; ++b)
       if (!(st[2 * b + 1] > 0.0)) return zk_fail(ZK_E_BADARG, "Standard deviation is zero, can't standardize the image.");
   }
-  // batches of at most ~1 GiB of complex field
-  int B = (int)std::max<long long>(1, ((long long)1 << 30) / ((long long)N * N * 16));
-  B = std::min(B, n_windows);
-  if ((rc = d_z.alloc((size_t)B * N * N * 16))) return rc;
-  fft_plan plan, plan_tail;
-  if ((rc = plan.make(N, N, B))) return rc;
-  for (int first = 0; first < n_windows; first += B) {
-    const int nb = std::min(B, n_windows - first);
-    fft_plan* use = &plan;
-    if (nb != B) {
-      if ((rc = plan_tail.make(N, N, nb))) return rc;
-      use = &plan_tail;
-    }
-    const long long total = (long long)nb * N * N;
-    const double* st = standardize ? d_stats.as<double>() + 2 * first : nullptr;
-    if (dtype == ZK_F32)
-      hipLaunchKernelGGL(fill_kernel<float>, dim3(blocks_of(total)), dim3(256), 0, 0, d_img.as<float>(), (int)W,
-                         d_org.as<int32_t>() + 2 * first, ws, st, (const double*)nullptr, N, d_z.as<cplx>(), total);
-    else
-      hipLaunchKernelGGL(fill_kernel<double>, dim3(blocks_of(total)), dim3(256), 0, 0, d_img.as<double>(), (int)W,
-                         d_org.as<int32_t>() + 2 * first, ws, st, (const double*)nullptr, N, d_z.as<cplx>(), total);
-    ZK_HIP(hipGetLastError());
-    ZK_FFT(g_fft.ExecZ2Z(use->h, d_z.as<cplx>(), d_z.as<cplx>(), HIPFFT_FORWARD));
-    hipLaunchKernelGGL(power_kernel, dim3(blocks_of(total)), dim3(256), 0, 0, d_z.as<cplx>(), total);
-    ZK_FFT(g_fft.ExecZ2Z(use->h, d_z.as<cplx>(), d_z.as<cplx>(), HIPFFT_BACKWARD));
-    hipLaunchKernelGGL(crop_accumulate_kernel, dim3(blocks_of((long long)ws * ws)), dim3(256), 0, 0, d_z.as<cplx>(), nb, N, ws,
-                       1.0 / ((double)N * N * n_windows), d_acc.as<double>());
-    ZK_HIP(hipGetLastError());
-  }
+  if ((rc = zk_autocorr_same_dev(d_img.p, dtype, W, d_org.as<int32_t>(), n_windows, ws, ws, standardize ? d_stats.as<double>() : nullptr,
+                                 d_acc.as<double>(), 0)))
+    return rc;
   ZK_HIP(hipMemcpy(out_host, d_acc.p, (size_t)ws * ws * 8, hipMemcpyDeviceToHost));
   return 0;
 }
@@ -463,6 +495,16 @@ extern "C" int zk_autocorr_mean(int device, const void* image_host, int dtype, i
 extern "C" int64_t zk_polar_radii(int64_t h, int64_t w) {
   if (h <= 0 || w <= 0) return 0;
   return (int64_t)ceil(sqrt((double)h / 2.0 * ((double)h / 2.0) + (double)w / 2.0 * ((double)w / 2.0)));
+}
+
+int zk_polar_profile_dev(const double* d_data, int B, int h, int w, const int32_t* d_centres, int cut, int method, const double* d_mm,
+                         double* d_out) {
+  const int R = (int)zk_polar_radii(h, w);
+  const double radius = sqrt((double)h / 2.0 * ((double)h / 2.0) + (double)w / 2.0 * ((double)w / 2.0));
+  hipLaunchKernelGGL(polar_profile_kernel, dim3(blocks_of(R, 128), (unsigned)B), dim3(128), 0, 0, d_data, h, w, d_centres, cut, R, radius,
+                     method, d_mm, d_out);
+  ZK_HIP(hipGetLastError());
+  return 0;
 }
 
 extern "C" int zk_polar_profile(int device, const double* data_host, int64_t batch, int64_t h, int64_t w, int64_t center_row,
@@ -474,17 +516,22 @@ extern "C" int zk_polar_profile(int device, const double* data_host, int64_t bat
   if (method < 0 || method > 2) return zk_fail(ZK_E_BADARG, "Invalid method. Must be 'mean', 'max', or 'sum'.");
   ZK_ON_DEVICE(device);
   const int R = (int)zk_polar_radii(h, w);
-  const double radius = sqrt((double)h / 2.0 * ((double)h / 2.0) + (double)w / 2.0 * ((double)w / 2.0));
-  dev_buf d_in, d_mm, d_out;
+  dev_buf d_in, d_mm, d_out, d_c;
   int rc;
   if ((rc = d_in.alloc((size_t)batch * h * w * 8)) || (rc = d_mm.alloc((size_t)batch * 16)) ||
-      (rc = d_out.alloc((size_t)batch * R * 8)))
+      (rc = d_out.alloc((size_t)batch * R * 8)) || (rc = d_c.alloc((size_t)batch * 8)))
     return rc;
+  std::vector<int32_t> centres((size_t)2 * batch);
+  for (int64_t b = 0; b < batch; ++b) {
+    centres[2 * b] = (int32_t)center_row;
+    centres[2 * b + 1] = (int32_t)center_col;
+  }
   ZK_HIP(hipMemcpy(d_in.p, data_host, (size_t)batch * h * w * 8, hipMemcpyHostToDevice));
+  ZK_HIP(hipMemcpy(d_c.p, centres.data(), (size_t)batch * 8, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(minmax_kernel, dim3((unsigned)batch), dim3(256), 0, 0, d_in.as<double>(), (long long)h * w, d_mm.as<double>());
-  hipLaunchKernelGGL(polar_profile_kernel, dim3(blocks_of(R, 128), (unsigned)batch), dim3(128), 0, 0, d_in.as<double>(), (int)h,
-                     (int)w, (int)center_row, (int)center_col, R, radius, method, d_mm.as<double>(), d_out.as<double>());
-  ZK_HIP(hipGetLastError());
+  if ((rc = zk_polar_profile_dev(d_in.as<double>(), (int)batch, (int)h, (int)w, d_c.as<int32_t>(), 0, method, d_mm.as<double>(),
+                                 d_out.as<double>())))
+    return rc;
   ZK_HIP(hipMemcpy(out_host, d_out.p, (size_t)batch * R * 8, hipMemcpyDeviceToHost));
   return 0;
 }
@@ -498,7 +545,7 @@ extern "C" int zk_power_spectra(int device, const void* image_host, int dtype, i
   for (int b = 0; b < n_windows; ++b)
     if (origins_yx[2 * b] < 0 || origins_yx[2 * b] + size > H || origins_yx[2 * b + 1] < 0 || origins_yx[2 * b + 1] + size > W)
       return zk_fail(ZK_E_BADARG, "window outside the image");
-  if ((rc = fft_load())) return rc;
+  if ((rc = zk_fft_load())) return rc;
   ZK_ON_DEVICE(device);
   const int n = (int)size;
   const size_t es = zk_elem_size(dtype);
@@ -513,14 +560,14 @@ extern "C" int zk_power_spectra(int device, const void* image_host, int dtype, i
   const double* win = window_1d ? d_win.as<double>() : nullptr;
   if (dtype == ZK_F32)
     hipLaunchKernelGGL(fill_kernel<float>, dim3(blocks_of(total)), dim3(256), 0, 0, d_img.as<float>(), (int)W, d_org.as<int32_t>(), n,
-                       (const double*)nullptr, win, n, d_z.as<cplx>(), total);
+                       n, (const double*)nullptr, win, n, n, d_z.as<cplx>(), total);
   else
     hipLaunchKernelGGL(fill_kernel<double>, dim3(blocks_of(total)), dim3(256), 0, 0, d_img.as<double>(), (int)W, d_org.as<int32_t>(),
-                       n, (const double*)nullptr, win, n, d_z.as<cplx>(), total);
+                       n, n, (const double*)nullptr, win, n, n, d_z.as<cplx>(), total);
   ZK_HIP(hipGetLastError());
-  fft_plan plan;
+  zk_fft_plan plan;
   if ((rc = plan.make(n, n, n_windows))) return rc;
-  ZK_FFT(g_fft.ExecZ2Z(plan.h, d_z.as<cplx>(), d_z.as<cplx>(), HIPFFT_FORWARD));
+  ZK_FFT(zk_fft.ExecZ2Z(plan.h, d_z.as<cplx>(), d_z.as<cplx>(), HIPFFT_FORWARD));
   hipLaunchKernelGGL(shift_power_kernel, dim3(blocks_of(total)), dim3(256), 0, 0, d_z.as<cplx>(), n, d_out.as<double>(), total);
   ZK_HIP(hipGetLastError());
   ZK_HIP(hipMemcpy(out_host, d_out.p, (size_t)total * 8, hipMemcpyDeviceToHost));
@@ -533,7 +580,7 @@ extern "C" int zk_denoise_fft(int device, const void* image_host, int dtype, int
   if (!(p > 0.0 && p <= 1.0)) return zk_fail(ZK_E_BADARG, "Fraction p must be between 0 and 1.");
   if (!out_host) return zk_fail(ZK_E_BADARG, "null host pointer");
   if (H > 32768 || W > 32768) return zk_fail(ZK_E_BADARG, "image too large for one transform");
-  if ((rc = fft_load())) return rc;
+  if ((rc = zk_fft_load())) return rc;
   ZK_ON_DEVICE(device);
   const long long n = (long long)H * W;
   const size_t es = zk_elem_size(dtype);
@@ -547,9 +594,9 @@ extern "C" int zk_denoise_fft(int device, const void* image_host, int dtype, int
   else
     hipLaunchKernelGGL(to_complex_kernel<double>, dim3(blocks_of(n)), dim3(256), 0, 0, d_img.as<double>(), d_spec.as<cplx>(), n);
   ZK_HIP(hipGetLastError());
-  fft_plan plan;
+  zk_fft_plan plan;
   if ((rc = plan.make((int)H, (int)W, 1))) return rc;
-  ZK_FFT(g_fft.ExecZ2Z(plan.h, d_spec.as<cplx>(), d_spec.as<cplx>(), HIPFFT_FORWARD));
+  ZK_FFT(zk_fft.ExecZ2Z(plan.h, d_spec.as<cplx>(), d_spec.as<cplx>(), HIPFFT_FORWARD));
   ZK_HIP(hipMemcpy(d_pow.p, d_spec.p, (size_t)n * 16, hipMemcpyDeviceToDevice));
   hipLaunchKernelGGL(power_kernel, dim3(blocks_of(n)), dim3(256), 0, 0, d_pow.as<cplx>(), n);
   // k = ceil(p n) coefficients survive (reference _denoise_fft.py:33-38): find the k-th largest power exactly
@@ -563,7 +610,7 @@ extern "C" int zk_denoise_fft(int device, const void* image_host, int dtype, int
   hipLaunchKernelGGL(mask_kernel, dim3(blocks_of(n)), dim3(256), 0, 0, d_spec.as<cplx>(), d_pow.as<cplx>(), n, prefix,
                      (unsigned int)(k - above), d_hist.as<unsigned int>());
   ZK_HIP(hipGetLastError());
-  ZK_FFT(g_fft.ExecZ2Z(plan.h, d_spec.as<cplx>(), d_spec.as<cplx>(), HIPFFT_BACKWARD));
+  ZK_FFT(zk_fft.ExecZ2Z(plan.h, d_spec.as<cplx>(), d_spec.as<cplx>(), HIPFFT_BACKWARD));
   hipLaunchKernelGGL(real_scale_kernel, dim3(blocks_of(n)), dim3(256), 0, 0, d_spec.as<cplx>(), 1.0 / (double)n, d_out.as<double>(), n);
   ZK_HIP(hipGetLastError());
   ZK_HIP(hipMemcpy(out_host, d_out.p, (size_t)n * 8, hipMemcpyDeviceToHost));

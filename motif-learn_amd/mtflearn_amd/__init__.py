@@ -2,7 +2,9 @@
 
 ``from mtflearn_amd import ZPs, zmoments`` mirrors ``from mtflearn import ZPs, zmoments``
 (reference ``mtflearn/__init__.py:37-38``).  Only this path and the rows SURVEY 8(f) names around it are provided
-(``mtflearn_amd.features``: parameter pickers, ``pca``; ``mtflearn_amd.clustering``: ``kmeans_lbs`` / ``gmm_lbs`` /
+(``mtflearn_amd.features``: parameter pickers, ``pca``, the Fourier window-size estimators
+``get_characteristic_length`` / ``get_characteristic_length_fft`` / ``compute_autocorrelation`` with ``fft_power_spectrum`` /
+``angular_average``; ``mtflearn_amd.clustering``: ``kmeans_lbs`` / ``gmm_lbs`` /
 ``sort_lbs``; ``mtflearn_amd.manifold``: ``ForceGraph8``; ``mtflearn_amd.background``: ``estimate_background_*`` /
 ``remove_background_*`` and their parameter picker; ``mtflearn_amd.denoise``: ``denoise_svd`` / ``DenoiseSVD`` /
 ``denoise_svd_memory_view``, the reference's other two top-level names; ``mtflearn_amd.utils``: ``normalize_image`` /

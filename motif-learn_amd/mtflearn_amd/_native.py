@@ -115,6 +115,12 @@ SYMBOLS = {
                                  POINTER(c_double), POINTER(c_double)]),
     "zk_denoise_fft": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_double, POINTER(c_double)]),
     "zk_wavelet_sigma": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, POINTER(c_double)]),
+    "zk_circular_autocorr": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_void_p]),
+    "zk_shifted_magnitude": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_void_p]),
+    "zk_char_length_fft": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
+    "zk_char_length": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "zk_angular_average": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "zk_local_max": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_double, c_int, c_double, c_void_p, c_int64,
                              POINTER(c_int64)]),
     "zk_local_max_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_double, c_int, c_double, c_void_p, c_int64,
