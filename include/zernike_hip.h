@@ -1141,6 +1141,56 @@ int zk_tmd_render_dev(int device, void* frames_dev, void* masks_dev, int dtype, 
                       const double* amplitudes_host, const int64_t* weight_offsets_host, const double* weights_host, int mode,
                       void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Stack registration (no reference counterpart): the rigid drift of every frame of a (B, H, W) stack against a reference frame
+ * to 1 / upsample of a pixel (Guizar-Sicairos, Thurman, Fienup, Opt. Lett. 33, 156 (2008)), and the ordered mean of a stack.
+ *
+ * shifts[b] = (dy, dx) is the translation that, applied to frame b, registers it onto the reference (scikit-image's sign): for
+ * frame_b(y, x) = ref(y - s_y, x - s_x) it is (-s_y, -s_x).  Everything is float64; the integer formats are widened exactly.
+ *   spectra      F = fft2(frame * w), R = fft2(ref * w); w[y, x] = wy[y] * wx[x], all 1 (ZK_REGISTER_WINDOW_NONE) or the periodic
+ *                Hann window 0.5 - 0.5 cos(2 pi i / n) per axis (ZK_REGISTER_WINDOW_HANN).
+ *   cross power  P = R conj(F); with ZK_REGISTER_NORM_PHASE P is divided by max(|P|, 100 eps max|P|), max|P| per frame.
+ *   correlation  c = real(ifft2(P)).
+ *   coarse peak  (y0, x0): the first maximum of c in flat FFT-layout order over the lags whose wrapped values
+ *                (numpy.fft.fftfreq(n, 1 / n)) satisfy |ly| <= max_shift and |lx| <= max_shift; max_shift -1: every lag.  A
+ *                lattice image correlates at every lattice vector: max_shift says how far drift can have gone.
+ *   upsample 1   the coarse lag is the shift and peak its c.
+ *   upsample u   S = ceil(1.5 u), off = S / 2 (integer), ys[j] = y0 + (j - off) / u and xs[i] = x0 + (i - off) / u in float64,
+ *                C = real(Ey P Ex) / (H W) with Ey[j, k] = exp(+2 pi i ys[j] fftfreq(H)[k]) and Ex[k, i] = exp(+2 pi i
+ *                fftfreq(W)[k] xs[i]); the shift is (ys[j], xs[i]) -- these float64 expressions, bit for bit -- of the first
+ *                maximum of C in row-major order, and peak that C.  It is not clamped to max_shift again.  The phases are formed
+ *                from the integer k (y0 u + j - off) reduced modulo u H before it meets 2 pi / (u H).
+ * Ties go to the smaller flat index.  The reference is frame ref_index of the stack (ZK_REGISTER_REF_INDEX), the (H, W) frame
+ * `ref` of ref_dtype (ZK_REGISTER_REF_FRAME), or for frame b the frame b - 1 (ZK_REGISTER_REF_PREVIOUS: frame 0 meets itself and
+ * the rows are the pairwise shifts; the caller sums them).  shifts is (B, 2), peak (B).  corr (B, H, W) and up (B, S, S), when
+ * not NULL, receive c / (H W)-normalised as above and C (up needs upsample > 1): the planes the answer was read from, for tests.
+ * Frames go in runs whose complex fields stay under 1 GiB; no kernel looks across frames, no atomics are used, and a frame
+ * alone, in a stack, in the host and the _dev form and on a second run gives the same bits.  2 <= H, W <= 16384, upsample in
+ * 1 .. 1000.  Not defined: non-finite samples (nothing scans for them).
+ *
+ * zk_stack_mean: out[y, x] = (stack[0, y, x] + stack[1, y, x] + ... in ascending order) / B in float64: one division, no atomics.
+ *
+ * The host forms stream through a staging ring (frames for the shifts, runs of pixels for the mean).  The _dev forms take
+ * device pointers and run on hip_stream; zk_register_shifts_dev synchronises it before it releases its fields,
+ * zk_stack_mean_dev allocates nothing and does not synchronise.  Everything is checked before any device call; a refused
+ * argument is ZK_E_BADARG with a message.
+ * ------------------------------------------------------------------------------------------------------ */
+#define ZK_REGISTER_REF_INDEX    0
+#define ZK_REGISTER_REF_FRAME    1
+#define ZK_REGISTER_REF_PREVIOUS 2
+#define ZK_REGISTER_NORM_NONE    0
+#define ZK_REGISTER_NORM_PHASE   1
+#define ZK_REGISTER_WINDOW_NONE  0
+#define ZK_REGISTER_WINDOW_HANN  1
+int zk_register_shifts(int device, const void* stack_host, int dtype, int64_t B, int64_t H, int64_t W, int ref_mode, int64_t ref_index,
+                       const void* ref_host, int ref_dtype, int upsample, int64_t max_shift, int normalization, int window,
+                       double* shifts_host, double* peak_host, double* corr_host, double* up_host);
+int zk_register_shifts_dev(int device, const void* stack_dev, int dtype, int64_t B, int64_t H, int64_t W, int ref_mode, int64_t ref_index,
+                           const void* ref_dev, int ref_dtype, int upsample, int64_t max_shift, int normalization, int window,
+                           double* shifts_dev, double* peak_dev, double* corr_dev, double* up_dev, void* hip_stream);
+int zk_stack_mean(int device, const void* stack_host, int dtype, int64_t B, int64_t H, int64_t W, double* out_host);
+int zk_stack_mean_dev(int device, const void* stack_dev, int dtype, int64_t B, int64_t H, int64_t W, double* out_dev, void* hip_stream);
+
 /* Device memory for callers that have no allocator of their own (a NumPy / C user of the *_dev entry points). */
 int zk_device_malloc(int device, int64_t bytes, void** out_dev);
 int zk_device_free(int device, void* dev);

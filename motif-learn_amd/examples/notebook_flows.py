@@ -117,6 +117,22 @@ def main():
               + ("  (a double vacancy leaves nothing to find)" if name == "v2" else ""))
     print("         defect counts of frame 0:", {str(k): int(v) for k, v in sim.get_defect_counts().items()}, "; lbs:", np.bincount(sim.lbs).tolist())
 
+    # ---- a multi-frame acquisition: one simulator, eight jittered exposures -> register -> average -> denoise, no frame on the host ----
+    from mtflearn_amd.resident import register_stack_device
+    t = time.perf_counter()
+    series = tmd_frames_device([sims[0]] * 8, consistent_defects=True)     # (8, 512, 512) float32, resident
+    dx, dy = _jitter(5, series.shape, 0.0, 0.0)
+    drift = np.random.default_rng(5).uniform(-2.5, 2.5, (8, 2))            # a rigid drift per frame on top of the row jitter
+    drift[0] = 0.0
+    dx += _jitter(6, series.shape, 0.3, 0.0)[0] + drift[:, 1:2]
+    dy += drift[:, 0:1]
+    moved = scan_noise_device(series, _native.DeviceArray.from_numpy(dx), _native.DeviceArray.from_numpy(dy), order=3, mode="grid-wrap")
+    reg = register_stack_device(moved, reference=0, upsample=100, max_shift=8)   # max_shift: a lattice correlates at every lattice vector
+    averaged = denoise_svd_device(reg.mean, size, n_components=8)
+    print(f"series : 8 exposures -> scan noise -> register_stack_device -> denoise_svd in {1e3 * (time.perf_counter() - t):.1f} ms, all resident")
+    print("         drift found, worst error against the drawn one: "
+          f"{np.abs(reg.shifts.numpy() - drift).max():.3f} px; averaged frame {averaged.shape}")
+
     # ---- the refined chain: key points -> centroids -> estimate_d -> bonds -> polygons, nothing but scalars on the host ------
     from mtflearn_amd.distributed import estimate_d_device, find_regions_device, refine_points_device, vnn_graph_device
     t = time.perf_counter()

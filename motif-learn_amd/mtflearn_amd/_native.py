@@ -250,6 +250,12 @@ SYMBOLS = {
     "zk_scan_resample_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                      c_void_p, c_int64, c_void_p]),
     "zk_scan_resample_set_chunk": (c_int, [c_int, c_int64]),
+    "zk_register_shifts": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_int64, c_void_p, c_int, c_int, c_int64, c_int,
+                                   c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "zk_register_shifts_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_int64, c_void_p, c_int, c_int, c_int64,
+                                       c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "zk_stack_mean": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p]),
+    "zk_stack_mean_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "zk_tmd_render": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_int]),
     "zk_tmd_render_dev": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,

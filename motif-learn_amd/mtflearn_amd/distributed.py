@@ -37,6 +37,7 @@ from .resident import __all__ as _resident_names
 from .resident import baseline_device              # noqa: F401  newer than __all__ (as align_device): an attribute here too
 from .resident import scan_noise_device            # noqa: F401  likewise
 from .resident import tmd_frames_device            # noqa: F401  likewise
+from .resident import estimate_shifts_device, shift_stack_device, register_stack_device  # noqa: F401  likewise
 
 __all__ = ["shard_bounds", "one_gpu_rank_env", "RcclComm", "TorchComm", "DeviceCompute", "sharded_patch_moments",
            "sharded_frame_moments", "sharded_frame_maps", "sharded_frames_moments", *_resident_names]

@@ -744,6 +744,103 @@ def scan_noise_device(images, dx, dy, order=1, mode="reflect", out=None):
     return out
 
 
+def _resident_stack(stack, what, floats_only=False):
+    """``(stack, ZK_* code, (B, H, W))`` of the stack operand of a registration entry point."""
+    from .registration import _check_stack_shape
+    shape = _check_stack_shape(stack.shape)
+    stack, code = _device.resident_frame(stack, what, floats_only=floats_only, ndim=3)
+    return stack, code, shape
+
+
+def _estimate_shifts_resident(stack, code, shape, reference, options, planes=False):
+    """``zk_register_shifts_dev`` on checked operands: ``Shifts`` on the device (and the two planes with ``planes``)."""
+    from .registration import REF_PREVIOUS, Shifts, _accumulate, _check_reference, upsampled_size
+    b, h, w = shape
+    mode, index, frame = _check_reference(reference, shape)
+    frame_code = 0
+    if frame is not None:
+        if not getattr(frame, "is_cuda", False) or is_native(frame) != is_native(stack) or frame.device.index != stack.device.index:
+            raise ValueError("a reference frame must be an array of the stack's kind on its device")
+        frame, frame_code = _device.resident_frame(frame, "the reference frame")
+    upsample, lags, norm, win = options
+    shift, peak = _empty_f64((b, 2), stack), _empty_f64((b,), stack)
+    s = upsampled_size(upsample)
+    corr = _empty_f64((b, h, w), stack) if planes else None
+    up = _empty_f64((b, s, s), stack) if planes and upsample > 1 else None
+    ptr = lambda a: c_void_p(a.data_ptr()) if a is not None else None
+    _native.check(_native.load().zk_register_shifts_dev(stack.device.index, ptr(stack), code, b, h, w, mode, index, ptr(frame), frame_code,
+                                                        upsample, lags, norm, win, ptr(shift), ptr(peak), ptr(corr), ptr(up),
+                                                        c_void_p(stream_ptr(stack))), "zk_register_shifts_dev")
+    if mode == REF_PREVIOUS:                       # the running sum is the host's np.cumsum, as in estimate_shifts: B x 2 numbers cross
+        shift = _device.from_host(_accumulate(mode, _device.to_host(shift)), stack)
+    shifts = Shifts(shift, peak)
+    return (shifts, corr, up) if planes else shifts
+
+
+def estimate_shifts_device(stack, reference=0, upsample=100, max_shift=None, normalization=None, window=None):
+    """:func:`mtflearn_amd.registration.estimate_shifts` of a stack resident on the GPU (a torch tensor or a
+    :class:`~mtflearn_amd._native.DeviceArray`, ``(B, H, W)`` of float32 / float64 / uint8 / uint16 / int16; an array
+    ``reference`` is an ``(H, W)`` array of the same kind on the same device).  Returns ``Shifts(shift (B, 2), peak (B,))`` as
+    float64 device arrays of the stack's kind, bit for bit the host function's numbers.  Runs on torch's current stream, which
+    is synchronised before the call returns (the complex fields are released then); with ``reference="previous"`` the
+    ``B x 2`` pairwise shifts cross to the host for the running sum.  Like :func:`scan_noise_device` it is newer than
+    ``__all__`` and is reached as ``resident.estimate_shifts_device``."""
+    from .registration import _check_options
+    options = _check_options(upsample, max_shift, normalization, window)
+    stack, code, shape = _resident_stack(stack, "estimate_shifts_device")
+    return _estimate_shifts_resident(stack, code, shape, reference, options)
+
+
+def _shift_rows_resident(stack, shifts):
+    """The constant shift rows of :func:`shift_stack_device` on the stack's device; ``shifts`` from either side."""
+    from .registration import _check_shifts, _shift_rows
+    shifts = _check_shifts(_device.to_host(shifts) if getattr(shifts, "is_cuda", False) else shifts, int(stack.shape[0]))
+    dx, dy = _shift_rows(shifts, int(stack.shape[1]), int(stack.shape[2]))
+    return _device.from_host(dx, stack), _device.from_host(dy, stack)
+
+
+def shift_stack_device(stack, shifts, order=3, mode="grid-wrap", out=None):
+    """:func:`mtflearn_amd.registration.shift_stack` of a float32 / float64 stack resident on the GPU: ``out[b, y, x] = S_b(y -
+    shifts[b, 0], x - shifts[b, 1])`` in the stack's dtype.  ``shifts`` is ``(B, 2)``, a host array or a device array (what
+    :func:`estimate_shifts_device` returns; its ``B x 2`` numbers cross to the host, where the shift rows are laid out).  It is
+    :func:`scan_noise_device` with the rows ``dx[b, :] = -shifts[b, 1]`` and ``dy[b, :] = -shifts[b, 0]``, bit for bit."""
+    from .denoise import _check_scan_order_mode
+    _check_scan_order_mode(order, mode)
+    stack, _, _ = _resident_stack(stack, "shift_stack_device", floats_only=True)
+    dx, dy = _shift_rows_resident(stack, shifts)
+    return scan_noise_device(stack, dx, dy, order=order, mode=mode, out=out)
+
+
+def stack_mean_device(stack):
+    """The ``(H, W)`` float64 mean of a ``(B, H, W)`` stack resident on the GPU (``zk_stack_mean_dev``): per pixel the sum over
+    ``b`` in ascending order, divided once by ``B``.  Enqueued on torch's current stream without synchronising."""
+    stack, code = _device.resident_frame(stack, "stack_mean_device", ndim=3)
+    b, h, w = (int(v) for v in stack.shape)
+    if 0 in (b, h, w):
+        raise ValueError(f"an empty stack has no mean: shape {(b, h, w)}")
+    out = _empty_f64((h, w), stack)
+    _native.check(_native.load().zk_stack_mean_dev(stack.device.index, c_void_p(stack.data_ptr()), code, b, h, w, c_void_p(out.data_ptr()),
+                                                   c_void_p(stream_ptr(stack))), "zk_stack_mean_dev")
+    return out
+
+
+def register_stack_device(stack, reference=0, upsample=100, max_shift=None, normalization=None, window=None, order=3, mode="grid-wrap",
+                          return_aligned=False):
+    """:func:`mtflearn_amd.registration.register_stack` of a float32 / float64 stack resident on the GPU: ``Registered(mean (H, W)
+    float64, shifts (B, 2), peak (B,), aligned)`` as device arrays of the stack's kind, bit for bit the host function's numbers.
+    No frame crosses to the host (the ``B x 2`` shifts do, for the shift rows), so ``tmd_frames_device -> scan_noise_device ->
+    register_stack_device -> denoise_svd_device`` runs on the device from end to end.  Runs on torch's current stream."""
+    from .denoise import _check_scan_order_mode
+    from .registration import Registered, _check_options
+    options = _check_options(upsample, max_shift, normalization, window)
+    _check_scan_order_mode(order, mode)
+    stack, code, shape = _resident_stack(stack, "register_stack_device", floats_only=True)
+    shifts = _estimate_shifts_resident(stack, code, shape, reference, options)
+    dx, dy = _shift_rows_resident(stack, shifts.shift)
+    aligned = scan_noise_device(stack, dx, dy, order=order, mode=mode)
+    return Registered(stack_mean_device(aligned), shifts.shift, shifts.peak, aligned if return_aligned else None)
+
+
 def denoise_svd_device(image, patch_size, n_components, extraction_step=None, return_s=False):
     """:func:`mtflearn_amd.denoise_svd` of a frame resident on the GPU (a torch tensor or a
     :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` of float32 / float64 / uint8 / uint16 / int16).  Returns the float64

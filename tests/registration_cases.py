@@ -1,0 +1,153 @@
+"""The case table of the registration tests (tests/test_registration_cpu.py, tests/test_gpu_registration.py).
+
+Truth frames: a seeded white-noise frame whose Nyquist row / column is zeroed on even extents, translated through its spectrum
+by a known ``(s_y, s_x)`` -- real and exact, so the answer ``-s`` is known.  Frame 0 of every truth stack is the untranslated
+frame and the reference.
+
+Shapes: (7, 5) and (13, 17) odd and prime, H != W both ways; (16, 16) even, the Nyquist row and column live; (32, 48); (2, 9)
+the thinnest legal extent (its Nyquist row is kept -- it is all the y information there is -- and its y shifts are whole
+pixels, which stay real and exact); one (64, 64).
+upsample: 1 no refinement; 2 and 3 give S = 3 and 5, below any tile; 10 gives S = 15; 100 gives S = 150, which crosses the
+16- and 64-wide tiles of the product kernel with a remainder.
+B: 1, 3 and 70 -- more frames than one workgroup or one wave of per-frame lanes covers, every frame with its own shift.
+Shifts: zero; a coarse peak at flat index 0; one at the last row and column (negative lags); one within half a pixel of the wrap.
+Ties: a constant (16, 16) frame, where every sample of both planes is the same float64 (power-of-two sums are exact).
+Honeycomb: ``datasets.HoneyCombLattice`` (l = 6), drawn twice with the sites displaced by more than half a lattice period, in a
+direction where the lattice-equivalent displacement is shorter but has the larger component (see ``honeycomb``).
+"""
+import numpy as np
+
+import registration_oracle as ro
+
+SHAPES = ((7, 5), (13, 17), (16, 16), (32, 48), (2, 9), (64, 64))
+
+
+def positions(h, w):
+    """``-s`` of the four positions, per shape: zero, flat index 0, last row and column, within half a pixel of the wrap."""
+    if h == 2:
+        return [(0.0, 0.0), (0.0, 0.31), (-1.0, -0.87), (-1.0, w / 2 - 0.27)]
+    return [(0.0, 0.0), (0.31, -0.22), (-1.13, -0.87), (h / 2 - 0.27, -(w / 2) + 0.38)]
+
+
+def coarse_positions(h, w):
+    """The same four for ``upsample = 1``: fractions small enough that the nearest lag is the true one's."""
+    if h == 2:
+        return [(0.0, 0.0), (0.0, 0.2), (-1.0, -0.8), (-1.0, w // 2 - 0.2)]
+    return [(0.0, 0.0), (0.2, -0.15), (-1.1, -0.9), (h // 2 - 0.2, -(w // 2) + 0.2)]
+
+
+def truth_stack(shape, answers, seed):
+    """Frames whose registration onto frame ``base`` is ``answers[b]`` (``= -s``): ``(stack, base)``."""
+    h, w = shape
+    if h == 2:
+        base = np.random.default_rng(seed).standard_normal((h, w))
+        if w % 2 == 0:
+            F = np.fft.fft2(base)
+            F[:, w // 2] = 0
+            base = np.real(np.fft.ifft2(F))
+    else:
+        base = ro.band_limited_noise(h, w, seed)
+    return np.stack([ro.fourier_shift(base, -a[0], -a[1]) for a in answers]), base
+
+
+def _case(name, stack, reference=0, upsample=100, max_shift=None, normalization=None, window=None, truth=None, tie=None):
+    return dict(name=name, stack=stack, reference=reference, upsample=upsample, max_shift=max_shift, normalization=normalization,
+                window=window, truth=None if truth is None else np.asarray(truth, np.float64), tie=tie)
+
+
+UPSAMPLES = {(7, 5): (1, 10, 100), (13, 17): (1, 2, 3, 10, 100), (16, 16): (1, 2, 3, 10, 100), (32, 48): (3, 100), (2, 9): (1, 10, 100),
+             (64, 64): (100,)}
+
+
+def _build():
+    cases = []
+    for k, shape in enumerate(SHAPES):
+        h, w = shape
+        for u in UPSAMPLES[shape]:
+            pos = coarse_positions(h, w) if u == 1 else positions(h, w)
+            for part, answers in (("a", pos[:3]), ("b", [pos[0], pos[3], pos[2]])):      # B = 3, frame 0 the reference
+                stack, _ = truth_stack(shape, answers, 100 + k)
+                cases.append(_case(f"{h}x{w}-u{u}-{part}", stack, upsample=u, truth=answers))
+    # B = 1 against a reference frame given as an array
+    stack, base = truth_stack((13, 17), [(2.37, -3.81)], 7)
+    cases.append(_case("13x17-u100-B1-array", stack, reference=base, truth=[(2.37, -3.81)]))
+    # B = 70, every frame its own shift; the reference is the last frame, by a negative index
+    rng = np.random.default_rng(70)
+    answers = np.round(rng.uniform(-5, 5, (70, 2)), 1) + 0.03       # off the nodes and off the midpoints between them
+    answers[-1] = 0.0
+    stack, _ = truth_stack((13, 17), answers, 8)
+    cases.append(_case("13x17-u10-B70", stack, reference=-1, upsample=10, truth=answers))
+    # dtypes: float32 and the detector formats (quantised, so no exact truth: the oracle on the same numbers is the reference)
+    stack, _ = truth_stack((32, 48), positions(32, 48)[:3], 9)
+    cases.append(_case("32x48-u10-float32", stack.astype(np.float32), upsample=10))
+    q = (stack - stack.min()) / (stack.max() - stack.min())
+    cases.append(_case("32x48-u10-uint8", np.round(q * 255).astype(np.uint8), upsample=10))
+    cases.append(_case("32x48-u10-uint16", np.round(q * 65535).astype(np.uint16), upsample=10))
+    # options, each on two shapes
+    for shape, seed in (((13, 17), 10), ((32, 48), 11)):
+        h, w = shape
+        stack, _ = truth_stack(shape, positions(h, w)[:3], seed)
+        cases.append(_case(f"{h}x{w}-u10-phase", stack, upsample=10, normalization="phase", truth=positions(h, w)[:3]))
+        cases.append(_case(f"{h}x{w}-u10-hann", stack, upsample=10, window="hann"))
+    # "previous": frame b against frame b - 1
+    stack, _ = truth_stack((16, 16), [(0.0, 0.0), (0.4, -0.3), (1.1, 0.2), (0.6, 1.4)], 12)
+    cases.append(_case("16x16-u10-previous", stack, reference="previous", upsample=10))
+    # the two flat-top ties: the first index wins, lag (0, 0) and then node (0, 0) of the upsampled grid
+    flat = np.ones((2, 16, 16))
+    cases.append(_case("16x16-u1-tie", flat, upsample=1, tie=(0.0, 0.0)))
+    cases.append(_case("16x16-u10-tie", flat, upsample=10, tie=(-0.7, -0.7)))     # S = 15, off = 7: (0 - 7) / 10
+    return cases
+
+
+HONEY_L = 6.0
+HONEY_SIZE = 64
+HONEY_ANSWER = (-5.0, 3.4)      # (dy, dx) that registers the displaced frame: length 6.05, half a period is 5.196
+HONEY_MAX_SHIFT = 5.2
+
+
+def honeycomb():
+    """``(stack (2, 64, 64), true answer, max_shift)``.  Frame 1 is the lattice displaced by ``-answer``; the lattice vector
+    ``(dy, dx) = (-5.196, 9)`` makes ``(0.196, -5.6)`` an equivalent answer: shorter, so more of the two frames overlaps and
+    the plain correlation is higher there, but with a component beyond ``max_shift = 5.2``, inside which ``answer`` is the only
+    equivalent.  Gaussians of sigma ``l / 4`` on the sites of a larger ``HoneyCombLattice``, summed in NumPy."""
+    from mtflearn_amd.datasets import HoneyCombLattice
+    margin = 16
+    lattice = HoneyCombLattice(size=HONEY_SIZE + 2 * margin, l=HONEY_L, random_shift=False)
+    sites = np.concatenate(lattice.get_points()) - margin                       # (x, y)
+    yy, xx = np.mgrid[0:HONEY_SIZE, 0:HONEY_SIZE].astype(np.float64)
+    sigma = HONEY_L / 4
+
+    def draw(dy, dx):
+        img = np.zeros((HONEY_SIZE, HONEY_SIZE))
+        for x, y in sites:
+            img += np.exp(-((xx - (x + dx)) ** 2 + (yy - (y + dy)) ** 2) / (2 * sigma ** 2))
+        return img
+
+    return np.stack([draw(0.0, 0.0), draw(-HONEY_ANSWER[0], -HONEY_ANSWER[1])]), np.array(HONEY_ANSWER), HONEY_MAX_SHIFT
+
+
+CASES = _build()
+PLANE_CASES = ("13x17-u100-a", "16x16-u10-b", "32x48-u100-b")       # the cases whose two planes are compared sample by sample
+
+
+def by_name(name):
+    return next(c for c in CASES if c["name"] == name)
+
+
+def options(case):
+    return {k: case[k] for k in ("reference", "upsample", "max_shift", "normalization", "window")}
+
+
+def wrapped_error(got, want, shape):
+    """Per-axis distance modulo the extent: a peak next to the wrap may come back one period away."""
+    d = np.asarray(got) - np.asarray(want)
+    n = np.asarray(shape, np.float64)
+    return np.abs((d + n / 2) % n - n / 2)
+
+
+def end_to_end():
+    """The feature's purpose: ``(stack (8, 64, 64), base, answers)`` of a truth stack at random sub-pixel drifts."""
+    answers = np.round(np.random.default_rng(5).uniform(-3, 3, (8, 2)), 3)
+    answers[0] = 0.0
+    stack, base = truth_stack((64, 64), answers, 13)
+    return stack, base, answers
