@@ -721,6 +721,67 @@ int zk_com_refine_points_dev(int device, const void* image_dev, int image_dtype,
                              int points_dtype, int64_t n, int64_t size, int threshold, double* out_dev, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Gaussian fits of key points: a least-squares fit of a 2-D Gaussian to the window of every key point.  No plan involved, and
+ * no counterpart in the reference: this section is the definition.
+ * image: (H, W) of ZK_F32 or ZK_F64.  corners: n int32 pairs (cx, cy); window i is image[cy : cy + size, cx : cx + size],
+ * 3 <= size <= 32, widened to float64.  mask: ZK_GAUSS_BOX fits every pixel of the window, ZK_GAUSS_DISK (odd size only) the
+ * pixels with (row - r)^2 + (col - r)^2 <= r^2, r = size / 2 (integer division).  The fitted pixels must outnumber the parameters.
+ *
+ * Model, in window coordinates, dx = col - x0, dy = row - y0:
+ *   ZK_GAUSS_ELLIPTICAL  f = g + A exp(-(a dx^2 + 2 b dx dy + c dy^2) / 2), parameters p = (A, x0, y0, a, b, c, g)
+ *   ZK_GAUSS_CIRCULAR    the same with b = 0 and c = a, parameters p = (A, x0, y0, a, g)
+ * (the entries of the precision matrix, not widths and an angle: the problem stays regular where the column is round).
+ * With r_i = pixel_i - f_i, J the derivatives of f, the sums J^T J, J^T r and rss = sum r_i^2 run over the fitted pixels.
+ *
+ * Start: g = the minimum of the fitted pixels, A = their maximum less that minimum, x0 = y0 = size / 2 (integer division: the pixel
+ * the key point rounds to, so the fit is a function of the window alone and a point gives the same result through either entry
+ * point), a = c = 1 / sigma0^2, b = 0, lambda = 1e-3.  The sums of the start are taken first; that is not an iteration.
+ * Iteration (Levenberg-Marquardt with Marquardt's scaling), until a stop below:
+ *   1. if `max_iter` iterations have been made, stop with status 1; otherwise this is one more iteration;
+ *   2. solve (J^T J + lambda diag(J^T J)) delta = J^T r by Cholesky; trial = p + delta;
+ *   3. the trial is ACCEPTED when no pivot failed (every pivot > 0), every entry of the trial is finite, the form is positive
+ *      definite (a > 0, c > 0, a c - b^2 > 0), the centre lies in [-0.5, size - 0.5] on both axes, and rss(trial) <= rss(p);
+ *   4. accepted: p = trial, lambda = max(lambda / 10, 1e-12), and if |delta_k| <= tol (|p_k| + 1) for every parameter (p the
+ *      accepted trial) stop with status 0;
+ *   5. otherwise: p stays, lambda = lambda * 10, and if lambda > 1e12 stop with status 2.
+ * status: ZK_GAUSS_CONVERGED 0; ZK_GAUSS_MAX_ITER 1; ZK_GAUSS_STALLED 2 (lambda passed 1e12, or the fitted pixels are all
+ * equal: then the start is returned with no iteration and rss 0); ZK_GAUSS_NOT_FINITE 3 (a fitted pixel is NaN or inf: the eight
+ * outputs are NaN, no iteration).  Status 1 and 2 return the last accepted parameters.  iterations counts every pass through 1.
+ *
+ * params (n, 8) float64: x = (double)cx + x0, y = (double)cy + y0 (one rounded addition each), A, sigma_major = 1 / sqrt(l1),
+ * sigma_minor = 1 / sqrt(l2) with l1 <= l2 the eigenvalues of [[a, b], [b, c]] (l2 = (a + c) / 2 + sqrt(((a - c) / 2)^2 + b^2),
+ * l1 = (a c - b^2) / l2; the circular model: both are 1 / sqrt(a)), theta = atan2(-2 b, c - a) / 2, the angle of the major axis
+ * from the x axis towards y, in (-pi/2, pi/2] (0 for the circular model; -2 b is formed as 0 - 2 b, so b = 0 gives 0 or pi/2,
+ * never -pi/2), g, rss.
+ * iterations and status: n int32 each.
+ *
+ * One kernel launch for all points, one wave a point, the window in registers, no global scratch; the lanes' sums are joined in
+ * an order that depends on size alone and there are no floating-point atomics, so two runs and the two entry points agree bit
+ * for bit.  zk_gauss_fit takes and fills host arrays and checks every window before anything is launched.
+ * zk_gauss_fit_points_dev takes device arrays on hip_stream and key points, ZK_I32 or ZK_F64 pairs (x, y): the corner is
+ * rint(point) - size / 2, computed on the device; a window that leaves the frame raises a flag there and nothing is written for
+ * that point.  The stream is synchronised before it returns (the flag crosses to the host).
+ *
+ * Errors (ZK_E_BADARG, nothing returned): a dtype other than the two float types, n >= 2^24, size outside [3, 32], an unknown
+ * model or mask, the disk with an even size, no more fitted pixels than parameters (the disk at size 3), sigma0 not positive and
+ * finite, tol negative or not finite, max_iter outside [1, 10000], a window that leaves the frame.
+ * ------------------------------------------------------------------------------------------------------ */
+#define ZK_GAUSS_CIRCULAR   0
+#define ZK_GAUSS_ELLIPTICAL 1
+#define ZK_GAUSS_BOX  0
+#define ZK_GAUSS_DISK 1
+#define ZK_GAUSS_CONVERGED  0
+#define ZK_GAUSS_MAX_ITER   1
+#define ZK_GAUSS_STALLED    2
+#define ZK_GAUSS_NOT_FINITE 3
+int zk_gauss_fit(int device, const void* image_host, int image_dtype, int64_t H, int64_t W, const int32_t* corners_host, int64_t n,
+                 int64_t size, int model, int mask, double sigma0, double tol, int64_t max_iter, double* params_out,
+                 int32_t* iterations_out, int32_t* status_out);
+int zk_gauss_fit_points_dev(int device, const void* image_dev, int image_dtype, int64_t H, int64_t W, const void* points_dev,
+                            int points_dtype, int64_t n, int64_t size, int model, int mask, double sigma0, double tol, int64_t max_iter,
+                            double* params_dev, int32_t* iterations_dev, int32_t* status_dev, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * The device passes of the reference's estimate_d (graph/vnn.py:18-40): the bond length vnn_graph cuts at when no dmax is given.
  * No plan involved.
  *

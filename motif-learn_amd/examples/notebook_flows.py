@@ -148,6 +148,12 @@ def main():
     from mtflearn_amd.distributed import com_refine_device
     cut = com_refine_device(clean, d_keep, 9)                              # reference: com_refine(pts, img, 9); Li per window, 'otsu' on request
     print(f"         thresholded centroids (9 x 9 windows, Li) differ from the plain ones by at most {np.nanmax(np.abs(cut.numpy() - atoms.numpy())):.2f} px")
+    from mtflearn_amd import resident
+    fit, steps, status = resident.gaussian_fit_device(clean, d_keep, 9, model="circular")   # a 2-D Gaussian per column: (N, 8) x, y, A, widths, angle, g, rss
+    fit = fit.numpy()
+    print(f"         Gaussian fits (9 x 9, circular): {int((status.numpy() == 0).sum())} of {len(fit)} converged in at most {int(steps.numpy().max())} steps,"
+          f" median width {np.median(fit[:, 3]):.2f} px, amplitude {np.median(fit[:, 2]):.3g}; centres differ from the centroids by at most"
+          f" {np.nanmax(np.abs(fit[:, :2] - atoms.numpy())):.2f} px")
 
     # ---- back from moments: what does each k-means class look like? ------------------------------------------------
     from mtflearn_amd.clustering import DeviceRows, kmeans_fit

@@ -22,6 +22,10 @@ ZK_I32 = 5                         # int32 key points (local_max): zk_voronoi_ce
 VORONOI_NEIGHBOURS, VORONOI_GRAPH = 0, 1                           # zk_voronoi_cells modes
 REFINE_BOX, REFINE_DISK = 0, 1                                     # zk_refine_points modes
 THRESHOLD_LI, THRESHOLD_OTSU = 0, 1                                # zk_com_refine thresholds
+GAUSS_CIRCULAR, GAUSS_ELLIPTICAL = 0, 1                            # zk_gauss_fit models
+GAUSS_BOX, GAUSS_DISK = 0, 1                                       # zk_gauss_fit masks
+GAUSS_CONVERGED, GAUSS_MAX_ITER, GAUSS_STALLED, GAUSS_NOT_FINITE = 0, 1, 2, 3   # zk_gauss_fit status codes
+GAUSS_MODELS = {"circular": GAUSS_CIRCULAR, "elliptical": GAUSS_ELLIPTICAL}
 ALIGN_DISTANCE, ALIGN_COSINE = 0, 1                                # zk_align_rows keys
 ALIGN_KEYS = {"distance": ALIGN_DISTANCE, "cosine": ALIGN_COSINE}
 EELS_WHITTAKER, EELS_ALS, EELS_ARPLS, EELS_AIRPLS = 0, 1, 2, 3      # zk_eels_pls modes
@@ -161,6 +165,10 @@ SYMBOLS = {
                                   c_void_p]),
     "zk_com_refine_points_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p,
                                          c_void_p]),
+    "zk_gauss_fit": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_double, c_double, c_int64,
+                             c_void_p, c_void_p, c_void_p]),
+    "zk_gauss_fit_points_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int64, c_int64, c_int, c_int, c_double,
+                                        c_double, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "zk_knn_distances": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_void_p]),
     "zk_knn_distances_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p]),
     "zk_knn_stats": (c_int, [c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),

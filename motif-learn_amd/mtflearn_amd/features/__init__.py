@@ -9,7 +9,7 @@ from .moments import (zmoments, construct_rot_maps_matrix, construct_complex_mat
 from .pickers import (estimate_patch_size, radial_profile, autocorrelation, estimate_n_max, estimate_n_max_from_patch,
                       _get_cumulative_energy)
 from .consumers import pca
-from .keypoints import KeyPoints, com_refine_points, refine_points
+from .keypoints import GaussianFit, KeyPoints, com_refine_points, gaussian_fit_points, refine_points
 from .peaks import local_max
 from .window_size import (compute_autocorrelation, get_characteristic_length, get_characteristic_length_fft,
                           fft_power_spectrum, angular_average)
@@ -25,6 +25,6 @@ def baseline_correction(y, niter=10):
 __all__ = ["ZPs", "zmoments", "construct_rot_maps_matrix", "construct_complex_matrix",
            "construct_real_matrix", "nm2j", "nm2j_complex", "check_array1d",
            "estimate_patch_size", "radial_profile", "autocorrelation", "estimate_n_max", "estimate_n_max_from_patch", "pca",
-           "KeyPoints", "refine_points", "com_refine_points", "local_max", "baseline_correction",
+           "KeyPoints", "refine_points", "com_refine_points", "gaussian_fit_points", "GaussianFit", "local_max", "baseline_correction",
            "compute_autocorrelation", "get_characteristic_length", "get_characteristic_length_fft", "fft_power_spectrum",
            "angular_average"]

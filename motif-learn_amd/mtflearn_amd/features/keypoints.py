@@ -10,9 +10,12 @@ of / above the frame comes back empty or short from NumPy's slicing and makes th
 """
 from __future__ import annotations
 
+from collections import namedtuple
+
 import numpy as np
 
-__all__ = ["disk_patch", "center_of_mass_refine", "refine_points", "com_refine", "com_refine_points", "clear_border", "KeyPoints"]
+__all__ = ["disk_patch", "center_of_mass_refine", "refine_points", "com_refine", "com_refine_points", "gaussian_fit_points",
+           "GaussianFit", "clear_border", "KeyPoints"]
 
 
 def _interior(pts, x_limit, y_limit, size):
@@ -152,6 +155,92 @@ def com_refine_points(pts, img, size, threshold=None, return_thresholds=False):
     return (out, levels, steps) if return_thresholds else out
 
 
+GaussianFit = namedtuple("GaussianFit", "xy amplitude sigma theta background rss iterations status kept")
+
+
+def gaussian_fit_options(size, model, mode, sigma, tol, max_iter):
+    """``(size, model code, mask code, sigma0, tol, max_iter)`` of a Gaussian fit, as ``zk_gauss_fit`` takes them; what it would
+    refuse is a ``ValueError`` here, before any device call (shared with ``resident.gaussian_fit_device``)."""
+    from .. import _native
+    if isinstance(size, bool) or int(size) != size or not 3 <= int(size) <= 32:
+        raise ValueError(f"size must be an integer in [3, 32], not {size}")
+    size = int(size)
+    if model not in _native.GAUSS_MODELS:
+        raise ValueError(f"model must be 'circular' or 'elliptical', not {model!r}")
+    if mode not in (None, 'disk'):
+        raise ValueError(f"mode must be None or 'disk', not {mode!r}")
+    if mode == 'disk' and size % 2 == 0:
+        raise ValueError(f"mode='disk' needs an odd size, not {size}")
+    n_params = 7 if model == "elliptical" else 5
+    n_pixels = int(disk_patch(size // 2).sum()) if mode == 'disk' else size * size
+    if n_pixels <= n_params:
+        raise ValueError(f"the {model} model has {n_params} parameters and the window only {n_pixels} fitted pixels: "
+                         "a larger size or the box is needed")
+    sigma = size / 4 if sigma is None else float(sigma)
+    if not (sigma > 0 and np.isfinite(sigma)):
+        raise ValueError(f"sigma must be positive and finite, not {sigma}")
+    tol = float(tol)
+    if not (tol >= 0 and np.isfinite(tol)):
+        raise ValueError(f"tol must be finite and not negative, not {tol}")
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or not 1 <= int(max_iter) <= 10000:
+        raise ValueError(f"max_iter must be an integer in [1, 10000], not {max_iter}")
+    return size, _native.GAUSS_MODELS[model], _native.GAUSS_DISK if mode == 'disk' else _native.GAUSS_BOX, sigma, tol, int(max_iter)
+
+
+def gaussian_fit_points(pts, img, size, model="elliptical", mode=None, sigma=None, tol=1e-10, max_iter=100, clear=True):
+    """Least-squares fit of a 2-D Gaussian to the ``size x size`` window of every key point, on the GPU (``zk_gauss_fit``:
+    Levenberg-Marquardt, one wave a point; the algorithm is written out in ``include/zernike_hip.h``).  NumPy in, a
+    :class:`GaussianFit` of NumPy arrays out: ``xy`` ``(M, 2)`` the fitted centres in frame coordinates, ``amplitude``,
+    ``sigma`` ``(M, 2)`` the major and minor widths (equal for the circular model), ``theta`` the angle of the major axis in
+    ``(-pi/2, pi/2]`` (0 for the circular model), ``background``, ``rss``, ``iterations`` and ``status`` (int32: 0 converged,
+    1 ``max_iter`` reached, 2 the damping passed 1e12 or the window is constant, 3 a fitted pixel is NaN or inf -- then the
+    parameters are NaN) and ``kept``, the indices into ``pts`` of the fitted points.
+
+    The window convention is :func:`com_refine_points`'s: with ``clear`` the points are filtered by
+    ``clear_border(pts, img.shape, size)``; the window of a kept point starts at ``np.rint(pt).astype(int) - size // 2``.
+    With ``clear=False`` every window must lie inside the frame, or ``ValueError`` is raised.  The fit starts at the window's
+    centre pixel (the pixel the point rounds to) with width ``sigma`` (default ``size / 4``), so it depends on the window
+    alone.  ``model`` is ``'elliptical'`` (7 parameters) or ``'circular'`` (5); ``mode='disk'`` fits only the pixels of
+    ``disk_patch(size // 2)`` and needs an odd ``size``.  ``img`` must be a 2-D float32 or float64 frame, ``3 <= size <= 32``,
+    ``len(pts) < 2^24``; every refusal is a ``ValueError`` before the first device call, and there is no CPU fallback.  Empty
+    ``pts`` returns empty arrays without touching the device."""
+    from ctypes import c_void_p
+    from .. import _native
+    img, pts = np.asarray(img), np.asarray(pts)
+    if img.ndim != 2 or img.dtype not in (np.float32, np.float64):
+        raise ValueError(f"gaussian_fit_points needs a 2-D float32 or float64 frame, not {img.ndim}-D {img.dtype}")
+    if pts.size == 0:
+        pts = pts.reshape(0, 2).astype(np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 2 or pts.dtype.kind not in "iuf":
+        raise ValueError(f"gaussian_fit_points needs real points of shape (N, 2), not {pts.dtype} {pts.shape}")
+    size, model_code, mask_code, sigma, tol, max_iter = gaussian_fit_options(size, model, mode, sigma, tol, max_iter)
+    if pts.dtype.kind == "f" and not np.isfinite(pts).all():
+        raise ValueError("gaussian_fit_points needs finite points")
+    if len(pts) >= 2 ** 24:
+        raise ValueError("gaussian_fit_points needs len(pts) < 2^24")
+    height, width = img.shape
+    if clear:
+        margin = size // 2 + 1                                                                 # clear_border's rule, as indices
+        kept = np.flatnonzero((pts[:, 0] > margin) & (pts[:, 0] < width - margin) & (pts[:, 1] > margin) & (pts[:, 1] < height - margin))
+    else:
+        kept = np.arange(len(pts))
+    kept = kept.astype(np.int64)
+    first = np.rint(pts[kept]).astype(int) - size // 2
+    if len(first) and (first.min() < 0 or (first[:, 0] + size > width).any() or (first[:, 1] + size > height).any()):
+        raise ValueError("gaussian_fit_points needs every window inside the frame")
+    params, steps, status = np.empty((len(kept), 8), np.float64), np.empty(len(kept), np.int32), np.empty(len(kept), np.int32)
+    if len(kept):
+        img, first = np.ascontiguousarray(img), np.ascontiguousarray(first, dtype=np.int32)
+        lib = _native.load()
+        _native.require_device()
+        _native.check(lib.zk_gauss_fit(_native.default_device(), img.ctypes.data_as(c_void_p), _native.dtype_code(img.dtype), height, width,
+                                       first.ctypes.data_as(c_void_p), len(first), size, model_code, mask_code, sigma, tol, max_iter,
+                                       params.ctypes.data_as(c_void_p), steps.ctypes.data_as(c_void_p), status.ctypes.data_as(c_void_p)),
+                      "zk_gauss_fit")
+    return GaussianFit(params[:, 0:2].copy(), params[:, 2].copy(), params[:, 3:5].copy(), params[:, 5].copy(), params[:, 6].copy(),
+                       params[:, 7].copy(), steps, status, kept)
+
+
 class KeyPoints:
     """Key points of an image together with a window size (``_keypoint.py:53-92``)."""
 
@@ -193,3 +282,8 @@ class KeyPoints:
         """:meth:`refine` on the GPU (extension, in the spirit of :meth:`moments`): the same truncation ``pts.astype(int)``, the
         same numbers (:func:`refine_points`)."""
         self.pts = refine_points(self.img if data is None else data, self.pts.astype(int), size=r, mode=mode)
+
+    def fit_gaussians(self, size=None, **kw):
+        """The :class:`GaussianFit` of the points on the image (:func:`gaussian_fit_points`, on the GPU; extension).  ``size``
+        defaults to the object's; the keywords are that function's.  The object is left as it is."""
+        return gaussian_fit_points(self.pts, self.img, self.size if size is None else size, **kw)

@@ -862,3 +862,35 @@ def denoise_svd_memory_view_device(image, patch_size, n_components=None, thresho
     image = _device.resident_frame(image, "denoise_svd_memory_view_device")[0]
     p = _memory_view_patch(tuple(int(v) for v in image.shape), patch_size)
     return _memory_view_device(image, p, n_components, threshold)
+
+
+def gaussian_fit_device(image, points, size, model="elliptical", mode=None, sigma=None, tol=1e-10, max_iter=100):
+    """:func:`mtflearn_amd.features.gaussian_fit_points` of a frame and key points resident on the GPU: ``image`` ``(H, W)``
+    float32 / float64, ``points`` ``(N, 2)`` int32 or float64 ``(x, y)`` (what :func:`local_max_device`,
+    :func:`refine_points_device` or :func:`com_refine_device` return), both torch tensors or both
+    :class:`~mtflearn_amd._native.DeviceArray`.  Returns ``(params, iterations, status)`` as device arrays of the same kind:
+    ``params`` ``(N, 8)`` float64 with columns ``x, y, amplitude, sigma_major, sigma_minor, theta, background, rss``,
+    ``iterations`` and ``status`` ``(N)`` int32 (the codes of the host function).  ``params[:, :2]`` is what
+    :func:`vnn_graph_device` and :func:`estimate_d_device` accept (contiguous for a torch tensor after ``.contiguous()``).
+    The corner ``rint(point) - size // 2`` is formed on the device and the fit depends on the window alone: a point gives the
+    same bits here and through the host function.  There is NO border clearing: every ``size x size`` window must lie inside
+    the frame, or ``ValueError`` is raised (the windows are checked on the device: nothing is written for such a point, and
+    only the flag crosses to the host) -- the contract of :func:`com_refine_device`.  The options are the host function's and
+    are checked before any device call.  Runs on torch's current stream.
+
+    Newer than the move out of :mod:`mtflearn_amd.distributed`: this function is reached as ``resident.gaussian_fit_device``
+    and is not part of ``__all__``."""
+    from .features.keypoints import gaussian_fit_options
+    image, code, points, points_code = _device.resident_frame_points(image, points, "gaussian_fit_device", ("int32", "float64"))
+    size, model_code, mask_code, sigma, tol, max_iter = gaussian_fit_options(size, model, mode, sigma, tol, max_iter)
+    n = int(points.shape[0])
+    h, w = (int(v) for v in image.shape)
+    params = _empty_f64((n, 8), image)
+    steps, status = _device.empty((n,), np.int32, image), _device.empty((n,), np.int32, image)
+    if n:
+        rc = _native.load().zk_gauss_fit_points_dev(image.device.index, c_void_p(image.data_ptr()), code, h, w, c_void_p(points.data_ptr()),
+                                                    points_code, n, size, model_code, mask_code, sigma, tol, max_iter,
+                                                    c_void_p(params.data_ptr()), c_void_p(steps.data_ptr()), c_void_p(status.data_ptr()),
+                                                    c_void_p(stream_ptr(image)))
+        _device.check_refusal(rc, "zk_gauss_fit_points_dev")
+    return params, steps, status
