@@ -1,7 +1,8 @@
 // zk_com_refine.hip -- the reference's thresholded centroid refinement (features/_keypoint.py, com_refine) on the device: a
 // size x size window is cut at every key point, thresholded with Li's rule or with Otsu's, what lies below the threshold
-// counts as zero, and the point moves to the centroid of what is left.  A file of its own beside zk_refine.hip (whose bin rule
-// it restates value by value), built with the same -ffp-contract=off: every product and sum below is rounded once.
+// counts as zero, and the point moves to the centroid of what is left.  A file of its own beside zk_refine.hip, built with the same
+// -ffp-contract=off: every product and sum below is rounded once.  The window's corner is zk_point_window.h's, the histogram's
+// bin rule zk_np_bins.h's.
 //
 // One launch, one workgroup per window, no global scratch and no floating-point atomics.  A window of at most 256 pixels
 // (size <= 16) is worked on by ONE WAVE (a workgroup of 64 lanes: four pixels a lane at most), a larger one by a workgroup of
@@ -32,19 +33,16 @@
 // loads of a window are rows of `size` neighbouring pixels; what binds the kernel has not been measured beyond whole-call times.
 #include <math.h>
 
-#include "zk_internal.h"
-#include "zk_scratch.h"
+#include "zk_np_bins.h"
+#include "zk_point_window.h"
 
 namespace {
 
-constexpr int BINS = 256;                            // np.histogram(bins=256)
 constexpr int MIN_SIZE = 2, MAX_SIZE = 64;           // the side of a window
 constexpr int WAVE_AREA = 256;                       // windows up to this many pixels take one wave, larger ones four
 constexpr int LI_MAX_ITERATIONS = 1000;
-constexpr int CORNERS = -1;                          // the points are int32 window corners (zk_com_refine, zk_com_refine_dev)
-constexpr double POINT_LIMIT = 1073741824.0;         // |rint(point)| below 2^30: the corner is an int
 
-enum { ERR_WINDOW = 1, ERR_LI = 2 };
+enum { ERR_LI = 2 };                                 // beside ERR_WINDOW in the flag word
 
 struct op_add {
   __device__ double operator()(double a, double b) const { return a + b; }
@@ -99,13 +97,7 @@ __device__ inline double otsu_threshold(const double* w, int area, double lo, do
     if (k < BINS) hist[k] = 0;
   }
   __syncthreads();
-  for (int i = t; i < area; i += NT) {
-    const double v = w[i], f = ((v - lo) / (hi - lo)) * (double)BINS;
-    int b = f >= (double)BINS ? BINS - 1 : (f > 0 ? (int)f : 0);           // truncation; 256 folds into 255 (a NaN goes to 0)
-    if (v < edge[b] && b > 0) --b;
-    if (v >= edge[b + 1] && b != BINS - 1) ++b;
-    atomicAdd(&hist[b], 1);
-  }
+  for (int i = t; i < area; i += NT) atomicAdd(&hist[np_bin(w[i], lo, hi, edge)], 1);
   __syncthreads();
   if (t < 2) {                                       // np.cumsum is sequential: lane 0 upwards, lane 1 downwards
     double acc = 0;
@@ -214,32 +206,14 @@ __global__ __launch_bounds__(NT) void com_refine_kernel(const T* __restrict__ im
   const long long n = blockIdx.x;
   double *w = lds, *work = lds + area;
   // the corner of the window: uniform over the workgroup, so every exit below is taken by all lanes
-  double px = 0, py = 0;
-  long long x0, y0;
-  bool inside = true;
-  if (pts_dtype == CORNERS) {
-    x0 = ((const int*)pts)[2 * n];
-    y0 = ((const int*)pts)[2 * n + 1];
-  } else {
-    if (pts_dtype == ZK_I32) {
-      px = (double)((const int*)pts)[2 * n];
-      py = (double)((const int*)pts)[2 * n + 1];
-    } else {
-      px = ((const double*)pts)[2 * n];
-      py = ((const double*)pts)[2 * n + 1];
-    }
-    const double rx = rint(px), ry = rint(py);
-    inside = fabs(rx) < POINT_LIMIT && fabs(ry) < POINT_LIMIT;             // false for a NaN
-    x0 = inside ? (long long)rx - size / 2 : 0;
-    y0 = inside ? (long long)ry - size / 2 : 0;
-  }
-  if (!inside || x0 < 0 || y0 < 0 || x0 + size > W || y0 + size > H) {
+  const point_window at = window_at(pts, pts_dtype, n, size, H, W);
+  if (!at.inside) {
     if (t == 0) atomicOr(flag, ERR_WINDOW);
     return;
   }
   double range[2] = {INFINITY, -INFINITY};
   for (int i = t; i < area; i += NT) {
-    const double v = (double)img[(y0 + i / size) * W + x0 + i % size];
+    const double v = (double)img[(at.y0 + i / size) * W + at.x0 + i % size];
     w[i] = v;
     range[0] = fmin(range[0], v);
     range[1] = fmax(range[1], v);
@@ -271,8 +245,8 @@ __global__ __launch_bounds__(NT) void com_refine_kernel(const T* __restrict__ im
   if (t == 0) {
     double x = sums[2] / sums[0], y = sums[1] / sums[0];
     if (pts_dtype != CORNERS) {
-      x = (x - (double)size / 2) + px;
-      y = (y - (double)size / 2) + py;
+      x = (x - (double)size / 2) + at.px;
+      y = (y - (double)size / 2) + at.py;
     }
     out[2 * n] = x;
     out[2 * n + 1] = y;
@@ -283,18 +257,13 @@ __global__ __launch_bounds__(NT) void com_refine_kernel(const T* __restrict__ im
 
 int check_com(const char* who, const void* img, int dtype, int64_t H, int64_t W, const void* pts, int64_t n, int64_t size, int threshold,
               const void* out) {
+  int rc;
+  if ((rc = check_frame(who, img, dtype, H, W, n))) return rc;
   const std::string name(who);
-  if (dtype != ZK_F32 && dtype != ZK_F64) return zk_fail(ZK_E_BADARG, name + ": the frame must be ZK_F32 or ZK_F64 (a float frame)");
-  if (H <= 0 || W <= 0 || H > ((int64_t)1 << 31) - 1 || W > ((int64_t)1 << 31) - 1 || !img)
-    return zk_fail(ZK_E_BADARG, name + ": needs a frame with 0 < H, W < 2^31");
-  if (n < 0 || n >= ((int64_t)1 << 24)) return zk_fail(ZK_E_BADARG, name + ": needs 0 <= n_points < 2^24");
   if (size < MIN_SIZE || size > MAX_SIZE) return zk_fail(ZK_E_BADARG, name + ": needs 2 <= size <= 64");
   if (threshold != ZK_THRESHOLD_LI && threshold != ZK_THRESHOLD_OTSU) return zk_fail(ZK_E_BADARG, name + ": unknown threshold");
-  if (n && (!pts || !out)) return zk_fail(ZK_E_BADARG, name + ": null pointer");
-  return 0;
+  return check_pointers(who, n, pts && out);
 }
-
-const char* const WINDOW_MESSAGE = ": a window leaves the frame (every corner needs 0 <= x0 <= W - size, 0 <= y0 <= H - size)";
 
 template <typename T, int NT>
 int com_launch(const void* img, int64_t H, int64_t W, const void* pts, int pts_dtype, int64_t n, int size, int padded, int otsu,
@@ -310,26 +279,22 @@ int com_launch(const void* img, int64_t H, int64_t W, const void* pts, int pts_d
 int com_call(const char* who, const void* img, int dtype, int64_t H, int64_t W, const void* pts, int pts_dtype, int64_t n, int size,
              int threshold, double* out, double* thresholds, int* iterations, hipStream_t s) {
   if (n == 0) return 0;
-  int rc;
-  dev_buf d_flag;
-  if ((rc = d_flag.alloc(16))) return rc;
-  ZK_HIP(hipMemsetAsync(d_flag.p, 0, 16, s));
+  int rc, flags;
+  dev_flag flag;
+  if ((rc = flag.arm(s))) return rc;
   const int area = size * size, otsu = threshold == ZK_THRESHOLD_OTSU;
   int padded = 2;
   while (padded < area) padded <<= 1;
   const size_t tables = sizeof(double) * (3 * BINS + 1) + sizeof(int) * 2 * BINS;
   const size_t lds = sizeof(double) * area + (otsu ? tables : sizeof(double) * padded);
   if (area <= WAVE_AREA)
-    rc = dtype == ZK_F32 ? com_launch<float, 64>(img, H, W, pts, pts_dtype, n, size, padded, otsu, lds, out, thresholds, iterations, d_flag.as<int>(), s)
-                         : com_launch<double, 64>(img, H, W, pts, pts_dtype, n, size, padded, otsu, lds, out, thresholds, iterations, d_flag.as<int>(), s);
+    rc = dtype == ZK_F32 ? com_launch<float, 64>(img, H, W, pts, pts_dtype, n, size, padded, otsu, lds, out, thresholds, iterations, flag.word(), s)
+                         : com_launch<double, 64>(img, H, W, pts, pts_dtype, n, size, padded, otsu, lds, out, thresholds, iterations, flag.word(), s);
   else
-    rc = dtype == ZK_F32 ? com_launch<float, 256>(img, H, W, pts, pts_dtype, n, size, padded, otsu, lds, out, thresholds, iterations, d_flag.as<int>(), s)
-                         : com_launch<double, 256>(img, H, W, pts, pts_dtype, n, size, padded, otsu, lds, out, thresholds, iterations, d_flag.as<int>(), s);
-  if (rc) return rc;
-  int flags = 0;
-  ZK_HIP(hipMemcpyAsync(&flags, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  ZK_HIP(hipStreamSynchronize(s));                   // the flag crosses to the host
-  if (flags & ERR_WINDOW) return zk_fail(ZK_E_BADARG, std::string(who) + WINDOW_MESSAGE);
+    rc = dtype == ZK_F32 ? com_launch<float, 256>(img, H, W, pts, pts_dtype, n, size, padded, otsu, lds, out, thresholds, iterations, flag.word(), s)
+                         : com_launch<double, 256>(img, H, W, pts, pts_dtype, n, size, padded, otsu, lds, out, thresholds, iterations, flag.word(), s);
+  if (rc || (rc = flag.read(s, &flags))) return rc;
+  if (flags & ERR_WINDOW) return window_fail(who);
   if (flags & ERR_LI) return zk_fail(ZK_E_BADARG, std::string(who) + ": Li's iteration has not ended after 1000 steps in a window");
   return 0;
 }
@@ -362,24 +327,15 @@ extern "C" int zk_com_refine(int device, const void* image_host, int image_dtype
                              int32_t* iterations_out) {
   int rc = check_com("com_refine", image_host, image_dtype, H, W, corners_host, n, size, threshold, centroids_out);
   if (rc) return rc;
-  for (int64_t i = 0; i < n; ++i) {                  // the windows are checked before anything is launched
-    const int64_t x0 = corners_host[2 * i], y0 = corners_host[2 * i + 1];
-    if (x0 < 0 || y0 < 0 || x0 + size > W || y0 + size > H) return zk_fail(ZK_E_BADARG, std::string("com_refine") + WINDOW_MESSAGE);
-  }
+  if (!corners_inside(corners_host, n, size, H, W)) return window_fail("com_refine");   // before anything is launched
   if (n == 0) return 0;
   ZK_ON_DEVICE(device);
-  const size_t px = (image_dtype == ZK_F32 ? sizeof(float) : sizeof(double)) * (size_t)H * (size_t)W, count = (size_t)n;
-  dev_buf d_img, d_pts, d_out, d_thr, d_it;
-  if ((rc = d_img.alloc(px)) || (rc = d_pts.alloc(sizeof(int32_t) * 2 * count)) || (rc = d_out.alloc(sizeof(double) * 2 * count)) ||
-      (rc = d_thr.alloc(sizeof(double) * count)) || (rc = d_it.alloc(sizeof(int32_t) * count)))
+  const size_t count = (size_t)n;
+  host_stage st;
+  if ((rc = st.up(image_host, image_dtype, H, W, corners_host, n, {sizeof(double) * 2 * count, sizeof(double) * count, sizeof(int32_t) * count})) ||
+      (rc = com_call("com_refine", st.img.p, image_dtype, H, W, st.rows.p, CORNERS, n, (int)size, threshold, st.out[0].as<double>(),
+                     st.out[1].as<double>(), st.out[2].as<int>(), (hipStream_t)0)) ||
+      (rc = st.fetch(0, centroids_out)) || (rc = st.fetch(1, thresholds_out)))
     return rc;
-  ZK_HIP(hipMemcpy(d_img.p, image_host, px, hipMemcpyHostToDevice));
-  ZK_HIP(hipMemcpy(d_pts.p, corners_host, sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice));
-  if ((rc = com_call("com_refine", d_img.p, image_dtype, H, W, d_pts.p, CORNERS, n, (int)size, threshold, d_out.as<double>(),
-                     d_thr.as<double>(), d_it.as<int>(), (hipStream_t)0)))
-    return rc;
-  ZK_HIP(hipMemcpy(centroids_out, d_out.p, sizeof(double) * 2 * count, hipMemcpyDeviceToHost));
-  if (thresholds_out) ZK_HIP(hipMemcpy(thresholds_out, d_thr.p, sizeof(double) * count, hipMemcpyDeviceToHost));
-  if (iterations_out) ZK_HIP(hipMemcpy(iterations_out, d_it.p, sizeof(int32_t) * count, hipMemcpyDeviceToHost));
-  return 0;
+  return st.fetch(2, iterations_out);
 }

@@ -24,20 +24,15 @@
 // LDS: 640 bytes a wave.  Registers and what binds the kernel: DESIGN.md, "Gaussian fits of key points".
 #include <math.h>
 
-#include "zk_internal.h"
-#include "zk_scratch.h"
+#include "zk_point_window.h"
 
 namespace {
 
 constexpr int MIN_SIZE = 3, MAX_SIZE = 32;           // the side of a window
 constexpr int MAX_ITER_LIMIT = 10000;
-constexpr int CORNERS = -1;                          // the points are int32 window corners (zk_gauss_fit)
-constexpr double POINT_LIMIT = 1073741824.0;         // |rint(point)| below 2^30: the corner is an int
 constexpr double LAMBDA_START = 1e-3, LAMBDA_MIN = 1e-12, LAMBDA_MAX = 1e12;
 constexpr int FITTED = 1 << 16;                      // pos: col | row << 8 | FITTED
 constexpr int SLOT = 40;                             // doubles of one LDS slot: the padded sums of the elliptical model
-
-enum { ERR_WINDOW = 1 };
 
 template <int NP>
 struct layout {
@@ -179,25 +174,12 @@ __global__ __launch_bounds__(64) void gauss_fit_kernel(const T* __restrict__ img
   const int lane = threadIdx.x, area = size * size;
   const long long n = blockIdx.x;
   // the corner of the window: uniform over the wave, so every exit below is taken by all lanes
-  long long x0, y0;
-  bool inside = true;
-  if (pts_dtype == CORNERS || pts_dtype == ZK_I32) {
-    x0 = ((const int*)pts)[2 * n];
-    y0 = ((const int*)pts)[2 * n + 1];
-    if (pts_dtype == ZK_I32) {
-      x0 -= size / 2;
-      y0 -= size / 2;
-    }
-  } else {
-    const double rx = rint(((const double*)pts)[2 * n]), ry = rint(((const double*)pts)[2 * n + 1]);
-    inside = fabs(rx) < POINT_LIMIT && fabs(ry) < POINT_LIMIT;               // false for a NaN
-    x0 = inside ? (long long)rx - size / 2 : 0;
-    y0 = inside ? (long long)ry - size / 2 : 0;
-  }
-  if (!inside || x0 < 0 || y0 < 0 || x0 + size > W || y0 + size > H) {
+  const point_window at = window_at(pts, pts_dtype, n, size, H, W);
+  if (!at.inside) {
     if (lane == 0) atomicOr(flag, ERR_WINDOW);
     return;
   }
+  const long long x0 = at.x0, y0 = at.y0;
   double pix[PPL], lo = INFINITY, hi = -INFINITY;
   int pos[PPL];
   bool bad = false;
@@ -297,8 +279,6 @@ __global__ __launch_bounds__(64) void gauss_fit_kernel(const T* __restrict__ img
   }
 }
 
-const char* const WINDOW_MESSAGE = ": a window leaves the frame (every corner needs 0 <= x0 <= W - size, 0 <= y0 <= H - size)";
-
 int fitted_pixels(int size, int mask) {
   if (mask == ZK_GAUSS_BOX) return size * size;
   const int r = size / 2;
@@ -310,11 +290,9 @@ int fitted_pixels(int size, int mask) {
 
 int check_fit(const char* who, const void* img, int dtype, int64_t H, int64_t W, const void* pts, int64_t n, int64_t size, int model,
               int mask, double sigma0, double tol, int64_t max_iter, const void* params, const void* iterations, const void* status) {
+  int rc;
+  if ((rc = check_frame(who, img, dtype, H, W, n))) return rc;
   const std::string name(who);
-  if (dtype != ZK_F32 && dtype != ZK_F64) return zk_fail(ZK_E_BADARG, name + ": the frame must be ZK_F32 or ZK_F64 (a float frame)");
-  if (H <= 0 || W <= 0 || H > ((int64_t)1 << 31) - 1 || W > ((int64_t)1 << 31) - 1 || !img)
-    return zk_fail(ZK_E_BADARG, name + ": needs a frame with 0 < H, W < 2^31");
-  if (n < 0 || n >= ((int64_t)1 << 24)) return zk_fail(ZK_E_BADARG, name + ": needs 0 <= n < 2^24");
   if (size < MIN_SIZE || size > MAX_SIZE) return zk_fail(ZK_E_BADARG, name + ": needs 3 <= size <= 32");
   if (model != ZK_GAUSS_CIRCULAR && model != ZK_GAUSS_ELLIPTICAL) return zk_fail(ZK_E_BADARG, name + ": unknown model");
   if (mask != ZK_GAUSS_BOX && mask != ZK_GAUSS_DISK) return zk_fail(ZK_E_BADARG, name + ": unknown mask");
@@ -324,8 +302,7 @@ int check_fit(const char* who, const void* img, int dtype, int64_t H, int64_t W,
   if (!(sigma0 > 0) || !isfinite(sigma0)) return zk_fail(ZK_E_BADARG, name + ": sigma0 must be positive and finite");
   if (!(tol >= 0) || !isfinite(tol)) return zk_fail(ZK_E_BADARG, name + ": tol must be finite and not negative");
   if (max_iter < 1 || max_iter > MAX_ITER_LIMIT) return zk_fail(ZK_E_BADARG, name + ": needs 1 <= max_iter <= 10000");
-  if (n && (!pts || !params || !iterations || !status)) return zk_fail(ZK_E_BADARG, name + ": null pointer");
-  return 0;
+  return check_pointers(who, n, pts && params && iterations && status);
 }
 
 struct fit_args {
@@ -363,21 +340,16 @@ int fit_by_size(const fit_args& a) {
 
 int fit_call(const char* who, int dtype, int model, fit_args a) {
   if (a.n == 0) return 0;
-  int rc;
-  dev_buf d_flag;
-  if ((rc = d_flag.alloc(16))) return rc;
-  ZK_HIP(hipMemsetAsync(d_flag.p, 0, 16, a.s));
-  a.flag = d_flag.as<int>();
+  int rc, flags;
+  dev_flag flag;
+  if ((rc = flag.arm(a.s))) return rc;
+  a.flag = flag.word();
   if (model == ZK_GAUSS_ELLIPTICAL)
     rc = dtype == ZK_F32 ? fit_by_size<float, 7>(a) : fit_by_size<double, 7>(a);
   else
     rc = dtype == ZK_F32 ? fit_by_size<float, 5>(a) : fit_by_size<double, 5>(a);
-  if (rc) return rc;
-  int flags = 0;
-  ZK_HIP(hipMemcpyAsync(&flags, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, a.s));
-  ZK_HIP(hipStreamSynchronize(a.s));                 // the flag crosses to the host
-  if (flags & ERR_WINDOW) return zk_fail(ZK_E_BADARG, std::string(who) + WINDOW_MESSAGE);
-  return 0;
+  if (rc || (rc = flag.read(a.s, &flags))) return rc;
+  return flags & ERR_WINDOW ? window_fail(who) : 0;
 }
 
 }  // namespace
@@ -403,25 +375,16 @@ extern "C" int zk_gauss_fit(int device, const void* image_host, int image_dtype,
   int rc = check_fit("gauss_fit", image_host, image_dtype, H, W, corners_host, n, size, model, mask, sigma0, tol, max_iter, params_out,
                      iterations_out, status_out);
   if (rc) return rc;
-  for (int64_t i = 0; i < n; ++i) {                  // the windows are checked before anything is launched
-    const int64_t x0 = corners_host[2 * i], y0 = corners_host[2 * i + 1];
-    if (x0 < 0 || y0 < 0 || x0 + size > W || y0 + size > H) return zk_fail(ZK_E_BADARG, std::string("gauss_fit") + WINDOW_MESSAGE);
-  }
+  if (!corners_inside(corners_host, n, size, H, W)) return window_fail("gauss_fit");   // before anything is launched
   if (n == 0) return 0;
   ZK_ON_DEVICE(device);
-  const size_t px = (image_dtype == ZK_F32 ? sizeof(float) : sizeof(double)) * (size_t)H * (size_t)W, count = (size_t)n;
-  dev_buf d_img, d_pts, d_par, d_it, d_st;
-  if ((rc = d_img.alloc(px)) || (rc = d_pts.alloc(sizeof(int32_t) * 2 * count)) || (rc = d_par.alloc(sizeof(double) * 8 * count)) ||
-      (rc = d_it.alloc(sizeof(int32_t) * count)) || (rc = d_st.alloc(sizeof(int32_t) * count)))
+  const size_t count = (size_t)n;
+  host_stage st;
+  if ((rc = st.up(image_host, image_dtype, H, W, corners_host, n, {sizeof(double) * 8 * count, sizeof(int32_t) * count, sizeof(int32_t) * count})) ||
+      (rc = fit_call("gauss_fit", image_dtype, model,
+                     fit_args{st.img.p, H, W, st.rows.p, CORNERS, n, (int)size, mask, sigma0, tol, (int)max_iter, st.out[0].as<double>(),
+                              st.out[1].as<int>(), st.out[2].as<int>(), nullptr, (hipStream_t)0})) ||
+      (rc = st.fetch(0, params_out)) || (rc = st.fetch(1, iterations_out)))
     return rc;
-  ZK_HIP(hipMemcpy(d_img.p, image_host, px, hipMemcpyHostToDevice));
-  ZK_HIP(hipMemcpy(d_pts.p, corners_host, sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice));
-  if ((rc = fit_call("gauss_fit", image_dtype, model,
-                     fit_args{d_img.p, H, W, d_pts.p, CORNERS, n, (int)size, mask, sigma0, tol, (int)max_iter, d_par.as<double>(), d_it.as<int>(),
-                              d_st.as<int>(), nullptr, (hipStream_t)0})))
-    return rc;
-  ZK_HIP(hipMemcpy(params_out, d_par.p, sizeof(double) * 8 * count, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(iterations_out, d_it.p, sizeof(int32_t) * count, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(status_out, d_st.p, sizeof(int32_t) * count, hipMemcpyDeviceToHost));
-  return 0;
+  return st.fetch(2, status_out);
 }

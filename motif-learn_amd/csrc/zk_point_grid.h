@@ -1,5 +1,5 @@
 // zk_point_grid.h -- the uniform bin grid over a 2-D point set, shared by the searches that walk it (the cells of
-// zk_voronoi.hip, the nearest neighbours of zk_refine.hip).  The single owner of:
+// zk_voronoi.hip, the nearest neighbours of zk_knn.hip).  The single owner of:
 //
 //   points       load_points_kernel: (N, 2) ZK_F64 as they are or ZK_I32 widened exactly, to double2; a NaN or inf raises
 //                ERR_NONFINITE in the caller's flag word.
@@ -13,7 +13,7 @@
 //
 // Loading and building are two steps: a caller may read the flag, or return, before any frame exists.
 //
-// This header is compiled under each includer's flags, and zk_refine.o is built with -ffp-contract=off where zk_voronoi.o is
+// This header is compiled under each includer's flags, and zk_knn.o is built with -ffp-contract=off where zk_voronoi.o is
 // not.  The device expressions here are subtract, divide, floor, compare and integer arithmetic only: nothing of the shape
 // a * b + c that contraction could fuse, so both objects bin alike.  Keep it so; a frame kernel, a clip or a distance does not
 // belong here.  Everything has internal linkage: each object keeps its own device copy.

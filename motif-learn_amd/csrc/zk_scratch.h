@@ -1,5 +1,5 @@
 // zk_scratch.h -- host-side scratch helpers of the translation units that own their device memory per call: a device buffer
-// freed with its scope, the block count of a launch, and rocPRIM's temporary storage with the one way to call an algorithm
+// freed with its scope, the error word of a call (dev_flag), the block count of a launch, and rocPRIM's temporary storage with the one way to call an algorithm
 // that needs it.
 #pragma once
 
@@ -20,6 +20,24 @@ struct dev_buf {
   template <typename T>
   T* as() const {
     return (T*)p;
+  }
+};
+
+// the error word of one call: kernels raise bits in it with atomicOr, the host reads it once, at the call's one synchronise
+struct dev_flag {
+  dev_buf buf;
+  int* word() const { return buf.as<int>(); }
+  int arm(hipStream_t s) {                           // allocated and zeroed
+    int rc;
+    if ((rc = buf.alloc(16))) return rc;
+    ZK_HIP(hipMemsetAsync(buf.p, 0, 16, s));
+    return 0;
+  }
+  int read(hipStream_t s, int* flags) {              // everything queued on `s` before this has finished when it returns
+    *flags = 0;
+    ZK_HIP(hipMemcpyAsync(flags, buf.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    ZK_HIP(hipStreamSynchronize(s));
+    return 0;
   }
 };
 

@@ -18,17 +18,48 @@ __all__ = ["disk_patch", "center_of_mass_refine", "refine_points", "com_refine",
            "GaussianFit", "clear_border", "KeyPoints"]
 
 
-def _interior(pts, x_limit, y_limit, size):
-    """Rows of ``pts`` (x, y) strictly more than ``size // 2 + 1`` away from 0 and from the given limits."""
+def _interior_mask(pts, x_limit, y_limit, size):
+    """Which rows of ``pts`` (x, y) lie strictly more than ``size // 2 + 1`` away from 0 and from the given limits: the one
+    statement of the border rule (``_keypoint.py:46-50``)."""
     margin = size // 2 + 1
     xy = np.asarray(pts)
-    inside = (xy[:, 0] > margin) & (xy[:, 0] < x_limit - margin) & (xy[:, 1] > margin) & (xy[:, 1] < y_limit - margin)
-    return pts[inside]
+    return (xy[:, 0] > margin) & (xy[:, 0] < x_limit - margin) & (xy[:, 1] > margin) & (xy[:, 1] < y_limit - margin)
+
+
+def _interior(pts, x_limit, y_limit, size):
+    """Rows of ``pts`` (x, y) strictly more than ``size // 2 + 1`` away from 0 and from the given limits."""
+    return pts[_interior_mask(pts, x_limit, y_limit, size)]
 
 
 def clear_border(pts, shape, size):
     """Points farther than ``size // 2 + 1`` from every border of an image of ``shape`` (``_keypoint.py:46-50``)."""
     return _interior(pts, shape[1], shape[0], size)
+
+
+def _frame_and_points(img, pts, who):
+    """``img`` as a 2-D float32 / float64 frame and ``pts`` as real, finite ``(N, 2)`` points with ``N < 2^24``, or the
+    ``ValueError`` of ``who``."""
+    img, pts = np.asarray(img), np.asarray(pts)
+    if img.ndim != 2 or img.dtype not in (np.float32, np.float64):
+        raise ValueError(f"{who} needs a 2-D float32 or float64 frame, not {img.ndim}-D {img.dtype}")
+    if pts.size == 0:
+        pts = pts.reshape(0, 2).astype(np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 2 or pts.dtype.kind not in "iuf":
+        raise ValueError(f"{who} needs real points of shape (N, 2), not {pts.dtype} {pts.shape}")
+    if pts.dtype.kind == "f" and not np.isfinite(pts).all():
+        raise ValueError(f"{who} needs finite points")
+    if len(pts) >= 2 ** 24:
+        raise ValueError(f"{who} needs len(pts) < 2^24")
+    return img, pts
+
+
+def _window_corners(pts, size, shape, who):
+    """The int32 ``(x0, y0)`` of every point's ``size x size`` window, ``np.rint(pt).astype(int) - size // 2``; ``ValueError``
+    when one leaves a frame of ``shape``."""
+    first = np.rint(pts).astype(int) - size // 2
+    if len(first) and (first.min() < 0 or (first[:, 0] + size > shape[1]).any() or (first[:, 1] + size > shape[0]).any()):
+        raise ValueError(f"{who} needs every window inside the frame")
+    return np.ascontiguousarray(first, dtype=np.int32)
 
 
 def disk_patch(radius, dtype=np.uint8):
@@ -122,28 +153,16 @@ def com_refine_points(pts, img, size, threshold=None, return_thresholds=False):
     ``pts`` returns a ``(0, 2)`` array without touching the device."""
     from ctypes import c_void_p
     from .. import _native
-    img, pts = np.asarray(img), np.asarray(pts)
-    if img.ndim != 2 or img.dtype not in (np.float32, np.float64):
-        raise ValueError(f"com_refine_points needs a 2-D float32 or float64 frame, not {img.ndim}-D {img.dtype}")
-    if pts.size == 0:
-        pts = pts.reshape(0, 2).astype(np.float64)
-    if pts.ndim != 2 or pts.shape[1] != 2 or pts.dtype.kind not in "iuf":
-        raise ValueError(f"com_refine_points needs real points of shape (N, 2), not {pts.dtype} {pts.shape}")
+    img, pts = _frame_and_points(img, pts, "com_refine_points")
     if int(size) != size or not 2 <= int(size) <= 64:
         raise ValueError(f"size must be an integer in [2, 64], not {size}")
     size = int(size)
-    if pts.dtype.kind == "f" and not np.isfinite(pts).all():
-        raise ValueError("com_refine_points needs finite points")
-    if len(pts) >= 2 ** 24:
-        raise ValueError("com_refine_points needs len(pts) < 2^24")
     kept = clear_border(pts, img.shape, size)
     moved, levels, steps = np.empty((len(kept), 2), np.float64), np.empty(len(kept), np.float64), np.empty(len(kept), np.int32)
     if len(kept):
-        first = np.rint(kept).astype(int) - size // 2
+        first = _window_corners(kept, size, img.shape, "com_refine_points")               # border clearing guarantees them
         height, width = img.shape
-        if first.min() < 0 or (first[:, 0] + size > width).any() or (first[:, 1] + size > height).any():
-            raise ValueError("com_refine_points needs every window inside the frame")      # border clearing guarantees it
-        img, first = np.ascontiguousarray(img), np.ascontiguousarray(first, dtype=np.int32)
+        img = np.ascontiguousarray(img)
         lib = _native.load()
         _native.require_device()
         _native.check(lib.zk_com_refine(_native.default_device(), img.ctypes.data_as(c_void_p), _native.dtype_code(img.dtype), height, width,
@@ -206,31 +225,15 @@ def gaussian_fit_points(pts, img, size, model="elliptical", mode=None, sigma=Non
     ``pts`` returns empty arrays without touching the device."""
     from ctypes import c_void_p
     from .. import _native
-    img, pts = np.asarray(img), np.asarray(pts)
-    if img.ndim != 2 or img.dtype not in (np.float32, np.float64):
-        raise ValueError(f"gaussian_fit_points needs a 2-D float32 or float64 frame, not {img.ndim}-D {img.dtype}")
-    if pts.size == 0:
-        pts = pts.reshape(0, 2).astype(np.float64)
-    if pts.ndim != 2 or pts.shape[1] != 2 or pts.dtype.kind not in "iuf":
-        raise ValueError(f"gaussian_fit_points needs real points of shape (N, 2), not {pts.dtype} {pts.shape}")
+    img, pts = _frame_and_points(img, pts, "gaussian_fit_points")
     size, model_code, mask_code, sigma, tol, max_iter = gaussian_fit_options(size, model, mode, sigma, tol, max_iter)
-    if pts.dtype.kind == "f" and not np.isfinite(pts).all():
-        raise ValueError("gaussian_fit_points needs finite points")
-    if len(pts) >= 2 ** 24:
-        raise ValueError("gaussian_fit_points needs len(pts) < 2^24")
     height, width = img.shape
-    if clear:
-        margin = size // 2 + 1                                                                 # clear_border's rule, as indices
-        kept = np.flatnonzero((pts[:, 0] > margin) & (pts[:, 0] < width - margin) & (pts[:, 1] > margin) & (pts[:, 1] < height - margin))
-    else:
-        kept = np.arange(len(pts))
+    kept = np.flatnonzero(_interior_mask(pts, width, height, size)) if clear else np.arange(len(pts))
     kept = kept.astype(np.int64)
-    first = np.rint(pts[kept]).astype(int) - size // 2
-    if len(first) and (first.min() < 0 or (first[:, 0] + size > width).any() or (first[:, 1] + size > height).any()):
-        raise ValueError("gaussian_fit_points needs every window inside the frame")
+    first = _window_corners(pts[kept], size, img.shape, "gaussian_fit_points")
     params, steps, status = np.empty((len(kept), 8), np.float64), np.empty(len(kept), np.int32), np.empty(len(kept), np.int32)
     if len(kept):
-        img, first = np.ascontiguousarray(img), np.ascontiguousarray(first, dtype=np.int32)
+        img = np.ascontiguousarray(img)
         lib = _native.load()
         _native.require_device()
         _native.check(lib.zk_gauss_fit(_native.default_device(), img.ctypes.data_as(c_void_p), _native.dtype_code(img.dtype), height, width,

@@ -31,7 +31,7 @@ Voronoi neighbours, or with nearly as many: cells are clipped in bin order and m
 
 ``estimate_d`` (reference ``graph/vnn.py:18-40``) keeps the reference's signature and rule: for ``k = 2 .. 12`` the distances to
 the nearest ``k - 1`` neighbours are thresholded (Otsu, or Li's minimum cross-entropy for anything but ``'otsu'``) and the
-threshold that splits its sample most evenly wins.  The device does every pass over the data (``csrc/zk_refine.hip``: the
+threshold that splits its sample most evenly wins.  The device does every pass over the data (``csrc/zk_knn.hip``: the
 12-neighbour distance matrix on a grid of bins, one pass for the eleven ranges, one for the eleven 256-bin histograms under
 NumPy's own binning rule, one fixed-tree reduction per Li iteration, a radix sort for Li's tolerance); the host applies the
 scalar rules to a few hundred numbers with NumPy.  The two thresholds are this project's statements of the published

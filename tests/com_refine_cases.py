@@ -22,6 +22,24 @@ def corners(pts, size):
     return (np.rint(pts).astype(int) - size // 2).astype(np.int32)
 
 
+EDGE_SHAPE = (9, 12)
+
+
+def edge_points(size):
+    """Six int32 points of an ``EDGE_SHAPE`` frame whose ``size`` windows (2 <= size <= 5) sit at x0 = 0, x0 = W - size, y0 = 0,
+    y0 = H - size and twice in the interior, and float64 points that round to them: offsets below a half, and the ties k + 0.5 at
+    even k (down) and odd k (up).  Shared with tests/test_gpu_gauss_fit.py."""
+    (h, w), half = EDGE_SHAPE, size // 2
+    ints = np.array([(half, 4), (w - size + half, 3), (5, half), (7, h - size + half), (4, 4), (6, 4)], dtype=np.int32)
+    reals = ints + np.array([(0.3, -0.4), (-0.49, 0.49), (0.49, -0.3), (-0.2, 0.0), (0.5, -0.5), (-0.5, 0.5)])   # 4.5 -> 4, 3.5 -> 4, 5.5 -> 6
+    first = ints - half
+    assert np.array_equal(np.rint(reals), ints) and first.min() == 0 and (first[:, 0] + size).max() == w and (first[:, 1] + size).max() == h
+    return ints, reals
+
+
+ONE_PIXEL_OUT = ((0, (-1, 0)), (1, (1, 0)), (2, (0, -1)), (3, (0, 1)))        # (row of edge_points, step): left, right, top, bottom
+
+
 def windows(frame, pts, size):
     """The float64 windows the kernel works on, ``(N, size, size)``."""
     return np.array([frame[y:y + size, x:x + size].astype(np.float64) for x, y in corners(pts, size)]).reshape(len(pts), size, size)

@@ -1,4 +1,4 @@
-"""Point sets that reach the edges of the point-set kernels (csrc/zk_point_grid.h, parts B and C of csrc/zk_refine.hip,
+"""Point sets that reach the edges of the point-set kernels (csrc/zk_point_grid.h, csrc/zk_knn.hip,
 csrc/zk_voronoi.hip), regenerated from seeds: NumPy only, read-only arrays.  The sets of tests/refine_cases.py and
 tests/vnn_cases.py are near-uniform; each set here is named for the line of a kernel it exercises.
 

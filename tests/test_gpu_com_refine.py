@@ -142,6 +142,37 @@ def test_a_window_outside_the_frame_raises_and_the_next_call_succeeds(golden):
         assert np.abs(to_host(out) - golden[f"{name}/li/xy"]).max() <= 1e-10
 
 
+@pytest.mark.parametrize("dtype", (np.float32, np.float64))
+@pytest.mark.parametrize("size", (2, 4, 5))
+def test_corner_int32_and_float64_routes_share_one_window(size, dtype):
+    """The corner entry point, int32 points and float64 points on the same windows, on the frame's edges and at rint's ties: the
+    same bytes once the corner route is finished as the host finishes it, ``(c - size / 2) + p``."""
+    frame = (np.random.default_rng(size).random(cc.EDGE_SHAPE) + 0.5).astype(dtype)
+    ints, reals = cc.edge_points(size)
+    for threshold in cc.THRESHOLDS:
+        rule = None if threshold == "li" else "otsu"
+        for pts in (ints, reals):
+            want = any_window(frame, pts, size, threshold)[0]
+            got = to_host(distributed.com_refine_device(resident(frame, "native"), resident(pts, "native"), size, rule))
+            assert np.isfinite(want).all() and got.tobytes() == want.tobytes(), (threshold, pts.dtype)
+
+
+def test_a_window_one_pixel_outside_raises_for_int32_and_float64_points():
+    size = 4
+    frame = np.random.default_rng(4).random(cc.EDGE_SHAPE) + 0.5
+    ints, reals = cc.edge_points(size)
+    for k, step in cc.ONE_PIXEL_OUT:
+        for pts in (ints, reals):
+            bad = pts.copy()
+            bad[k] += step
+            with pytest.raises(ValueError, match="leaves the frame"):
+                distributed.com_refine_device(resident(frame, "native"), resident(bad, "native"), size)
+            with pytest.raises(RuntimeError, match="leaves the frame"):
+                any_window(frame, bad, size, "li")
+            good = to_host(distributed.com_refine_device(resident(frame, "native"), resident(pts, "native"), size))   # the next call succeeds
+            assert good.tobytes() == any_window(frame, pts, size, "li")[0].tobytes()
+
+
 def test_resident_chain_local_max_com_refine_bonds():
     """local_max_device -> com_refine_device -> vnn_graph_device on the 512^2 frame: frame and points stay on the device; the
     refined points equal the host function's on the same key points and feed the bonds."""

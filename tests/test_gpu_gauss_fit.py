@@ -181,6 +181,40 @@ def test_rounding_of_points():
         assert on_resident(frame, halves, 9, kind)[0].tobytes() == want.tobytes()
 
 
+@pytest.mark.parametrize("dtype", (np.float32, np.float64))
+@pytest.mark.parametrize("size", (3, 4, 5))
+def test_corner_int32_and_float64_routes_share_one_window(size, dtype):
+    """The corner entry point, int32 points and float64 points on the windows of tests/com_refine_cases.py ``edge_points`` (the
+    frame's four edges, rint's ties at even and odd k): parameters, iterations and status byte for byte.  Beside
+    ``test_rounding_of_points`` and ``test_windows_on_the_frame_borders``, which hold the same at size 9 inside a 64^2 frame and at
+    sizes 7 / 8 for int32 points in the frame's corners."""
+    import com_refine_cases as cc
+    frame = (np.random.default_rng(size).random(cc.EDGE_SHAPE) + 0.5).astype(dtype)
+    ints, reals = cc.edge_points(size)
+    for model in gc.MODELS:
+        want = on_corners(frame, ints, size, model)
+        assert same_bits(on_corners(frame, reals, size, model), want)
+        for pts in (ints, reals):
+            assert same_bits(on_resident(frame, pts, size, "native", model=model), want), (model, pts.dtype)
+
+
+def test_a_window_one_pixel_outside_is_refused_for_int32_and_float64_points():
+    import com_refine_cases as cc
+    size = 4
+    frame = np.random.default_rng(4).random(cc.EDGE_SHAPE) + 0.5
+    ints, reals = cc.edge_points(size)
+    want = on_corners(frame, ints, size)
+    for k, step in cc.ONE_PIXEL_OUT:
+        for pts in (ints, reals):
+            bad = pts.copy()
+            bad[k] += step
+            with pytest.raises(ValueError, match="leaves the frame"):
+                resident.gaussian_fit_device(on_device(frame, "native"), on_device(bad, "native"), size)
+            with pytest.raises(RuntimeError, match="leaves the frame"):
+                on_corners(frame, bad, size)
+            assert same_bits(on_resident(frame, pts, size, "native"), want)                               # the next call succeeds
+
+
 def test_status_paths():
     frame, sites = gc.lattice_frame(0.02)
     usual = features.gaussian_fit_points(sites, frame, 9)

@@ -79,7 +79,7 @@ def estimate(pts, threshold, dd=None):
 
 
 def kernel_bin_rule(d, first, last):
-    """The 256-bin counts of ``d`` under the rule csrc/zk_refine.hip applies to one value at a time: index
+    """The 256-bin counts of ``d`` under the rule csrc/zk_np_bins.h applies to one value at a time: index
     ``(v - first) / (last - first) * 256`` truncated, 256 folded into 255, one down when ``v < edges[index]``, one up when
     ``v >= edges[index + 1]`` outside the last bin; ``edges = np.linspace(first, last, 257)``."""
     edges = np.linspace(first, last, 257)
