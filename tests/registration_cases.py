@@ -14,7 +14,12 @@ Shifts: zero; a coarse peak at flat index 0; one at the last row and column (neg
 Ties: a constant (16, 16) frame, where every sample of both planes is the same float64 (power-of-two sums are exact).
 Honeycomb: ``datasets.HoneyCombLattice`` (l = 6), drawn twice with the sites displaced by more than half a lattice period, in a
 direction where the lattice-equivalent displacement is shorter but has the larger component (see ``honeycomb``).
+
+``EDGE_CASES`` are the cases past one reduction block (4096 samples), one 64-wide tile and one run of frames.  Their inputs are
+large, so they are ``(name, function)`` pairs: the function builds the case dict at its first call and keeps it.
 """
+import functools
+
 import numpy as np
 
 import registration_oracle as ro
@@ -151,3 +156,137 @@ def end_to_end():
     answers[0] = 0.0
     stack, base = truth_stack((64, 64), answers, 13)
     return stack, base, answers
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Past one reduction block, one tile and one run: built at the first use, never at import.
+# ---------------------------------------------------------------------------------------------------------------------
+ANSWERS_72 = [(0.0, 0.0), (3.31, -2.22), (-20.37, 50.21), (-1.13, -0.87), (35.4, -67.3)]       # coarse peaks in partials 0, 0, 1, 2, 1
+ANSWERS_1040 = [(0.0, 0.0), (0.31, -0.22), (-1.13, -0.87)]                                     # the last: row 1038, partial 261 of 263
+ANSWERS_13 = [(0.0, 0.0), (3.3, -1.2), (1.2, -3.3), (-2.0, 2.0), (-2.6, 2.6)]
+ANSWERS_16x12 = [(0.0, 0.0), (-7.8, 5.7), (7.8, -5.7)]                                         # the lags -n / 2 of both even extents
+MASKS_13 = (0, 1, 2, 2.999, 6, 8, 100)
+MASKS_16x12 = (5, 6, 7, 8)
+
+
+@functools.lru_cache(maxsize=None)
+def _truth(shape, answers, seed):
+    return truth_stack(shape, answers, seed)[0]
+
+
+@functools.lru_cache(maxsize=None)
+def _flat_128x64():
+    return np.ones((2, 128, 64))
+
+
+@functools.lru_cache(maxsize=None)
+def _quantised():
+    """The 32 x 48 stack of the dtype cases of ``CASES`` scaled to [0, 1]: ``(q, the float stack)``."""
+    stack, _ = truth_stack((32, 48), positions(32, 48)[:3], 9)
+    return (stack - stack.min()) / (stack.max() - stack.min()), stack
+
+
+def _int16(q):
+    return (np.round(q * 65535) - 32768).astype(np.int16)           # centred: about half the samples are negative
+
+
+@functools.lru_cache(maxsize=None)
+def field_runs_stack():
+    """``(stack (130, 512, 512) uint8, answers)``: two complex fields of a frame take 32 x 262144 bytes, so the field budget of
+    1 GiB holds 128 frames and the stack goes in runs of 128 + 2 (129 frames: 128 + 1)."""
+    answers = np.round(np.random.default_rng(130).uniform(-6, 6, (130, 2)), 1) + 0.03
+    answers[0] = 0.0
+    stack = _truth((512, 512), tuple(map(tuple, answers)), 205)
+    q = (stack - stack.min()) / (stack.max() - stack.min())
+    return np.round(q * 255).astype(np.uint8), answers
+
+
+@functools.lru_cache(maxsize=None)
+def table_runs_stack():
+    """``(stack (120, 16, 16), answers)``: at ``upsample = 1000`` (S = 1500) the tables of a frame take 19,152,000 bytes, so the
+    table budget of 1 GiB holds 56 frames and the stack goes in runs of 56 + 56 + 8.
+
+    The answers are tenths plus an offset off the nodes of the 1 / 1000 grid: ``0.0303 (1 + b % 3)``, and 0.0452 for the last
+    frame.  These frames are exact, so with one offset for all of them frame ``b`` would lie a whole number of tenths from frame
+    ``b - 1`` and from the last frame; wherever that is ``n + 0.5`` px, the lags ``n`` and ``n + 1`` of the coarse plane tie and
+    the case fails the margin condition for ``reference="previous"`` and ``reference=-1``.  With these offsets no difference
+    to frame 0, to the frame before or to the last frame is closer than 0.0149 px to a multiple of 0.1."""
+    answers = np.round(np.random.default_rng(120).uniform(-5, 5, (120, 2)), 1) + 0.0303 * (1 + np.arange(120) % 3)[:, None]
+    answers[0] = 0.0
+    answers[-1] += 0.0452 - 0.0303 * (1 + 119 % 3)
+    return _truth((16, 16), tuple(map(tuple, answers)), 202), answers
+
+
+def _edge(name, source, **options):
+    """``(name, function)``: the function builds the case at its first call; ``source()`` is the stack, or a dict of the
+    case's lazily built entries (``stack`` and, say, ``reference``)."""
+    @functools.lru_cache(maxsize=None)
+    def make():
+        built = source()
+        return _case(name, **{**(built if isinstance(built, dict) else dict(stack=built)), **options})
+    return name, make
+
+
+def _s72():
+    return _truth((72, 136), tuple(ANSWERS_72), 201)
+
+
+def _s1040():
+    return _truth((1040, 1032), tuple(ANSWERS_1040), 206)
+
+
+def _s13():
+    return _truth((13, 17), tuple(ANSWERS_13), 203)
+
+
+def _s16x12():
+    return _truth((16, 12), tuple(ANSWERS_16x12), 204)
+
+
+def _edge_cases():
+    cases = [
+        # 1. 9792 samples: partials of 4096, 4096 and 1600; W = 136 is two column tiles and 8, H = 72 four depth slices and 8
+        _edge("72x136-u1", _s72, upsample=1),
+        _edge("72x136-u100", _s72, upsample=100, truth=ANSWERS_72),
+        _edge("72x136-u10-phase", _s72, upsample=10, normalization="phase"),
+        _edge("72x136-u10-hann", _s72, upsample=10, window="hann"),
+        _edge("72x136-u10-ms10", _s72, upsample=10, max_shift=10),      # rows 11 .. 61 shut: partial 1 (rows 30 .. 60) has no sample
+        _edge("72x136-u1-ms3", _s72, upsample=1, max_shift=3),
+        _edge("72x136-u10-ms0", _s72, upsample=10, max_shift=0),
+        # 2. 8192 equal samples: the partials of blocks 0 and 1 tie
+        _edge("128x64-u1-tie", _flat_128x64, upsample=1, tie=(0.0, 0.0)),
+        _edge("128x64-u1-ms2-tie", _flat_128x64, upsample=1, max_shift=2, tie=(0.0, 0.0)),
+        _edge("128x64-u10-tie", _flat_128x64, upsample=10, tie=(-0.7, -0.7)),       # S = 15, off = 7: (0 - 7) / 10
+        # 3. 1,073,280 samples: 263 partials, more than the 256 lanes that fold them
+        _edge("1040x1032-u10", _s1040, upsample=10, truth=ANSWERS_1040),
+        _edge("1040x1032-u10-phase", _s1040, upsample=10, normalization="phase"),
+    ]
+    # 4. the mask on small frames: the y test apart from the x test, 0, wider than the frame, the lag -n / 2
+    cases += [_edge(f"13x17-u10-ms{ms}", _s13, upsample=10, max_shift=ms) for ms in MASKS_13]
+    cases += [_edge(f"16x12-u10-ms{ms}", _s16x12, upsample=10, max_shift=ms) for ms in MASKS_16x12]
+    # 5. int16, and a reference array of another dtype than the stack's (quantised: the oracle on the same numbers is the reference)
+    cases += [
+        _edge("32x48-u10-int16", lambda: _int16(_quantised()[0]), upsample=10),
+        _edge("32x48-u10-uint8-ref-float64", lambda: dict(stack=np.round(_quantised()[0] * 255).astype(np.uint8),
+                                                          reference=np.round(_quantised()[0][0] * 255)), upsample=10),
+        _edge("32x48-u10-float32-ref-int16", lambda: dict(stack=_quantised()[1].astype(np.float32),
+                                                          reference=_int16(_quantised()[0][0])), upsample=10),
+    ]
+    for tag, reference in (("first", 0), ("previous", "previous"), ("last", -1)):
+        # 6. runs of 128 + 2 frames under the field budget: "previous" hands frame 127 over the boundary, -1 lives in run 2
+        cases.append(_edge(f"512x512-u10-B130-{tag}", lambda: field_runs_stack()[0], upsample=10, reference=reference))
+    for tag, reference in (("first", 0), ("previous", "previous"), ("last", -1)):
+        # 7. runs of 56 + 56 + 8 frames under the table budget
+        cases.append(_edge(f"16x16-u1000-B120-{tag}", lambda: dict(zip(("stack", "truth"), table_runs_stack())), upsample=1000,
+                           reference=reference))                     # the truth is that of the first form: against frame 0
+    return cases
+
+
+EDGE_CASES = _edge_cases()
+EDGE_PLANE_CASES = ("72x136-u100",)     # both planes of every frame are compared sample by sample
+
+
+def edge(name):
+    return dict(EDGE_CASES)[name]()
+
+

@@ -40,8 +40,9 @@ def test_oracle_recovers_truth(case):
     assert err.max() <= bound * (1 + 1e-9)
 
 
-@pytest.mark.parametrize("case", [c for c in rc.CASES if c["tie"] is None], ids=lambda c: c["name"])
-def test_margin(case):
+def _smallest_margin(case):
+    """The smallest top-two margin of a case's deciding planes: the coarse plane under its mask, and the upsampled plane.  A
+    masked coarse plane of a single sample (``max_shift = 0``) has no second candidate: its margin is ``inf``."""
     opts = rc.options(case)
     opts.pop("reference")
     worst = np.inf
@@ -52,15 +53,126 @@ def test_margin(case):
         if opts["max_shift"] is not None:
             ly, lx = np.fft.fftfreq(c.shape[0], 1 / c.shape[0]), np.fft.fftfreq(c.shape[1], 1 / c.shape[1])
             c = c[np.abs(ly) <= opts["max_shift"]][:, np.abs(lx) <= opts["max_shift"]]
-        worst = min(worst, ro.top_two_margin(c), np.inf if C is None else ro.top_two_margin(C))
+        worst = min(worst, np.inf if c.size == 1 else ro.top_two_margin(c), np.inf if C is None else ro.top_two_margin(C))
+    return worst
+
+
+@pytest.mark.parametrize("case", [c for c in rc.CASES if c["tie"] is None], ids=lambda c: c["name"])
+def test_margin(case):
+    worst = _smallest_margin(case)
     print(f"{case['name']}: smallest top-two margin {worst:.2e}")
     assert worst >= 1e-9
+
+
+def test_margin_of_a_single_permitted_lag_is_infinite():
+    case = rc.edge("72x136-u10-ms0")
+    coarse_only = dict(case, upsample=1)
+    assert _smallest_margin(coarse_only) == np.inf and np.isfinite(_smallest_margin(case))
 
 
 @pytest.mark.parametrize("case", [c for c in rc.CASES if c["tie"] is not None], ids=lambda c: c["name"])
 def test_ties_take_the_first_index(case):
     shift, _ = ro.estimate_shifts(case["stack"], **rc.options(case))
     np.testing.assert_array_equal(shift, np.tile(case["tie"], (len(case["stack"]), 1)))
+
+
+# ------------------------------------------------------------------------------------------------ the edge cases
+EDGE_IDS = [name for name, _ in rc.EDGE_CASES]
+EDGE_TIES = [name for name in EDGE_IDS if name.endswith("-tie")]
+
+
+def test_edge_cases_are_lazy_and_named_once():
+    assert len(set(EDGE_IDS)) == len(EDGE_IDS) and not set(EDGE_IDS) & {c["name"] for c in rc.CASES}
+    assert all(callable(make) for _, make in rc.EDGE_CASES)
+    assert sorted(EDGE_TIES) == sorted(name for name, make in rc.EDGE_CASES if name.startswith("128x64"))
+    for name in EDGE_TIES:
+        assert rc.edge(name)["tie"] is not None
+
+
+@pytest.mark.parametrize("name", [n for n in EDGE_IDS if n not in EDGE_TIES])
+def test_edge_margin(name):
+    """The margin condition of ``test_margin`` on every edge case that is not a tie, the mask applied to the coarse plane."""
+    case = rc.edge(name)
+    assert case["tie"] is None
+    worst = _smallest_margin(case)
+    print(f"{name}: smallest top-two margin {worst:.2e}")
+    assert worst >= 1e-9
+
+
+@pytest.mark.parametrize("name", EDGE_TIES)
+def test_edge_ties_take_the_first_index(name):
+    case = rc.edge(name)
+    shift, _ = ro.estimate_shifts(case["stack"], **rc.options(case))
+    np.testing.assert_array_equal(shift, np.tile(case["tie"], (len(case["stack"]), 1)))
+
+
+@pytest.mark.parametrize("name", ["72x136-u100", "1040x1032-u10", "16x16-u1000-B120-first"])
+def test_edge_oracle_recovers_truth(name):
+    case = rc.edge(name)
+    shift, _ = ro.estimate_shifts(case["stack"], **rc.options(case))
+    err = rc.wrapped_error(shift, case["truth"], case["stack"].shape[1:])
+    print(f"{name}: worst per-axis error {err.max():.4f} px (bound {1.0 / case['upsample']:g})")
+    assert err.max() <= 1.0 / case["upsample"] * (1 + 1e-9)
+
+
+def _flat_lags(case):
+    """The flat index of every frame's coarse peak, without a mask."""
+    h, w = case["stack"].shape[1:]
+    shift, _ = ro.estimate_shifts(case["stack"], reference=case["reference"], upsample=1)
+    return [int(s[0] % h) * w + int(s[1] % w) for s in shift]
+
+
+def test_the_mask_matters_between_neighbouring_thresholds():
+    """The oracle's answers of the mask cases: what is said to differ differs, what is said to be equal is equal."""
+    def answer(prefix, ms):
+        case = rc.edge(f"{prefix}-ms{ms}")
+        return ro.estimate_shifts(case["stack"], **rc.options(case))[0]
+
+    free = ro.estimate_shifts(rc.edge("13x17-u10-ms2")["stack"], upsample=10)[0]
+    by = {ms: answer("13x17-u10", ms) for ms in rc.MASKS_13}
+    coarse = ro.estimate_shifts(rc.edge("13x17-u10-ms2")["stack"], upsample=1)[0]
+    np.testing.assert_array_equal(coarse[1:3], [[3, -1], [1, -3]])      # frame 1 is beyond 2 in y only, frame 2 in x only
+    assert (by[2][1] != free[1]).any() and (by[2][2] != free[2]).any()
+    np.testing.assert_array_equal(by[2][3:], free[3:])
+    np.testing.assert_array_equal(by[2.999], by[2])
+    np.testing.assert_array_equal(by[8], free)
+    np.testing.assert_array_equal(by[100], free)
+    for low, high in ((0, 1), (1, 2), (2, 6)):
+        assert (by[low] != by[high]).any(), (low, high)
+    free = ro.estimate_shifts(rc.edge("16x12-u10-ms8")["stack"], upsample=10)[0]
+    by = {ms: answer("16x12-u10", ms) for ms in rc.MASKS_16x12}
+    coarse = ro.estimate_shifts(rc.edge("16x12-u10-ms8")["stack"], upsample=1)[0]
+    np.testing.assert_array_equal(coarse[1:], [[-8, -6], [-8, -6]])     # row 8 and column 6: the lags -n / 2 of 16 and 12
+    np.testing.assert_array_equal(by[8], free)
+    for low, high in ((5, 6), (7, 8)):                                  # 6 admits column 6 and 8 admits row 8; 5 and 7 do not
+        assert (by[low] != by[high]).any(), (low, high)
+
+
+def _constant(name):
+    text = open(os.path.join(ROOT, "motif-learn_amd", "csrc", "zk_register.hip")).read()
+    m = re.search(rf"constexpr \w+ {name} = (?:\(size_t\))?(\d+)(?: << (\d+))?;", text)
+    return int(m.group(1)) << int(m.group(2) or 0)
+
+
+def test_edge_sizes_reach_what_they_are_for():
+    """The sizes of the edge cases against the constants of csrc/zk_register.hip: were a constant to change, the cases would
+    quietly stop reaching the branches they were chosen for."""
+    red, gt, gk = _constant("RED_PER_BLOCK"), _constant("GT"), _constant("GK")
+    field, table, mean = _constant("FIELD_BYTES"), _constant("TABLE_BYTES"), _constant("MEAN_BUDGET")
+    parts = lambda h, w: -(-h * w // red)
+    assert (red, gt, gk) == (4096, 64, 16)
+    assert parts(72, 136) == 3 and 72 * 136 - 2 * red == 1600 and (136 // gt, 136 % gt) == (2, 8) and (72 // gk, 72 % gk) == (4, 8)
+    assert [k // red for k in _flat_lags(rc.edge("72x136-u1"))] == [0, 0, 1, 2, 1]
+    rows = np.arange(72)
+    shut = rows[np.abs(np.fft.fftfreq(72, 1 / 72)) > 10]
+    assert shut.min() * 136 <= red and shut.max() * 136 + 135 >= 2 * red - 1          # max_shift = 10 shuts all of partial 1
+    assert parts(128, 64) == 2
+    assert parts(1040, 1032) == 263 and [k // red for k in _flat_lags(rc.edge("1040x1032-u10"))] == [0, 0, 262]
+    assert field // (512 * 512 * 32) == 128                                          # runs of 128 + 2, and of 128 + 1
+    s = 1500
+    assert table // ((s * (16 + 2 * 16) * 2 + s * s) * 8) == 56                      # runs of 56 + 56 + 8
+    chunk = mean // (2100 + 8) & ~255
+    assert (chunk, 257 * 511 - chunk) == (127232, 4095)                              # the two pixel chunks of the chunked mean
 
 
 def test_previous_is_the_running_sum_of_pairwise_answers():
