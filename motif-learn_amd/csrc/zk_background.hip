@@ -421,13 +421,11 @@ int run_host(int device, const args& a, const void* img_host, int dtype, int64_t
   ZK_ON_DEVICE(device);
   const size_t in_bytes = (size_t)H * W * zk_elem_size(dtype);
   const size_t out_bytes = a.method == M_BASELINE ? (size_t)H * W * 8 : in_bytes;
-  dev_buf d_img, d_bg, d_res;
-  if ((rc = d_img.alloc(in_bytes)) || (rc = d_bg.alloc(out_bytes)) || (res_host && (rc = d_res.alloc(out_bytes)))) return rc;
-  ZK_HIP(hipMemcpy(d_img.p, img_host, in_bytes, hipMemcpyHostToDevice));
-  if ((rc = run(a, d_img.p, dtype, (int)H, (int)W, clip, d_bg.p, res_host ? d_res.p : nullptr, (hipStream_t)0))) return rc;
-  ZK_HIP(hipMemcpy(bg_host, d_bg.p, out_bytes, hipMemcpyDeviceToHost));
-  if (res_host) ZK_HIP(hipMemcpy(res_host, d_res.p, out_bytes, hipMemcpyDeviceToHost));
-  return 0;
+  dev_buf d_img, d_bg, d_res;                        // d_res stays null without a res_host
+  if ((rc = d_img.upload(img_host, in_bytes)) || (rc = d_bg.alloc(out_bytes)) || (res_host && (rc = d_res.alloc(out_bytes)))) return rc;
+  if ((rc = run(a, d_img.p, dtype, (int)H, (int)W, clip, d_bg.p, d_res.p, (hipStream_t)0)) || (rc = d_bg.download(bg_host, out_bytes)))
+    return rc;
+  return d_res.download(res_host, out_bytes);
 }
 
 args opening_args(int64_t size_y, int64_t size_x) {

@@ -331,11 +331,14 @@ extern "C" int zk_com_refine(int device, const void* image_host, int image_dtype
   if (n == 0) return 0;
   ZK_ON_DEVICE(device);
   const size_t count = (size_t)n;
-  host_stage st;
-  if ((rc = st.up(image_host, image_dtype, H, W, corners_host, n, {sizeof(double) * 2 * count, sizeof(double) * count, sizeof(int32_t) * count})) ||
-      (rc = com_call("com_refine", st.img.p, image_dtype, H, W, st.rows.p, CORNERS, n, (int)size, threshold, st.out[0].as<double>(),
-                     st.out[1].as<double>(), st.out[2].as<int>(), (hipStream_t)0)) ||
-      (rc = st.fetch(0, centroids_out)) || (rc = st.fetch(1, thresholds_out)))
+  const size_t img_bytes = zk_elem_size(image_dtype) * (size_t)H * (size_t)W, corner_bytes = sizeof(int32_t) * 2 * count,
+               cen_bytes = sizeof(double) * 2 * count, thr_bytes = sizeof(double) * count, it_bytes = sizeof(int32_t) * count;
+  dev_buf d_img, d_corners, d_cen, d_thr, d_it;      // the three results are computed whether or not the caller takes them
+  if ((rc = d_img.upload(image_host, img_bytes)) || (rc = d_corners.upload(corners_host, corner_bytes)) || (rc = d_cen.alloc(cen_bytes)) ||
+      (rc = d_thr.alloc(thr_bytes)) || (rc = d_it.alloc(it_bytes)) ||
+      (rc = com_call("com_refine", d_img.p, image_dtype, H, W, d_corners.p, CORNERS, n, (int)size, threshold, d_cen.as<double>(),
+                     d_thr.as<double>(), d_it.as<int>(), (hipStream_t)0)) ||
+      (rc = d_cen.download(centroids_out, cen_bytes)) || (rc = d_thr.download(thresholds_out, thr_bytes)))
     return rc;
-  return st.fetch(2, iterations_out);
+  return d_it.download(iterations_out, it_bytes);
 }

@@ -5,6 +5,7 @@
 // (45 x 45 at n_max 8) is LAPACK's on the host, as in scikit-learn's own "covariance_eigh" solver, whose arithmetic the
 // Python wrapper follows (mtflearn_amd/features/consumers.py).
 #include "zk_internal.h"
+#include "zk_scratch.h"
 
 namespace {
 
@@ -113,22 +114,13 @@ extern "C" int zk_gram(int device, const double* X_host, int64_t N, int D, doubl
   if (N <= 0 || D <= 0 || D > 127) return zk_fail(ZK_E_BADARG, "need 1 <= D <= 127 features and N > 0 rows");
   ZK_ON_DEVICE(device);
   *X_dev_out = nullptr;
-  double *d_x = nullptr, *d_g = nullptr;
-  const size_t gb = (size_t)(D + 1) * (D + 1) * sizeof(double);
-  ZK_HIP(hipMalloc((void**)&d_x, (size_t)N * D * sizeof(double)));
-  hipError_t e = hipMalloc((void**)&d_g, gb);
-  if (e == hipSuccess) e = hipMemcpy(d_x, X_host, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice);
-  int rc = e == hipSuccess ? zk_gram_dev(device, d_x, N, D, d_g, nullptr) : zk_hip_fail(e, "zk_gram staging");
-  if (!rc) {
-    e = hipMemcpy(gram_host, d_g, gb, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = zk_hip_fail(e, "hipMemcpy(gram)");
-  }
-  if (d_g) (void)hipFree(d_g);
-  if (rc) {
-    (void)hipFree(d_x);
+  const size_t x_bytes = (size_t)N * D * sizeof(double), g_bytes = (size_t)(D + 1) * (D + 1) * sizeof(double);
+  dev_buf d_x, d_g;
+  int rc;
+  if ((rc = d_x.upload(X_host, x_bytes)) || (rc = d_g.alloc(g_bytes)) ||
+      (rc = zk_gram_dev(device, d_x.as<double>(), N, D, d_g.as<double>(), nullptr)) || (rc = d_g.download(gram_host, g_bytes)))
     return rc;
-  }
-  *X_dev_out = d_x;
+  *X_dev_out = d_x.release();
   return 0;
 }
 
@@ -136,23 +128,15 @@ extern "C" int zk_project(int device, const void* X_dev, int64_t N, int D, const
                           double* Y_host, int free_x) {
   if (!X_dev || !mean_host || !comp_host || !Y_host) return zk_fail(ZK_E_BADARG, "null pointer");
   ZK_ON_DEVICE(device);
-  if (N <= 0 || D <= 0 || k <= 0 || k > 16) {
-    if (free_x) (void)hipFree((void*)X_dev);  // free_x holds on every exit path once X_dev is known
-    return zk_fail(ZK_E_BADARG, "need N, D > 0 and 1 <= k <= 16 components");
-  }
-  double *d_t = nullptr, *d_y = nullptr;
-  hipError_t e = hipMalloc((void**)&d_t, (size_t)(D + (size_t)k * D) * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_y, (size_t)N * k * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(d_t, mean_host, (size_t)D * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_t + D, comp_host, (size_t)k * D * sizeof(double), hipMemcpyHostToDevice);
-  int rc = e == hipSuccess ? zk_project_dev(device, (const double*)X_dev, N, D, d_t, d_t + D, k, d_y, nullptr)
-                           : zk_hip_fail(e, "zk_project staging");
-  if (!rc) {
-    e = hipMemcpy(Y_host, d_y, (size_t)N * k * sizeof(double), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = zk_hip_fail(e, "hipMemcpy(Y)");
-  }
-  if (d_t) (void)hipFree(d_t);
-  if (d_y) (void)hipFree(d_y);
-  if (free_x) (void)hipFree((void*)X_dev);
-  return rc;
+  dev_buf x_owned;                                   // free_x holds on every exit path once X_dev is known; without it X_dev stays the caller's
+  if (free_x) x_owned.p = (void*)X_dev;
+  if (N <= 0 || D <= 0 || k <= 0 || k > 16) return zk_fail(ZK_E_BADARG, "need N, D > 0 and 1 <= k <= 16 components");
+  const size_t mean_bytes = (size_t)D * sizeof(double), comp_bytes = (size_t)k * D * sizeof(double), y_bytes = (size_t)N * k * sizeof(double);
+  dev_buf d_t, d_y;                                  // d_t: the mean, then the components
+  int rc;
+  if ((rc = d_t.alloc(mean_bytes + comp_bytes)) || (rc = d_y.alloc(y_bytes))) return rc;
+  ZK_HIP(hipMemcpy(d_t.p, mean_host, mean_bytes, hipMemcpyHostToDevice));
+  ZK_HIP(hipMemcpy(d_t.as<double>() + D, comp_host, comp_bytes, hipMemcpyHostToDevice));
+  if ((rc = zk_project_dev(device, (const double*)X_dev, N, D, d_t.as<double>(), d_t.as<double>() + D, k, d_y.as<double>(), nullptr))) return rc;
+  return d_y.download(Y_host, y_bytes);
 }

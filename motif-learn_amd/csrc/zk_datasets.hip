@@ -393,11 +393,9 @@ extern "C" int zk_render_gaussians(int device, void* frame_host, int dtype, int6
   ZK_ON_DEVICE(device);
   const size_t bytes = (size_t)batch * height * width * (dtype == ZK_F64 ? 8 : 4);
   dev_buf d_frame;
-  if ((rc = d_frame.alloc(bytes))) return rc;
-  ZK_HIP(hipMemcpy(d_frame.p, frame_host, bytes, hipMemcpyHostToDevice));
+  if ((rc = d_frame.upload(frame_host, bytes))) return rc;
   if ((rc = render_run(d_frame.p, dtype, height, width, batch, points_host, amplitudes_host, point_offsets_host, n_points, sigma,
                        r_factor, taper, list_budget, (hipStream_t)0)))
     return rc;
-  ZK_HIP(hipMemcpy(frame_host, d_frame.p, bytes, hipMemcpyDeviceToHost));
-  return 0;
+  return d_frame.download(frame_host, bytes);
 }

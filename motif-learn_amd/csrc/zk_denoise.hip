@@ -485,18 +485,9 @@ int reconstruct_dev(int device, int64_t H, int64_t W, int64_t ph, int64_t pw, co
   return 0;
 }
 
-// host-buffer forms: operands up, one device call, result down ----------------------------------------------------------------
-struct staged {
-  dev_buf b;
-  int up(const void* host, size_t bytes) {
-    int rc = b.alloc(bytes);
-    if (rc) return rc;
-    ZK_HIP(hipMemcpy(b.p, host, bytes, hipMemcpyHostToDevice));
-    return 0;
-  }
-};
-
 }  // namespace
+
+// the host-buffer forms below: operands up (dev_buf::upload; an absent mean or V stays a null pointer), one device call, result down
 
 // ---------------------------------------------------------------------------------------------------------
 extern "C" int zk_windows_apply_dev(int device, const void* image_dev, int dtype, int64_t height, int64_t width, int64_t patch_h,
@@ -515,16 +506,15 @@ extern "C" int zk_windows_apply(int device, const void* image_host, int dtype, i
   if (!image_host || !Q_host || !Y_host || n_rows < 1 || n_cols < 1) return zk_fail(ZK_E_BADARG, "null pointer or empty grid");
   ZK_ON_DEVICE(device);
   const size_t D = (size_t)patch_h * patch_w, N = (size_t)n_rows * n_cols;
-  staged img, Q, mu;
-  dev_buf Y;
-  if ((rc = img.up(image_host, (size_t)height * width * zk_elem_size(dtype))) || (rc = Q.up(Q_host, D * n_columns * 8)) ||
-      (mean_host && (rc = mu.up(mean_host, D * 8))) || (rc = Y.alloc(N * n_columns * 8)))
+  const size_t img_bytes = (size_t)height * width * zk_elem_size(dtype), q_bytes = D * n_columns * 8, mu_bytes = D * 8, y_bytes = N * n_columns * 8;
+  dev_buf img, Q, mu, Y;
+  if ((rc = img.upload(image_host, img_bytes)) || (rc = Q.upload(Q_host, q_bytes)) || (rc = mu.upload(mean_host, mu_bytes)) ||
+      (rc = Y.alloc(y_bytes)))
     return rc;
-  if ((rc = apply_dev(device, img.b.p, dtype, height, width, patch_h, patch_w, row_origins, n_rows, col_origins, n_cols, Q.b.as<double>(),
-                      n_columns, mean_host ? mu.b.as<double>() : nullptr, Y.as<double>(), (hipStream_t)0)))
+  if ((rc = apply_dev(device, img.p, dtype, height, width, patch_h, patch_w, row_origins, n_rows, col_origins, n_cols, Q.as<double>(),
+                      n_columns, mu.as<double>(), Y.as<double>(), (hipStream_t)0)))
     return rc;
-  ZK_HIP(hipMemcpy(Y_host, Y.p, N * n_columns * 8, hipMemcpyDeviceToHost));
-  return 0;
+  return Y.download(Y_host, y_bytes);
 }
 
 extern "C" int zk_windows_apply_t_dev(int device, const void* image_dev, int dtype, int64_t height, int64_t width, int64_t patch_h,
@@ -542,16 +532,13 @@ extern "C" int zk_windows_apply_t(int device, const void* image_host, int dtype,
   if (!image_host || !Y_host || !Z_host || n_rows < 1 || n_cols < 1) return zk_fail(ZK_E_BADARG, "null pointer or empty grid");
   ZK_ON_DEVICE(device);
   const size_t D = (size_t)patch_h * patch_w, N = (size_t)n_rows * n_cols;
-  staged img, Y;
-  dev_buf Z;
-  if ((rc = img.up(image_host, (size_t)height * width * zk_elem_size(dtype))) || (rc = Y.up(Y_host, N * n_columns * 8)) ||
-      (rc = Z.alloc(D * n_columns * 8)))
-    return rc;
-  if ((rc = apply_t_dev(device, img.b.p, dtype, height, width, patch_h, patch_w, row_origins, n_rows, col_origins, n_cols, Y.b.as<double>(),
+  const size_t img_bytes = (size_t)height * width * zk_elem_size(dtype), y_bytes = N * n_columns * 8, z_bytes = D * n_columns * 8;
+  dev_buf img, Y, Z;
+  if ((rc = img.upload(image_host, img_bytes)) || (rc = Y.upload(Y_host, y_bytes)) || (rc = Z.alloc(z_bytes))) return rc;
+  if ((rc = apply_t_dev(device, img.p, dtype, height, width, patch_h, patch_w, row_origins, n_rows, col_origins, n_cols, Y.as<double>(),
                         n_columns, Z.as<double>(), (hipStream_t)0)))
     return rc;
-  ZK_HIP(hipMemcpy(Z_host, Z.p, D * n_columns * 8, hipMemcpyDeviceToHost));
-  return 0;
+  return Z.download(Z_host, z_bytes);
 }
 
 extern "C" int zk_windows_moments_dev(int device, const void* image_dev, int dtype, int64_t height, int64_t width, int64_t patch_h,
@@ -566,13 +553,12 @@ extern "C" int zk_windows_moments(int device, const void* image_host, int dtype,
   if (!image_host || !mean_host || !cov_host) return zk_fail(ZK_E_BADARG, "null pointer");
   ZK_ON_DEVICE(device);
   const size_t D = (size_t)patch_h * patch_w;
-  staged img;
-  dev_buf mu, C;
-  if ((rc = img.up(image_host, (size_t)height * width * zk_elem_size(dtype))) || (rc = mu.alloc(D * 8)) || (rc = C.alloc(D * D * 8))) return rc;
-  if ((rc = moments_dev(device, img.b.p, dtype, height, width, patch_h, patch_w, mu.as<double>(), C.as<double>(), (hipStream_t)0))) return rc;
-  ZK_HIP(hipMemcpy(mean_host, mu.p, D * 8, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(cov_host, C.p, D * D * 8, hipMemcpyDeviceToHost));
-  return 0;
+  const size_t img_bytes = (size_t)height * width * zk_elem_size(dtype), mu_bytes = D * 8, c_bytes = D * D * 8;
+  dev_buf img, mu, C;
+  if ((rc = img.upload(image_host, img_bytes)) || (rc = mu.alloc(mu_bytes)) || (rc = C.alloc(c_bytes))) return rc;
+  if ((rc = moments_dev(device, img.p, dtype, height, width, patch_h, patch_w, mu.as<double>(), C.as<double>(), (hipStream_t)0))) return rc;
+  if ((rc = mu.download(mean_host, mu_bytes))) return rc;
+  return C.download(cov_host, c_bytes);
 }
 
 extern "C" int zk_windows_reconstruct_dev(int device, int64_t height, int64_t width, int64_t patch_h, int64_t patch_w,
@@ -593,14 +579,14 @@ extern "C" int zk_windows_reconstruct(int device, int64_t height, int64_t width,
   if (!Y_host || !out_host || n_rows < 1 || n_cols < 1) return zk_fail(ZK_E_BADARG, "null pointer or empty grid");
   ZK_ON_DEVICE(device);
   const size_t D = (size_t)patch_h * patch_w, N = (size_t)n_rows * n_cols;
-  staged Y, V, mu;
-  dev_buf out;
-  if ((rc = Y.up(Y_host, N * (V_host ? (size_t)n_components : D) * 8)) || (V_host && (rc = V.up(V_host, (size_t)n_components * D * 8))) ||
-      (mean_host && (rc = mu.up(mean_host, D * 8))) || (rc = out.alloc((size_t)height * width * 8)))
+  const size_t y_bytes = N * (V_host ? (size_t)n_components : D) * 8, v_bytes = (size_t)n_components * D * 8, mu_bytes = D * 8,
+               out_bytes = (size_t)height * width * 8;
+  dev_buf Y, V, mu, out;
+  if ((rc = Y.upload(Y_host, y_bytes)) || (rc = V.upload(V_host, v_bytes)) || (rc = mu.upload(mean_host, mu_bytes)) ||
+      (rc = out.alloc(out_bytes)))
     return rc;
-  if ((rc = reconstruct_dev(device, height, width, patch_h, patch_w, row_origins, n_rows, col_origins, n_cols, Y.b.as<double>(), n_components,
-                            V_host ? V.b.as<double>() : nullptr, mean_host ? mu.b.as<double>() : nullptr, out.as<double>(), (hipStream_t)0)))
+  if ((rc = reconstruct_dev(device, height, width, patch_h, patch_w, row_origins, n_rows, col_origins, n_cols, Y.as<double>(), n_components,
+                            V.as<double>(), mu.as<double>(), out.as<double>(), (hipStream_t)0)))
     return rc;
-  ZK_HIP(hipMemcpy(out_host, out.p, (size_t)height * width * 8, hipMemcpyDeviceToHost));
-  return 0;
+  return out.download(out_host, out_bytes);
 }

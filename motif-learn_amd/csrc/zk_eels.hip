@@ -546,26 +546,18 @@ int run_dev(int device, const eels_job& j, const void* data, int dtype, int64_t 
 // the host-buffer form: the cube goes up, baseline (signal, iteration counts) come down
 int run_host(int device, eels_job j, const void* data, int dtype, int64_t A, int64_t L, int64_t B, const double* weights_host, double* baseline,
              double* signal, int32_t* iters) {
-  const size_t total = (size_t)A * L * B, in_bytes = total * zk_elem_size(dtype), n_spectra = (size_t)A * B;
-  dev_buf d_data, d_base, d_sig, d_it, d_w;
+  const size_t total = (size_t)A * L * B, in_bytes = total * zk_elem_size(dtype), out_bytes = total * 8, it_bytes = (size_t)A * B * 4,
+               w_bytes = (j.weights_per_spectrum ? total : (size_t)L) * 8;
+  dev_buf d_data, d_base, d_sig, d_it, d_w;          // d_sig, d_it and d_w stay null for what the caller left out
   int rc;
-  if ((rc = d_data.alloc(in_bytes)) || (rc = d_base.alloc(total * 8)) || (signal && (rc = d_sig.alloc(total * 8))) ||
-      (iters && (rc = d_it.alloc(n_spectra * 4))))
+  if ((rc = d_data.upload(data, in_bytes)) || (rc = d_base.alloc(out_bytes)) || (signal && (rc = d_sig.alloc(out_bytes))) ||
+      (iters && (rc = d_it.alloc(it_bytes))) || (rc = d_w.upload(weights_host, w_bytes)))
     return rc;
-  ZK_HIP(hipMemcpy(d_data.p, data, in_bytes, hipMemcpyHostToDevice));
-  if (weights_host) {
-    const size_t wbytes = (j.weights_per_spectrum ? total : (size_t)L) * 8;
-    if ((rc = d_w.alloc(wbytes))) return rc;
-    ZK_HIP(hipMemcpy(d_w.p, weights_host, wbytes, hipMemcpyHostToDevice));
-    j.weights = d_w.as<double>();
-  }
-  if ((rc = run_dev(device, j, d_data.p, dtype, A, L, B, d_base.as<double>(), signal ? d_sig.as<double>() : nullptr,
-                    iters ? d_it.as<int32_t>() : nullptr, (hipStream_t)0)))
+  j.weights = d_w.as<double>();
+  if ((rc = run_dev(device, j, d_data.p, dtype, A, L, B, d_base.as<double>(), d_sig.as<double>(), d_it.as<int32_t>(), (hipStream_t)0)) ||
+      (rc = d_base.download(baseline, out_bytes)) || (rc = d_sig.download(signal, out_bytes)))
     return rc;
-  ZK_HIP(hipMemcpy(baseline, d_base.p, total * 8, hipMemcpyDeviceToHost));
-  if (signal) ZK_HIP(hipMemcpy(signal, d_sig.p, total * 8, hipMemcpyDeviceToHost));
-  if (iters) ZK_HIP(hipMemcpy(iters, d_it.p, n_spectra * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return d_it.download(iters, it_bytes);
 }
 
 eels_job snip_job(int niter) {

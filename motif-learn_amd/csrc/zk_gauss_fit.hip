@@ -379,12 +379,15 @@ extern "C" int zk_gauss_fit(int device, const void* image_host, int image_dtype,
   if (n == 0) return 0;
   ZK_ON_DEVICE(device);
   const size_t count = (size_t)n;
-  host_stage st;
-  if ((rc = st.up(image_host, image_dtype, H, W, corners_host, n, {sizeof(double) * 8 * count, sizeof(int32_t) * count, sizeof(int32_t) * count})) ||
+  const size_t img_bytes = zk_elem_size(image_dtype) * (size_t)H * (size_t)W, corner_bytes = sizeof(int32_t) * 2 * count,
+               par_bytes = sizeof(double) * 8 * count, int_bytes = sizeof(int32_t) * count;
+  dev_buf d_img, d_corners, d_par, d_it, d_status;
+  if ((rc = d_img.upload(image_host, img_bytes)) || (rc = d_corners.upload(corners_host, corner_bytes)) || (rc = d_par.alloc(par_bytes)) ||
+      (rc = d_it.alloc(int_bytes)) || (rc = d_status.alloc(int_bytes)) ||
       (rc = fit_call("gauss_fit", image_dtype, model,
-                     fit_args{st.img.p, H, W, st.rows.p, CORNERS, n, (int)size, mask, sigma0, tol, (int)max_iter, st.out[0].as<double>(),
-                              st.out[1].as<int>(), st.out[2].as<int>(), nullptr, (hipStream_t)0})) ||
-      (rc = st.fetch(0, params_out)) || (rc = st.fetch(1, iterations_out)))
+                     fit_args{d_img.p, H, W, d_corners.p, CORNERS, n, (int)size, mask, sigma0, tol, (int)max_iter, d_par.as<double>(),
+                              d_it.as<int>(), d_status.as<int>(), nullptr, (hipStream_t)0})) ||
+      (rc = d_par.download(params_out, par_bytes)) || (rc = d_it.download(iterations_out, int_bytes)))
     return rc;
-  return st.fetch(2, status_out);
+  return d_status.download(status_out, int_bytes);
 }

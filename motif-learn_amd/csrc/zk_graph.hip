@@ -9,6 +9,7 @@
 //                                   zk_force_layout_stage, operation for operation.
 // The sparse symmetrisation between them is SciPy's, as in the reference (mtflearn_amd/manifold.py).
 #include "zk_rows.h"  // the resident matrix; ZK_GLOBAL_PTR / ZK_LDS_PTR
+#include "zk_scratch.h"
 
 #include <cmath>
 #include <cstring>
@@ -412,32 +413,23 @@ extern "C" int zk_rows_knn_correlation(zk_rows* m, int k, int local_connectivity
   ZK_ON_DEVICE(m->device);
   hipStream_t s = m->stream;
   const long long Np = (N + 7) & ~7LL;
-  double *Z = nullptr, *Zt = nullptr, *d_dist = nullptr, *d_P = nullptr;
-  long long* d_ind = nullptr;
-  void* part_bufs[2] = {nullptr, nullptr};
-  auto cleanup = [&]() {
-    for (void* p : {(void*)Z, (void*)Zt, (void*)d_dist, (void*)d_P, (void*)d_ind, part_bufs[0], part_bufs[1]})
-      if (p) (void)hipFree(p);
-  };
+  // every buffer of the call, the part lists included: freed with the scope, after the one synchronise below (on an early
+  // return hipFree waits for what is in flight)
+  dev_buf b_Z, b_Zt, b_dist, b_ind, b_P, b_pind, b_pdist;
   // k <= 16 and D <= 96: the matrix-core kernel on the blocked copy (ZK_KNN_SCALAR=1 keeps the scalar-operand kernel for A/B)
   const bool mfma = k <= 16 && D <= 96 && N < (1LL << 31) - 64 && zk_switch_int(ZK_KNN_SCALAR, 0) != 1;
   // feature steps of the blocked copy: the kernel instance that holds D (zero features beyond it)
   const int steps = D <= 8 ? 2 : D <= 16 ? 4 : D <= 32 ? 8 : (D + 15) / 16 * 4;
   const long long Np64 = (N + 63) & ~63LL;
-  hipError_t e = hipSuccess;
+  const size_t dist_bytes = (size_t)N * k * sizeof(double), ind_bytes = (size_t)N * k * sizeof(long long);
+  int rc;
   if (mfma)
-    e = hipMalloc((void**)&Z, (size_t)Np64 * steps * 4 * sizeof(double));
-  else {
-    e = hipMalloc((void**)&Z, (size_t)N * D * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&Zt, (size_t)Np * D * sizeof(double) + 256);
-  }
-  if (e == hipSuccess) e = hipMalloc((void**)&d_dist, (size_t)N * k * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_ind, (size_t)N * k * sizeof(long long));
-  if (e == hipSuccess && P_out) e = hipMalloc((void**)&d_P, (size_t)N * k * sizeof(double));
-  if (e != hipSuccess) {
-    cleanup();
-    return zk_hip_fail(e, "hipMalloc(kNN buffers)");
-  }
+    rc = b_Z.alloc((size_t)Np64 * steps * 4 * sizeof(double));
+  else if (!(rc = b_Z.alloc((size_t)N * D * sizeof(double))))
+    rc = b_Zt.alloc((size_t)Np * D * sizeof(double) + 256);
+  if (rc || (rc = b_dist.alloc(dist_bytes)) || (rc = b_ind.alloc(ind_bytes)) || (P_out && (rc = b_P.alloc(dist_bytes)))) return rc;
+  double *const Z = b_Z.as<double>(), *const Zt = b_Zt.as<double>(), *const d_dist = b_dist.as<double>(), *const d_P = b_P.as<double>();
+  long long* const d_ind = b_ind.as<long long>();
   if (mfma) {
     hipLaunchKernelGGL(unit_rows_blocked_kernel, dim3((unsigned)((Np64 + 255) / 256)), dim3(256), 0, s, m->X, (long long)N, D, Np64,
                        steps, Z);
@@ -455,17 +447,9 @@ extern "C" int zk_rows_knn_correlation(zk_rows* m, int k, int local_connectivity
     int parts = (int)zk_switch_int(ZK_KNN_PARTS, 3u * 256u / tiles);
     if (parts > n_stages / 16) parts = (int)(n_stages / 16);
     parts = parts < 1 ? 1 : parts > 16 ? 16 : parts;
-    int* d_pind = nullptr;
-    double* d_pdist = nullptr;
-    if (parts > 1) {
-      e = hipMalloc((void**)&d_pind, (size_t)parts * N * k * sizeof(int));
-      if (e == hipSuccess) e = hipMalloc((void**)&d_pdist, (size_t)parts * N * k * sizeof(double));
-      if (e != hipSuccess) {
-        if (d_pind) (void)hipFree(d_pind);
-        cleanup();
-        return zk_hip_fail(e, "hipMalloc(kNN part lists)");
-      }
-    }
+    if (parts > 1 && ((rc = b_pind.alloc((size_t)parts * N * k * sizeof(int))) || (rc = b_pdist.alloc((size_t)parts * dist_bytes)))) return rc;
+    int* const d_pind = b_pind.as<int>();            // null for one part
+    double* const d_pdist = b_pdist.as<double>();
     const dim3 grid1(tiles1, parts);
     // (lists of 10 entries for k <= 10, ForceGraph8's default: a shorter insertion chain)
 #define ZK_KNN_CASE(NS)                                                                                                                  \
@@ -487,12 +471,8 @@ extern "C" int zk_rows_knn_correlation(zk_rows* m, int k, int local_connectivity
       ZK_KNN_CASE(24)
     }
 #undef ZK_KNN_CASE
-    if (parts > 1) {
+    if (parts > 1)
       hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, d_pind, d_pdist, (long long)N, k, parts, d_ind, d_dist);
-      // (freed after the stream has drained: cleanup() below runs after hipStreamSynchronize)
-      part_bufs[0] = d_pind;
-      part_bufs[1] = d_pdist;
-    }
   } else {
     hipLaunchKernelGGL(unit_rows_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, m->X, (long long)N, D, Np, Z, Zt);
     const size_t lds = (size_t)64 * D * sizeof(double);
@@ -507,12 +487,11 @@ extern "C" int zk_rows_knn_correlation(zk_rows* m, int k, int local_connectivity
   if (P_out)
     hipLaunchKernelGGL(affinity_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, d_dist, (long long)N, k, local_connectivity,
                        std::log2(perplexity), d_P);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(ind_out, d_ind, (size_t)N * k * sizeof(long long), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(dist_out, d_dist, (size_t)N * k * sizeof(double), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess && P_out) e = hipMemcpyAsync(P_out, d_P, (size_t)N * k * sizeof(double), hipMemcpyDeviceToHost, s);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(ind_out, d_ind, ind_bytes, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(dist_out, d_dist, dist_bytes, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && P_out) e = hipMemcpyAsync(P_out, d_P, dist_bytes, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  cleanup();
   return e == hipSuccess ? 0 : zk_hip_fail(e, "zk_rows_knn_correlation");
 }
 

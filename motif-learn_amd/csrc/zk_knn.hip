@@ -406,13 +406,13 @@ extern "C" int zk_knn_distances(int device, const void* points_host, int points_
     for (int64_t q = 0; q < 2 * n_points; ++q)
       if (!(fabs(((const double*)points_host)[q]) <= DBL_BIG)) return zk_fail(ZK_E_BADARG, "knn_distances: a point is not finite");
   ZK_ON_DEVICE(device);
-  const size_t bytes = (points_dtype == ZK_I32 ? sizeof(int32_t) : sizeof(double)) * 2 * (size_t)n_points;
+  const size_t pts_bytes = (points_dtype == ZK_I32 ? sizeof(int32_t) : sizeof(double)) * 2 * (size_t)n_points,
+               out_bytes = sizeof(double) * (size_t)k * (size_t)n_points;
   dev_buf d_pts, d_out;
-  if ((rc = d_pts.alloc(bytes)) || (rc = d_out.alloc(sizeof(double) * (size_t)k * (size_t)n_points))) return rc;
-  ZK_HIP(hipMemcpy(d_pts.p, points_host, bytes, hipMemcpyHostToDevice));
-  if ((rc = knn_call(d_pts.p, points_dtype, n_points, k, d_out.as<double>(), (hipStream_t)0))) return rc;
-  ZK_HIP(hipMemcpy(out_host, d_out.p, sizeof(double) * (size_t)k * (size_t)n_points, hipMemcpyDeviceToHost));
-  return 0;
+  if ((rc = d_pts.upload(points_host, pts_bytes)) || (rc = d_out.alloc(out_bytes)) ||
+      (rc = knn_call(d_pts.p, points_dtype, n_points, k, d_out.as<double>(), (hipStream_t)0)))
+    return rc;
+  return d_out.download(out_host, out_bytes);
 }
 
 extern "C" int zk_knn_stats_dev(int device, const double* dd_dev, int64_t n_points, int op, const double* params_host, int64_t* counts_host,
@@ -429,7 +429,6 @@ extern "C" int zk_knn_stats(int device, const double* dd_host, int64_t n_points,
   if (rc) return rc;
   ZK_ON_DEVICE(device);
   dev_buf d_dd;
-  if ((rc = d_dd.alloc(sizeof(double) * KNN * (size_t)n_points))) return rc;
-  ZK_HIP(hipMemcpy(d_dd.p, dd_host, sizeof(double) * KNN * (size_t)n_points, hipMemcpyHostToDevice));
+  if ((rc = d_dd.upload(dd_host, sizeof(double) * KNN * (size_t)n_points))) return rc;
   return stats_call(d_dd.as<double>(), n_points, op, params_host, counts_host, sums_host, (hipStream_t)0);
 }

@@ -439,17 +439,16 @@ extern "C" int zk_local_max(int device, const void* image_host, int dtype, int64
   int rc = check_args(dtype, height, width, image_host, min_distance, capacity, points_host, n_found);
   if (rc) return rc;
   ZK_ON_DEVICE(device);
-  const size_t bytes = (size_t)height * width * zk_elem_size(dtype);
+  const size_t img_bytes = (size_t)height * width * zk_elem_size(dtype);
   dev_buf d_img, d_pts;
-  if ((rc = d_img.alloc(bytes)) || (rc = d_pts.alloc((size_t)std::max<int64_t>(capacity, 1) * 8))) return rc;
-  ZK_HIP(hipMemcpy(d_img.p, image_host, bytes, hipMemcpyHostToDevice));
+  if ((rc = d_img.upload(image_host, img_bytes)) || (rc = d_pts.alloc((size_t)std::max<int64_t>(capacity, 1) * 8))) return rc;
   if ((rc = local_max_core(d_img.p, dtype, (int)height, (int)width, min_distance, has_threshold, threshold, d_pts.as<int32_t>(),
                            capacity, n_found, (hipStream_t)0)))
     return rc;
   const int64_t n_out = std::min(*n_found, capacity);
   if (n_out > 0) {
     std::vector<int32_t> pts((size_t)n_out * 2);
-    ZK_HIP(hipMemcpy(pts.data(), d_pts.p, pts.size() * 4, hipMemcpyDeviceToHost));
+    if ((rc = d_pts.download(pts.data(), pts.size() * 4))) return rc;   // the points found, widened to int64 below
     for (size_t i = 0; i < pts.size(); ++i) points_host[i] = pts[i];
   }
   return 0;

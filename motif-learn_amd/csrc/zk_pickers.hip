@@ -470,14 +470,12 @@ extern "C" int zk_autocorr_mean(int device, const void* image_host, int dtype, i
   if ((rc = zk_fft_load())) return rc;
   ZK_ON_DEVICE(device);
   const int ws = (int)window;
-  const size_t es = zk_elem_size(dtype);
+  const size_t img_bytes = (size_t)H * W * zk_elem_size(dtype), org_bytes = (size_t)n_windows * 8, acc_bytes = (size_t)ws * ws * 8;
   dev_buf d_img, d_org, d_stats, d_acc;
-  if ((rc = d_img.alloc((size_t)H * W * es)) || (rc = d_org.alloc((size_t)n_windows * 8)) ||
-      (rc = d_stats.alloc((size_t)n_windows * 16)) || (rc = d_acc.alloc((size_t)ws * ws * 8)))
+  if ((rc = d_img.upload(image_host, img_bytes)) || (rc = d_org.upload(origins_yx, org_bytes)) ||
+      (rc = d_stats.alloc((size_t)n_windows * 16)) || (rc = d_acc.alloc(acc_bytes)))
     return rc;
-  ZK_HIP(hipMemcpy(d_img.p, image_host, (size_t)H * W * es, hipMemcpyHostToDevice));
-  ZK_HIP(hipMemcpy(d_org.p, origins_yx, (size_t)n_windows * 8, hipMemcpyHostToDevice));
-  ZK_HIP(hipMemset(d_acc.p, 0, (size_t)ws * ws * 8));
+  ZK_HIP(hipMemset(d_acc.p, 0, acc_bytes));
   if (standardize) {
     if ((rc = zk_window_stats_dev(d_img.p, dtype, W, d_org.as<int32_t>(), n_windows, ws, ws, d_stats.as<double>()))) return rc;
     std::vector<double> st((size_t)2 * n_windows);
@@ -488,8 +486,7 @@ extern "C" int zk_autocorr_mean(int device, const void* image_host, int dtype, i
   if ((rc = zk_autocorr_same_dev(d_img.p, dtype, W, d_org.as<int32_t>(), n_windows, ws, ws, standardize ? d_stats.as<double>() : nullptr,
                                  d_acc.as<double>(), 0)))
     return rc;
-  ZK_HIP(hipMemcpy(out_host, d_acc.p, (size_t)ws * ws * 8, hipMemcpyDeviceToHost));
-  return 0;
+  return d_acc.download(out_host, acc_bytes);
 }
 
 extern "C" int64_t zk_polar_radii(int64_t h, int64_t w) {
@@ -516,24 +513,22 @@ extern "C" int zk_polar_profile(int device, const double* data_host, int64_t bat
   if (method < 0 || method > 2) return zk_fail(ZK_E_BADARG, "Invalid method. Must be 'mean', 'max', or 'sum'.");
   ZK_ON_DEVICE(device);
   const int R = (int)zk_polar_radii(h, w);
-  dev_buf d_in, d_mm, d_out, d_c;
-  int rc;
-  if ((rc = d_in.alloc((size_t)batch * h * w * 8)) || (rc = d_mm.alloc((size_t)batch * 16)) ||
-      (rc = d_out.alloc((size_t)batch * R * 8)) || (rc = d_c.alloc((size_t)batch * 8)))
-    return rc;
-  std::vector<int32_t> centres((size_t)2 * batch);
+  const size_t in_bytes = (size_t)batch * h * w * 8, out_bytes = (size_t)batch * R * 8;
+  std::vector<int32_t> centres((size_t)2 * batch);   // not an operand of the caller's: the one centre, once per image
   for (int64_t b = 0; b < batch; ++b) {
     centres[2 * b] = (int32_t)center_row;
     centres[2 * b + 1] = (int32_t)center_col;
   }
-  ZK_HIP(hipMemcpy(d_in.p, data_host, (size_t)batch * h * w * 8, hipMemcpyHostToDevice));
-  ZK_HIP(hipMemcpy(d_c.p, centres.data(), (size_t)batch * 8, hipMemcpyHostToDevice));
+  dev_buf d_in, d_mm, d_out, d_c;
+  int rc;
+  if ((rc = d_in.upload(data_host, in_bytes)) || (rc = d_c.upload(centres.data(), (size_t)batch * 8)) ||
+      (rc = d_mm.alloc((size_t)batch * 16)) || (rc = d_out.alloc(out_bytes)))
+    return rc;
   hipLaunchKernelGGL(minmax_kernel, dim3((unsigned)batch), dim3(256), 0, 0, d_in.as<double>(), (long long)h * w, d_mm.as<double>());
   if ((rc = zk_polar_profile_dev(d_in.as<double>(), (int)batch, (int)h, (int)w, d_c.as<int32_t>(), 0, method, d_mm.as<double>(),
                                  d_out.as<double>())))
     return rc;
-  ZK_HIP(hipMemcpy(out_host, d_out.p, (size_t)batch * R * 8, hipMemcpyDeviceToHost));
-  return 0;
+  return d_out.download(out_host, out_bytes);
 }
 
 extern "C" int zk_power_spectra(int device, const void* image_host, int dtype, int64_t H, int64_t W, int64_t size,
@@ -548,16 +543,14 @@ extern "C" int zk_power_spectra(int device, const void* image_host, int dtype, i
   if ((rc = zk_fft_load())) return rc;
   ZK_ON_DEVICE(device);
   const int n = (int)size;
-  const size_t es = zk_elem_size(dtype);
   const long long total = (long long)n_windows * n * n;
+  const size_t img_bytes = (size_t)H * W * zk_elem_size(dtype), org_bytes = (size_t)n_windows * 8, win_bytes = (size_t)n * 8,
+               out_bytes = (size_t)total * 8;
   dev_buf d_img, d_org, d_win, d_z, d_out;
-  if ((rc = d_img.alloc((size_t)H * W * es)) || (rc = d_org.alloc((size_t)n_windows * 8)) || (rc = d_win.alloc((size_t)n * 8)) ||
-      (rc = d_z.alloc((size_t)total * 16)) || (rc = d_out.alloc((size_t)total * 8)))
+  if ((rc = d_img.upload(image_host, img_bytes)) || (rc = d_org.upload(origins_yx, org_bytes)) || (rc = d_win.upload(window_1d, win_bytes)) ||
+      (rc = d_z.alloc((size_t)total * 16)) || (rc = d_out.alloc(out_bytes)))
     return rc;
-  ZK_HIP(hipMemcpy(d_img.p, image_host, (size_t)H * W * es, hipMemcpyHostToDevice));
-  ZK_HIP(hipMemcpy(d_org.p, origins_yx, (size_t)n_windows * 8, hipMemcpyHostToDevice));
-  if (window_1d) ZK_HIP(hipMemcpy(d_win.p, window_1d, (size_t)n * 8, hipMemcpyHostToDevice));
-  const double* win = window_1d ? d_win.as<double>() : nullptr;
+  const double* win = d_win.as<double>();            // null without a window
   if (dtype == ZK_F32)
     hipLaunchKernelGGL(fill_kernel<float>, dim3(blocks_of(total)), dim3(256), 0, 0, d_img.as<float>(), (int)W, d_org.as<int32_t>(), n,
                        n, (const double*)nullptr, win, n, n, d_z.as<cplx>(), total);
@@ -570,8 +563,7 @@ extern "C" int zk_power_spectra(int device, const void* image_host, int dtype, i
   ZK_FFT(zk_fft.ExecZ2Z(plan.h, d_z.as<cplx>(), d_z.as<cplx>(), HIPFFT_FORWARD));
   hipLaunchKernelGGL(shift_power_kernel, dim3(blocks_of(total)), dim3(256), 0, 0, d_z.as<cplx>(), n, d_out.as<double>(), total);
   ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpy(out_host, d_out.p, (size_t)total * 8, hipMemcpyDeviceToHost));
-  return 0;
+  return d_out.download(out_host, out_bytes);
 }
 
 extern "C" int zk_denoise_fft(int device, const void* image_host, int dtype, int64_t H, int64_t W, double p, double* out_host) {
@@ -583,12 +575,11 @@ extern "C" int zk_denoise_fft(int device, const void* image_host, int dtype, int
   if ((rc = zk_fft_load())) return rc;
   ZK_ON_DEVICE(device);
   const long long n = (long long)H * W;
-  const size_t es = zk_elem_size(dtype);
+  const size_t img_bytes = (size_t)n * zk_elem_size(dtype), spec_bytes = (size_t)n * 16, out_bytes = (size_t)n * 8;
   dev_buf d_img, d_spec, d_pow, d_hist, d_out;
-  if ((rc = d_img.alloc((size_t)n * es)) || (rc = d_spec.alloc((size_t)n * 16)) || (rc = d_pow.alloc((size_t)n * 16)) ||
-      (rc = d_hist.alloc(65537 * 4)) || (rc = d_out.alloc((size_t)n * 8)))
+  if ((rc = d_img.upload(image_host, img_bytes)) || (rc = d_spec.alloc(spec_bytes)) || (rc = d_pow.alloc(spec_bytes)) ||
+      (rc = d_hist.alloc(65537 * 4)) || (rc = d_out.alloc(out_bytes)))
     return rc;
-  ZK_HIP(hipMemcpy(d_img.p, image_host, (size_t)n * es, hipMemcpyHostToDevice));
   if (dtype == ZK_F32)
     hipLaunchKernelGGL(to_complex_kernel<float>, dim3(blocks_of(n)), dim3(256), 0, 0, d_img.as<float>(), d_spec.as<cplx>(), n);
   else
@@ -597,7 +588,7 @@ extern "C" int zk_denoise_fft(int device, const void* image_host, int dtype, int
   zk_fft_plan plan;
   if ((rc = plan.make((int)H, (int)W, 1))) return rc;
   ZK_FFT(zk_fft.ExecZ2Z(plan.h, d_spec.as<cplx>(), d_spec.as<cplx>(), HIPFFT_FORWARD));
-  ZK_HIP(hipMemcpy(d_pow.p, d_spec.p, (size_t)n * 16, hipMemcpyDeviceToDevice));
+  ZK_HIP(hipMemcpy(d_pow.p, d_spec.p, spec_bytes, hipMemcpyDeviceToDevice));
   hipLaunchKernelGGL(power_kernel, dim3(blocks_of(n)), dim3(256), 0, 0, d_pow.as<cplx>(), n);
   // k = ceil(p n) coefficients survive (reference _denoise_fft.py:33-38): find the k-th largest power exactly
   long long k = (long long)ceil(p * (double)n);
@@ -613,8 +604,7 @@ extern "C" int zk_denoise_fft(int device, const void* image_host, int dtype, int
   ZK_FFT(zk_fft.ExecZ2Z(plan.h, d_spec.as<cplx>(), d_spec.as<cplx>(), HIPFFT_BACKWARD));
   hipLaunchKernelGGL(real_scale_kernel, dim3(blocks_of(n)), dim3(256), 0, 0, d_spec.as<cplx>(), 1.0 / (double)n, d_out.as<double>(), n);
   ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpy(out_host, d_out.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-  return 0;
+  return d_out.download(out_host, out_bytes);
 }
 
 // skimage.restoration.estimate_sigma for a 2-D image (restated, see mtflearn_amd/features/pickers.py): the median of the
@@ -628,10 +618,10 @@ extern "C" int zk_wavelet_sigma(int device, const void* image_host, int dtype, i
   ZK_ON_DEVICE(device);
   const int oh = (int)((H + 3) / 2), ow = (int)((W + 3) / 2);
   const long long n = (long long)oh * ow;
-  const size_t es = zk_elem_size(dtype);
   dev_buf d_img, d_d, d_hist;
-  if ((rc = d_img.alloc((size_t)H * W * es)) || (rc = d_d.alloc((size_t)n * 8)) || (rc = d_hist.alloc(65536 * 4 + 8))) return rc;
-  ZK_HIP(hipMemcpy(d_img.p, image_host, (size_t)H * W * es, hipMemcpyHostToDevice));
+  if ((rc = d_img.upload(image_host, (size_t)H * W * zk_elem_size(dtype))) || (rc = d_d.alloc((size_t)n * 8)) ||
+      (rc = d_hist.alloc(65536 * 4 + 8)))
+    return rc;
   if (dtype == ZK_F32)
     hipLaunchKernelGGL(db2_dd_kernel<float>, dim3(blocks_of(n)), dim3(256), 0, 0, d_img.as<float>(), (int)H, (int)W, oh, ow, d_d.as<double>());
   else

@@ -12,8 +12,9 @@
 //   flag         ERR_WINDOW, the bit a kernel raises for a window that leaves the frame, and window_fail, the refusal it becomes.
 //   host checks  check_frame (float frame, 0 < H, W < 2^31, n < 2^24), check_pointers and corners_inside, the host's form of the
 //                inside test, which the host-array entry points apply before anything is launched.
-//   staging      host_stage: the device copies of a host-array entry point -- frame, int32 rows, results -- allocated and copied
-//                with plain hipMalloc / hipMemcpy in that order (pageable memory, no ring: these calls are not the hot path).
+//   staging      none of its own: a host-array entry point takes its frame and int32 rows up with dev_buf::upload, allocates
+//                its results and brings them down with dev_buf::download (zk_scratch.h: pageable memory, no ring -- these calls
+//                are not the hot path).  A null result pointer is an output the caller does not want.
 //
 // This header is compiled under each includer's flags: zk_refine.o and zk_com_refine.o are built with -ffp-contract=off,
 // zk_gauss_fit.o is not.  The device code here is rint, fabs, compares, conversions and integer arithmetic only: nothing of the
@@ -22,8 +23,6 @@
 #pragma once
 
 #include <math.h>
-
-#include <initializer_list>
 
 #include "zk_internal.h"
 #include "zk_scratch.h"
@@ -89,27 +88,5 @@ inline int check_frame(const char* who, const void* img, int dtype, int64_t H, i
 inline int check_pointers(const char* who, int64_t n, bool all_given) {
   return n && !all_given ? zk_fail(ZK_E_BADARG, std::string(who) + ": null pointer") : 0;
 }
-
-struct host_stage {
-  dev_buf img, rows, out[3];
-  size_t bytes[3] = {0, 0, 0};
-  // out_bytes: the size of every result array, three at most
-  int up(const void* image, int dtype, int64_t H, int64_t W, const int32_t* rows_host, int64_t n, std::initializer_list<size_t> out_bytes) {
-    const size_t px = zk_elem_size(dtype) * (size_t)H * (size_t)W, rb = sizeof(int32_t) * 2 * (size_t)n;
-    int rc, k = 0;
-    if ((rc = img.alloc(px)) || (rc = rows.alloc(rb))) return rc;
-    for (size_t b : out_bytes) {
-      if ((rc = out[k].alloc(b))) return rc;
-      bytes[k++] = b;
-    }
-    ZK_HIP(hipMemcpy(img.p, image, px, hipMemcpyHostToDevice));
-    ZK_HIP(hipMemcpy(rows.p, rows_host, rb, hipMemcpyHostToDevice));
-    return 0;
-  }
-  int fetch(int k, void* host) const {                 // a null `host` is an output the caller does not want
-    if (host) ZK_HIP(hipMemcpy(host, out[k].p, bytes[k], hipMemcpyDeviceToHost));
-    return 0;
-  }
-};
 
 }  // namespace

@@ -126,9 +126,11 @@ extern "C" int zk_refine_points(int device, const void* image_host, int image_dt
   }
   if (n_points == 0) return 0;
   ZK_ON_DEVICE(device);
-  host_stage st;
-  if ((rc = st.up(image_host, image_dtype, H, W, points_host, n_points, {sizeof(double) * 2 * (size_t)n_points})) ||
-      (rc = refine_call(st.img.p, image_dtype, H, W, st.rows.as<int>(), n_points, (int)size, mode, st.out[0].as<double>(), (hipStream_t)0)))
+  const size_t img_bytes = zk_elem_size(image_dtype) * (size_t)H * (size_t)W, pts_bytes = sizeof(int32_t) * 2 * (size_t)n_points,
+               out_bytes = sizeof(double) * 2 * (size_t)n_points;
+  dev_buf d_img, d_pts, d_out;
+  if ((rc = d_img.upload(image_host, img_bytes)) || (rc = d_pts.upload(points_host, pts_bytes)) || (rc = d_out.alloc(out_bytes)) ||
+      (rc = refine_call(d_img.p, image_dtype, H, W, d_pts.as<int>(), n_points, (int)size, mode, d_out.as<double>(), (hipStream_t)0)))
     return rc;
-  return st.fetch(0, out_host);
+  return d_out.download(out_host, out_bytes);
 }

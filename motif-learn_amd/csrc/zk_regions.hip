@@ -512,12 +512,9 @@ extern "C" int zk_find_regions(int device, const double* points_host, int64_t n_
         return zk_fail(ZK_E_BADARG, "find_regions: an edge is out of [0, n_points) or joins a node to itself");
     }
   ZK_ON_DEVICE(*state ? ((regions_state*)*state)->device : device);
-  dev_buf d_pts, d_ijs;
-  if (!*state && n_points) {
-    if ((rc = d_pts.alloc(sizeof(double) * 2 * (size_t)n_points)) || (rc = d_ijs.alloc(sizeof(int64_t) * 2 * (size_t)n_edges))) return rc;
-    ZK_HIP(hipMemcpy(d_pts.p, points_host, sizeof(double) * 2 * (size_t)n_points, hipMemcpyHostToDevice));
-    if (n_edges) ZK_HIP(hipMemcpy(d_ijs.p, edges_host, sizeof(int64_t) * 2 * (size_t)n_edges, hipMemcpyHostToDevice));
-  }
+  const size_t pts_bytes = sizeof(double) * 2 * (size_t)n_points, ijs_bytes = sizeof(int64_t) * 2 * (size_t)n_edges;
+  dev_buf d_pts, d_ijs;                              // the second call of a pair (*state set) reads neither
+  if (!*state && n_points && ((rc = d_pts.upload(points_host, pts_bytes)) || (rc = d_ijs.upload(edges_host, ijs_bytes)))) return rc;
   return regions_call(device, d_pts.as<double>(), n_points, d_ijs.as<int64_t>(), n_edges, state, counts_host, offsets_host, vertices_host,
                       ks_host, centers_host, adjacency_host, hipMemcpyDeviceToHost, (hipStream_t)0);
 }

@@ -612,13 +612,11 @@ extern "C" int zk_register_shifts(int device, const void* stack_host, int dtype,
   zk_ring* r = &h->ring;
   const size_t per = j.per(), up_per = j.up_per(), in_unit = per * zk_elem_size(dtype);
   const bool by_index = ref_mode == ZK_REGISTER_REF_INDEX;
-  dev_buf d_ref, d_res;
-  if ((rc = d_res.alloc((size_t)B * 24))) return rc;
-  if (ref_mode != ZK_REGISTER_REF_PREVIOUS) {
-    const size_t bytes = per * zk_elem_size(by_index ? dtype : ref_dtype);
-    if ((rc = d_ref.alloc(bytes))) return rc;
-    ZK_HIP(hipMemcpy(d_ref.p, by_index ? (const char*)stack_host + (size_t)ref_index * in_unit : ref_host, bytes, hipMemcpyHostToDevice));
-  }
+  const size_t shift_bytes = (size_t)B * 16, peak_bytes = (size_t)B * 8, ref_bytes = per * zk_elem_size(by_index ? dtype : ref_dtype);
+  // the reference frame: one of the stack's, the caller's, or none (every frame against the one before it)
+  const void* ref_src = ref_mode == ZK_REGISTER_REF_PREVIOUS ? nullptr : by_index ? (const char*)stack_host + (size_t)ref_index * in_unit : ref_host;
+  dev_buf d_ref, d_res;                              // d_res: the shifts, then the peaks
+  if ((rc = d_res.alloc(shift_bytes + peak_bytes)) || (rc = d_ref.upload(ref_src, ref_bytes))) return rc;
   state st;
   rc = prepare(st, j, d_ref.p, by_index ? dtype : ref_dtype, h->stream);
   if (!rc) {
@@ -649,8 +647,8 @@ extern "C" int zk_register_shifts(int device, const void* stack_host, int dtype,
   }
   if (zk_ring_bytes(r) > RING_KEEP) zk_ring_free_slots(r);
   if (rc) return rc;  // zk_ring_run has drained every stream: the fields may go
-  ZK_HIP(hipMemcpy(shifts_host, d_res.p, (size_t)B * 16, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(peak_host, d_res.as<double>() + 2 * B, (size_t)B * 8, hipMemcpyDeviceToHost));
+  if ((rc = d_res.download(shifts_host, shift_bytes))) return rc;
+  ZK_HIP(hipMemcpy(peak_host, d_res.as<double>() + 2 * B, peak_bytes, hipMemcpyDeviceToHost));
   return 0;
 }
 

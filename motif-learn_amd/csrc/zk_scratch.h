@@ -1,6 +1,7 @@
 // zk_scratch.h -- host-side scratch helpers of the translation units that own their device memory per call: a device buffer
-// freed with its scope, the error word of a call (dev_flag), the block count of a launch, and rocPRIM's temporary storage with the one way to call an algorithm
-// that needs it.
+// freed with its scope (dev_buf), which is also how a host-array entry point takes its operands up and its results down
+// (upload / download), the error word of a call (dev_flag), the block count of a launch, and rocPRIM's temporary storage
+// with the one way to call an algorithm that needs it.
 #pragma once
 
 #include <rocprim/device/device_scan.hpp>
@@ -16,6 +17,25 @@ struct dev_buf {
   int alloc(size_t bytes) {
     ZK_HIP(hipMalloc(&p, bytes ? bytes : 16));
     return 0;
+  }
+  // The copies of the host-array entry points: pageable memory, blocking, on the null stream (these calls are not the hot
+  // path).  A null `host` is an operand the caller did not pass -- p stays null, and as<T>() is the nullptr the device
+  // body expects for it -- or a result the caller does not want.
+  int upload(const void* host, size_t bytes) {
+    if (!host) return 0;
+    int rc;
+    if ((rc = alloc(bytes))) return rc;
+    ZK_HIP(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+    return 0;
+  }
+  int download(void* host, size_t bytes) const {
+    if (host) ZK_HIP(hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  void* release() {                                  // the pointer is the caller's from here on
+    void* q = p;
+    p = nullptr;
+    return q;
   }
   template <typename T>
   T* as() const {

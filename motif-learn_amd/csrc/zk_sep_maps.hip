@@ -504,13 +504,7 @@ int zk_maps_planes_g2(zk_plan* p, const void* in, int dtype, int64_t H, int64_t 
   const bool direct = p->path != ZK_PATH_SEPARABLE && zk_plan_auto_direct(p, 1, dtype) && zk_auto_direct_allowed();
   if (direct) band = zk_direct_band_rows(p, W, band, n_rows);
   const size_t need = (size_t)p->n_poly * band * W * sizeof(double);
-  if (p->d_scratch_bytes < need) {
-    if (p->d_scratch) ZK_HIP(hipFree(p->d_scratch));
-    p->d_scratch = nullptr;
-    p->d_scratch_bytes = 0;
-    ZK_HIP(hipMalloc((void**)&p->d_scratch, need));
-    p->d_scratch_bytes = need;
-  }
+  if (const int rc = zk_ensure((void**)&p->d_scratch, &p->d_scratch_bytes, need)) return rc;
   const long long plane = zk_out_plane(p, n_rows, W);
   for (int64_t b0 = 0; b0 < n_rows; b0 += band) {
     const int64_t nb = n_rows - b0 < band ? n_rows - b0 : band;
@@ -555,13 +549,7 @@ int zk_maps_planes_large(zk_plan* p, int knm, const void* in, int dtype, int64_t
   band = band < 8 ? 8 : (band > n_rows ? n_rows : band);
   band = zk_direct_band_rows(p, W, band, n_rows);
   const size_t need = (size_t)p->n_poly * band * W * sizeof(double);
-  if (p->d_scratch_bytes < need) {
-    if (p->d_scratch) ZK_HIP(hipFree(p->d_scratch));
-    p->d_scratch = nullptr;
-    p->d_scratch_bytes = 0;
-    ZK_HIP(hipMalloc((void**)&p->d_scratch, need));
-    p->d_scratch_bytes = need;
-  }
+  if (const int rc = zk_ensure((void**)&p->d_scratch, &p->d_scratch_bytes, need)) return rc;
   const long long plane = zk_out_plane(p, n_rows, W);
   for (int64_t b0 = 0; b0 < n_rows; b0 += band) {
     const int64_t nb = n_rows - b0 < band ? n_rows - b0 : band;

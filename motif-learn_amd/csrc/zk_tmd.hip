@@ -300,7 +300,6 @@ extern "C" int zk_tmd_render(int device, void* frames_host, void* masks_host, in
   if (blur && (rc = d_frames.alloc(frame_bytes))) return rc;
   if (masks_host && (rc = d_masks.alloc(mask_bytes))) return rc;
   if ((rc = run_job(d_frames.as<float>(), d_masks.as<float>(), j, (hipStream_t)0))) return rc;
-  if (blur) ZK_HIP(hipMemcpy(frames_host, d_frames.p, frame_bytes, hipMemcpyDeviceToHost));
-  if (masks_host && mask_bytes) ZK_HIP(hipMemcpy(masks_host, d_masks.p, mask_bytes, hipMemcpyDeviceToHost));
-  return 0;
+  if (blur && (rc = d_frames.download(frames_host, frame_bytes))) return rc;   // without weights no frame is rendered
+  return d_masks.download(masks_host, mask_bytes);
 }

@@ -496,14 +496,6 @@ int check_map(int op, const double* params, const void* out) {
   return 0;
 }
 
-int upload(dev_buf& d, const void* host, int dtype, int64_t n) {
-  const size_t bytes = (size_t)n * zk_elem_size(dtype);
-  int rc;
-  if ((rc = d.alloc(bytes))) return rc;
-  ZK_HIP(hipMemcpy(d.p, host, bytes, hipMemcpyHostToDevice));
-  return 0;
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------
@@ -521,7 +513,7 @@ extern "C" int zk_image_stats(int device, const void* image_host, int dtype, int
   if (rc || (rc = check_stats(mode, minmax_host, n_nonfinite_host, sums_host))) return rc;
   ZK_ON_DEVICE(device);
   dev_buf d_img;
-  if ((rc = upload(d_img, image_host, dtype, n))) return rc;
+  if ((rc = d_img.upload(image_host, (size_t)n * zk_elem_size(dtype)))) return rc;
   return stats_run(d_img.p, dtype, n, mode, center, minmax_host, n_nonfinite_host, sums_host, (hipStream_t)0);
 }
 
@@ -539,7 +531,7 @@ extern "C" int zk_image_order_stats(int device, const void* image_host, int dtyp
   if (rc || (rc = check_order(n, mode, ranks_host, n_ranks, values_host))) return rc;
   ZK_ON_DEVICE(device);
   dev_buf d_img;
-  if ((rc = upload(d_img, image_host, dtype, n))) return rc;
+  if ((rc = d_img.upload(image_host, (size_t)n * zk_elem_size(dtype)))) return rc;
   return order_stats_run(d_img.p, dtype, n, mode, center, ranks_host, n_ranks, values_host, (hipStream_t)0);
 }
 
@@ -558,8 +550,7 @@ extern "C" int zk_image_map(int device, const void* image_host, int dtype, int64
   ZK_ON_DEVICE(device);
   const size_t out_bytes = (size_t)n * map_out_size(dtype, op);
   dev_buf d_img, d_out;
-  if ((rc = upload(d_img, image_host, dtype, n)) || (rc = d_out.alloc(out_bytes))) return rc;
+  if ((rc = d_img.upload(image_host, (size_t)n * zk_elem_size(dtype))) || (rc = d_out.alloc(out_bytes))) return rc;
   if ((rc = map_run(d_img.p, dtype, n, op, params_host, keep_nonfinite, d_out.p, (hipStream_t)0))) return rc;
-  ZK_HIP(hipMemcpy(out_host, d_out.p, out_bytes, hipMemcpyDeviceToHost));
-  return 0;
+  return d_out.download(out_host, out_bytes);
 }

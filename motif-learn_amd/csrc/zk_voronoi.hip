@@ -584,12 +584,9 @@ extern "C" int zk_voronoi_cells(int device, const void* points_host, int points_
     for (int64_t k = 0; k < 2 * n_points; ++k)
       if (!(fabs(((const double*)points_host)[k]) <= 1.7976931348623157e308)) return zk_fail(ZK_E_BADARG, "voronoi_cells: a point is not finite");
   ZK_ON_DEVICE(*state ? ((voronoi_state*)*state)->device : device);
+  const size_t pts_bytes = (points_dtype == ZK_I32 ? sizeof(int32_t) : sizeof(double)) * 2 * (size_t)n_points;
   dev_buf d_pts;
-  if (!*state && n_points) {
-    const size_t bytes = (points_dtype == ZK_I32 ? sizeof(int32_t) : sizeof(double)) * 2 * (size_t)n_points;
-    if ((rc = d_pts.alloc(bytes))) return rc;
-    ZK_HIP(hipMemcpy(d_pts.p, points_host, bytes, hipMemcpyHostToDevice));
-  }
+  if (!*state && n_points && (rc = d_pts.upload(points_host, pts_bytes))) return rc;
   return voronoi_call(device, d_pts.p, points_dtype, n_points, pad, mode, dmax, threshold, state, counts_host, ijs_host, ridge_host, edge_host,
                       hipMemcpyDeviceToHost, (hipStream_t)0);
 }

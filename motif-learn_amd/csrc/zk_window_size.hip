@@ -349,10 +349,7 @@ inline int parts_per_frame(int64_t H, int64_t W) { return (int)((H * W + RED_PER
 int frame_origins(dev_buf& d_org, int64_t B, int64_t H) {
   std::vector<int32_t> org((size_t)2 * B, 0);
   for (int64_t b = 0; b < B; ++b) org[(size_t)2 * b] = (int32_t)(b * H);
-  int rc = d_org.alloc((size_t)B * 8);
-  if (rc) return rc;
-  ZK_HIP(hipMemcpy(d_org.p, org.data(), (size_t)B * 8, hipMemcpyHostToDevice));
-  return 0;
+  return d_org.upload(org.data(), (size_t)B * 8);
 }
 
 // mean / std of every frame on the device; a constant frame is the reference's ValueError
@@ -443,17 +440,9 @@ int tail_lds(K kernel, size_t bytes) {
   return 0;
 }
 
-int upload(dev_buf& d_img, const void* host, size_t bytes) {
-  int rc = d_img.alloc(bytes);
-  if (rc) return rc;
-  ZK_HIP(hipMemcpy(d_img.p, host, bytes, hipMemcpyHostToDevice));
-  return 0;
-}
-
 int download_profiles(const profile_stage& ps, int64_t B, int32_t* centres_host, double* profiles_host) {
   if (centres_host) std::copy(ps.centres_host.begin(), ps.centres_host.end(), centres_host);
-  if (profiles_host) ZK_HIP(hipMemcpy(profiles_host, ps.prof.p, (size_t)B * ps.R * 8, hipMemcpyDeviceToHost));
-  return 0;
+  return ps.prof.download(profiles_host, (size_t)B * ps.R * 8);
 }
 
 int shifted_map(const char* who, int device, const void* images_host, int dtype, int64_t B, int64_t H, int64_t W, int autocorr,
@@ -463,19 +452,17 @@ int shifted_map(const char* who, int device, const void* images_host, int dtype,
   if (!out_host) return zk_fail(ZK_E_BADARG, std::string(who) + ": null pointer");
   if ((rc = zk_fft_load())) return rc;
   ZK_ON_DEVICE(device);
-  const size_t n = (size_t)B * H * W;
+  const size_t n = (size_t)B * H * W, map_bytes = n * 8;
   dev_buf d_img, d_org, d_stats, d_map, d_parts;
-  if ((rc = upload(d_img, images_host, n * zk_elem_size(dtype))) || (rc = d_map.alloc(n * 8)) ||
+  if ((rc = d_img.upload(images_host, n * zk_elem_size(dtype))) || (rc = d_map.alloc(map_bytes)) ||
       (rc = d_parts.alloc((size_t)B * parts_per_frame(H, W) * sizeof(partial))))
     return rc;
   if (standardize && ((rc = frame_origins(d_org, B, H)) || (rc = d_stats.alloc((size_t)B * 16)) ||
                       (rc = frame_stats(d_img.p, dtype, B, H, W, d_org.as<int32_t>(), d_stats.as<double>()))))
     return rc;
-  if ((rc = magnitude_maps(d_img.p, dtype, standardize ? d_stats.as<double>() : nullptr, B, H, W, autocorr, use_log, d_map.as<double>(),
-                           d_parts.as<partial>())))
+  if ((rc = magnitude_maps(d_img.p, dtype, d_stats.as<double>(), B, H, W, autocorr, use_log, d_map.as<double>(), d_parts.as<partial>())))
     return rc;
-  ZK_HIP(hipMemcpy(out_host, d_map.p, n * 8, hipMemcpyDeviceToHost));
-  return 0;
+  return d_map.download(out_host, map_bytes);
 }
 
 }  // namespace
@@ -499,25 +486,25 @@ extern "C" int zk_char_length_fft(int device, const void* images_host, int dtype
   if (niter < 0 || size < 1 || size > (1 << 20)) return zk_fail(ZK_E_BADARG, "char_length_fft: niter must be >= 0 and size in 1 .. 2^20");
   if ((rc = zk_fft_load())) return rc;
   ZK_ON_DEVICE(device);
-  const size_t n = (size_t)B * H * W;
+  const size_t n = (size_t)B * H * W, ind_bytes = (size_t)B * 4;
   dev_buf d_img, d_map, d_parts, d_y2, d_ind;
   profile_stage ps;
-  if ((rc = upload(d_img, images_host, n * zk_elem_size(dtype))) || (rc = d_map.alloc(n * 8)) ||
-      (rc = d_parts.alloc((size_t)B * parts_per_frame(H, W) * sizeof(partial))) || (rc = d_ind.alloc((size_t)B * 4)) ||
+  if ((rc = d_img.upload(images_host, n * zk_elem_size(dtype))) || (rc = d_map.alloc(n * 8)) ||
+      (rc = d_parts.alloc((size_t)B * parts_per_frame(H, W) * sizeof(partial))) || (rc = d_ind.alloc(ind_bytes)) ||
       (rc = magnitude_maps(d_img.p, dtype, nullptr, B, H, W, 0, use_log, d_map.as<double>(), d_parts.as<partial>())) ||
       (rc = cut_profiles(ps, d_map.as<double>(), d_parts.as<partial>(), B, H, W)))
     return rc;
-  if (smoothed_host) {
-    if ((rc = d_y2.alloc((size_t)B * ps.R * 8))) return rc;
-    ZK_HIP(hipMemset(d_y2.p, 0, (size_t)B * ps.R * 8));
+  const size_t y2_bytes = (size_t)B * ps.R * 8;
+  if (smoothed_host) {                               // without it d_y2 stays null, which the kernel takes as "not wanted"
+    if ((rc = d_y2.alloc(y2_bytes))) return rc;
+    ZK_HIP(hipMemset(d_y2.p, 0, y2_bytes));
   }
   const size_t lds = (size_t)2 * std::max(ps.n_max, 1) * 8;
   if ((rc = tail_lds(fft_tail_kernel, lds))) return rc;
   hipLaunchKernelGGL(fft_tail_kernel, dim3((unsigned)B), dim3(256), lds, 0, ps.prof.as<double>(), ps.R, ps.centres.as<int32_t>(), niter, size,
-                     smoothed_host ? d_y2.as<double>() : nullptr, d_ind.as<int32_t>());
+                     d_y2.as<double>(), d_ind.as<int32_t>());
   ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpy(ind_host, d_ind.p, (size_t)B * 4, hipMemcpyDeviceToHost));
-  if (smoothed_host) ZK_HIP(hipMemcpy(smoothed_host, d_y2.p, (size_t)B * ps.R * 8, hipMemcpyDeviceToHost));
+  if ((rc = d_ind.download(ind_host, ind_bytes)) || (rc = d_y2.download(smoothed_host, y2_bytes))) return rc;
   return download_profiles(ps, B, centres_host, profiles_host);
 }
 
@@ -528,19 +515,18 @@ extern "C" int zk_char_length(int device, const void* images_host, int dtype, in
   if (!peaks_host) return zk_fail(ZK_E_BADARG, "char_length: null pointer");
   if ((rc = zk_fft_load())) return rc;
   ZK_ON_DEVICE(device);
-  const size_t n = (size_t)B * H * W;
+  const size_t n = (size_t)B * H * W, peak_bytes = (size_t)B * 4;
   const int n_parts = parts_per_frame(H, W);
   dev_buf d_img, d_org, d_stats, d_map, d_parts, d_peak;
   profile_stage ps;
-  if ((rc = upload(d_img, images_host, n * zk_elem_size(dtype))) || (rc = d_map.alloc(n * 8)) ||
-      (rc = d_parts.alloc((size_t)B * n_parts * sizeof(partial))) || (rc = d_peak.alloc((size_t)B * 4)) || (rc = frame_origins(d_org, B, H)))
+  if ((rc = d_img.upload(images_host, n * zk_elem_size(dtype))) || (rc = d_map.alloc(n * 8)) ||
+      (rc = d_parts.alloc((size_t)B * n_parts * sizeof(partial))) || (rc = d_peak.alloc(peak_bytes)) || (rc = frame_origins(d_org, B, H)))
     return rc;
   if (standardize && ((rc = d_stats.alloc((size_t)B * 16)) ||
                       (rc = frame_stats(d_img.p, dtype, B, H, W, d_org.as<int32_t>(), d_stats.as<double>()))))
     return rc;
   // scipy.signal.correlate(image, image, 'same', 'fft') of every frame: the windows of zk_autocorr_mean, one map each
-  if ((rc = zk_autocorr_same_dev(d_img.p, dtype, W, d_org.as<int32_t>(), (int)B, (int)H, (int)W, standardize ? d_stats.as<double>() : nullptr,
-                                 d_map.as<double>(), 1)))
+  if ((rc = zk_autocorr_same_dev(d_img.p, dtype, W, d_org.as<int32_t>(), (int)B, (int)H, (int)W, d_stats.as<double>(), d_map.as<double>(), 1)))
     return rc;
   hipLaunchKernelGGL(magnitude_reduce_kernel, dim3(n_parts, (unsigned)B), dim3(256), 0, 0, (const cplx*)nullptr, (int)H, (int)W, 1.0, 0,
                      d_map.as<double>(), d_parts.as<partial>());
@@ -551,7 +537,7 @@ extern "C" int zk_char_length(int device, const void* images_host, int dtype, in
   hipLaunchKernelGGL(peak_tail_kernel, dim3((unsigned)B), dim3(256), lds, 0, ps.prof.as<double>(), ps.R, ps.centres.as<int32_t>(),
                      d_peak.as<int32_t>());
   ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpy(peaks_host, d_peak.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+  if ((rc = d_peak.download(peaks_host, peak_bytes))) return rc;
   return download_profiles(ps, B, centres_host, profiles_host);
 }
 
@@ -564,13 +550,13 @@ extern "C" int zk_angular_average(int device, const double* spectra_host, int64_
   for (int64_t i = 0; i < num_bins; ++i)
     if (!(edges_host[i] < edges_host[i + 1])) return zk_fail(ZK_E_BADARG, "angular_average: the bin edges must increase");
   ZK_ON_DEVICE(device);
-  const size_t n = (size_t)B * H * W, nb = (size_t)num_bins;
+  const size_t n = (size_t)B * H * W, nb = (size_t)num_bins, bins_bytes = B * nb * 8;  // sums and counts alike
   dev_buf d_in, d_edges, d_sum, d_cnt;
-  if ((rc = upload(d_in, spectra_host, n * 8)) || (rc = upload(d_edges, edges_host, (nb + 1) * 8)) || (rc = d_sum.alloc(B * nb * 8)) ||
-      (rc = d_cnt.alloc(B * nb * 8)))
+  if ((rc = d_in.upload(spectra_host, n * 8)) || (rc = d_edges.upload(edges_host, (nb + 1) * 8)) || (rc = d_sum.alloc(bins_bytes)) ||
+      (rc = d_cnt.alloc(bins_bytes)))
     return rc;
-  ZK_HIP(hipMemset(d_sum.p, 0, B * nb * 8));
-  ZK_HIP(hipMemset(d_cnt.p, 0, B * nb * 8));
+  ZK_HIP(hipMemset(d_sum.p, 0, bins_bytes));
+  ZK_HIP(hipMemset(d_cnt.p, 0, bins_bytes));
   const dim3 grid(blocks_of((long long)H * W, 256 * ANG_RUN), (unsigned)B);
   if (num_bins <= ANG_LDS_BINS)
     hipLaunchKernelGGL(angular_kernel<true>, grid, dim3(256), 0, 0, d_in.as<double>(), (int)H, (int)W, d_edges.as<double>(), (int)num_bins,
@@ -579,7 +565,6 @@ extern "C" int zk_angular_average(int device, const double* spectra_host, int64_
     hipLaunchKernelGGL(angular_kernel<false>, grid, dim3(256), 0, 0, d_in.as<double>(), (int)H, (int)W, d_edges.as<double>(), (int)num_bins,
                        use_mask, d_sum.as<double>(), d_cnt.as<unsigned long long>());
   ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpy(sums_host, d_sum.p, B * nb * 8, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(counts_host, d_cnt.p, B * nb * 8, hipMemcpyDeviceToHost));
-  return 0;
+  if ((rc = d_sum.download(sums_host, bins_bytes))) return rc;
+  return d_cnt.download(counts_host, bins_bytes);
 }
