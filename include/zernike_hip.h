@@ -1252,6 +1252,47 @@ int zk_register_shifts_dev(int device, const void* stack_dev, int dtype, int64_t
 int zk_stack_mean(int device, const void* stack_host, int dtype, int64_t B, int64_t H, int64_t W, double* out_host);
 int zk_stack_mean_dev(int device, const void* stack_dev, int dtype, int64_t B, int64_t H, int64_t W, double* out_dev, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Geometric phase analysis (no reference counterpart): the strain and rotation maps of every frame of a (B, H, W) stack from
+ * the phases of two Bragg spots (Hytch, Snoeck, Kilaas, Ultramicroscopy 74, 131 (1998)).
+ *
+ * g (2, 2) on the host: the rows g_k = (gy, gx) are the two Bragg vectors in cycles per pixel; sigma the mask width in cycles
+ * per pixel.  Everything is float64; the integer formats are widened exactly.  Axis index a and j: 0 = y, 1 = x.
+ *   spectrum     F = fft2(frame * w), w all 1 (ZK_GPA_WINDOW_NONE) or the separable periodic Hann window of the registration
+ *                (ZK_GPA_WINDOW_HANN).
+ *   planes       M_k[ky, kx] = exp(-(dy^2 + dx^2) / (2 sigma^2)), dy = fftfreq(H)[ky] - gy wrapped to the nearest representative
+ *                (dy -= rint(dy)), dx likewise; H_k = ifft2(F M_k) with its 1 / (H W); amplitude_k = |H_k|.
+ *   gradient     dP_k/dx = arg(H_k[y, x + 1] conj(H_k[y, x - 1]) c2x_k) / 2 inside, arg(H_k[y, 1] conj(H_k[y, 0]) c1x_k) in the
+ *                first and arg(H_k[y, W - 1] conj(H_k[y, W - 2]) c1x_k) in the last column, c1x_k = exp(-2 pi i gx_k) and c2x_k =
+ *                exp(-4 pi i gx_k) formed once on the host; y likewise with gy_k.  arg is atan2(imaginary, real): the wrapped
+ *                phase is never unwrapped and never demodulated by a position-dependent factor, so no rounding grows with y, x.
+ *   reference    (y0, y1, x0, x1), a half-open rectangle inside the frame, or NULL.  m[k][a] = the mean of dP_k/dr_a over the
+ *                rectangle (a float64 sum in a fixed tree, divided once; no atomics); dP_k/dr_a -= m[k][a];
+ *                G = g + m / (2 pi), the refined Bragg vectors.  NULL: m = 0, G = g.
+ *   strain       e[j][a] = du_j/dr_a = -(1 / 2 pi) sum_k inv(G)[j][k] dP_k/dr_a; exx = e[x][x], eyy = e[y][y],
+ *                exy = (e[x][y] + e[y][x]) / 2, rotation = (e[y][x] - e[x][y]) / 2 in radians.  A frame I0(r - u(r)) gives
+ *                e = grad u to first order.
+ *   phase        arg(H_k exp(-2 pi i t)), t = gy y + gx x reduced by t -= floor(t): for display only.
+ * maps (4, B, H, W): exx, eyy, exy, rotation.  amp (B, 2, H, W).  g_out (B, 2, 2): G.  phase (B, 2, H, W) and planes
+ * (B, 2, H, W) complex float64 (H_k itself, for tests) when not NULL.  Frames go in runs whose three complex fields stay under
+ * 1 GiB (zk_gpa_set_run_bytes(device, bytes): another budget; 0: the default); no kernel looks across frames, and a frame
+ * alone, in a stack, in runs of any length, in the host and the _dev form and on a second run gives the same bits.
+ * 4 <= H, W <= 16384; |g components| <= 0.5; the rows of g non-zero and |det g| > 1e-6 |g_1| |g_2|; sigma finite and > 0.
+ * Not defined: non-finite samples (nothing scans for them).
+ *
+ * zk_gpa streams the frames through a staging ring; zk_gpa_dev takes device pointers, runs on hip_stream and synchronises it
+ * before it releases its fields.  g and reference are host pointers in both.  Everything is checked before any device call;
+ * a refused argument is ZK_E_BADARG with a message.
+ * ------------------------------------------------------------------------------------------------------ */
+#define ZK_GPA_WINDOW_NONE 0
+#define ZK_GPA_WINDOW_HANN 1
+int zk_gpa(int device, const void* stack_host, int dtype, int64_t B, int64_t H, int64_t W, const double* g, double sigma, int window,
+           const int64_t* reference, double* maps_host, double* amp_host, double* g_out_host, double* phase_host, void* planes_host);
+int zk_gpa_dev(int device, const void* stack_dev, int dtype, int64_t B, int64_t H, int64_t W, const double* g, double sigma, int window,
+               const int64_t* reference, double* maps_dev, double* amp_dev, double* g_out_dev, double* phase_dev, void* planes_dev,
+               void* hip_stream);
+int zk_gpa_set_run_bytes(int device, int64_t bytes);      /* the complex fields of one run of zk_gpa(_dev); 0: the default */
+
 /* Device memory for callers that have no allocator of their own (a NumPy / C user of the *_dev entry points). */
 int zk_device_malloc(int device, int64_t bytes, void** out_dev);
 int zk_device_free(int device, void* dev);

@@ -9,6 +9,7 @@
   refined chain:       the same key points -> sub-pixel centroids -> bond length -> Voronoi bonds -> polygons, all resident
   motifs:              k-means centres of the key-point moments -> ZPs.inverse_transform -> the motif each class stands for
   matching:            kmeans_aligned templates -> ZPs.align_maps -> cosine map from score, norm2, |t| -> local_max
+  strain:              a lattice displaced by a known field -> pick_g -> gpa against a reference rectangle -> strain maps
 
 Only the import line differs from the reference (`from mtflearn import ZPs`).  Needs an MI355X.
 Run:  python motif-learn_amd/examples/notebook_flows.py
@@ -193,6 +194,21 @@ def main():
     print(f"match  : align_maps of {cosine.shape} against {a_centres.shape[0]} templates -> cosine map -> local_max in"
           f" {1e3 * (time.perf_counter() - t):.1f} ms; {len(sites_found)} matches above 0.9, per class"
           f" {np.bincount(found_maps.best[sites_found[:, 1], sites_found[:, 0]], minlength=a_centres.shape[0]).tolist()}")
+
+    # ---- strain: how the lattice is deformed -- geometric phase analysis of a frame with a known displacement bump ---------------
+    from mtflearn_amd import strain
+    yy, xx = np.meshgrid(np.arange(512.0), np.arange(512.0), indexing="ij")
+    lattice_g = np.array([[0.0, 1 / 16], [1 / 16 * np.sqrt(3) / 2, -1 / 32]])   # a hexagonal pair, 16 px period
+    bump = 0.4 * np.exp(-((yy - 300) ** 2 + (xx - 330) ** 2) / (2 * 40.0 ** 2))  # u = (0, bump): atoms pushed along x
+    strained = sum(np.cos(2 * np.pi * (gy * yy + gx * (xx - bump))) for gy, gx in (*lattice_g, lattice_g[0] + lattice_g[1])).astype(np.float32)
+    t = time.perf_counter()
+    g = strain.pick_g(strained)                                            # the two strongest independent Bragg spots
+    res = strain.gpa(strained, g, reference=(32, 160, 32, 160), window="hann")
+    truth = np.gradient(bump, axis=1)                                      # exx = d u_x / dx
+    inner = (slice(64, 448), slice(64, 448))
+    print(f"strain : pick_g -> gpa of {strained.shape} in {1e3 * (time.perf_counter() - t):.1f} ms; g {np.round(res.g, 4).tolist()};"
+          f" exx in [{res.exx[inner].min():.4f}, {res.exx[inner].max():.4f}] against the field's [{truth.min():.4f}, {truth.max():.4f}],"
+          f" worst |exx - truth| inside {np.abs(res.exx - truth)[inner].max():.1e}, |rotation| <= {np.abs(res.rotation[inner]).max():.4f} rad")
 
 
 if __name__ == "__main__":

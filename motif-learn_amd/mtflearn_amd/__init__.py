@@ -14,7 +14,8 @@
 ``mtflearn_amd.graph``: ``find_regions`` / ``LatticeGraph`` / ``MotifsGraph``, the polygons of a lattice graph;
 ``mtflearn_amd.eels``: ``baseline_als`` / ``baseline_snip`` / ``baseline_arpls`` / ``baseline_airpls`` / ``WhittakerSmooth`` /
 ``remove_baseline`` over whole spectrum cubes; ``mtflearn_amd.registration``: ``estimate_shifts`` / ``shift_stack`` /
-``register_stack``, sub-pixel drift of a frame stack and its average, beyond the reference); see DESIGN.md.
+``register_stack``, sub-pixel drift of a frame stack and its average, and ``mtflearn_amd.strain``: ``gpa`` / ``pick_g``, strain and
+rotation maps by geometric phase analysis, both beyond the reference); see DESIGN.md.
 """
 __version__ = "0.1.0"
 

@@ -264,6 +264,11 @@ SYMBOLS = {
                                        c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "zk_stack_mean": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p]),
     "zk_stack_mean_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "zk_gpa": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                       c_void_p, c_void_p]),
+    "zk_gpa_dev": (c_int, [c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_double, c_int, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p, c_void_p]),
+    "zk_gpa_set_run_bytes": (c_int, [c_int, c_int64]),
     "zk_tmd_render": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_int]),
     "zk_tmd_render_dev": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
@@ -893,6 +898,12 @@ def align_set_band_bytes(band_bytes, device=None):
     one row)."""
     check(load().zk_align_set_band_bytes(default_device() if device is None else int(device), int(band_bytes)),
           "zk_align_set_band_bytes")
+
+
+def gpa_set_run_bytes(run_bytes, device=None):
+    """Bytes of complex fields per run of frames of ``zk_gpa`` / ``zk_gpa_dev`` (0: the default of 1 GiB; never less than one
+    frame)."""
+    check(load().zk_gpa_set_run_bytes(default_device() if device is None else int(device), int(run_bytes)), "zk_gpa_set_run_bytes")
 
 
 def _labels32(n, m):

@@ -841,6 +841,35 @@ def register_stack_device(stack, reference=0, upsample=100, max_shift=None, norm
     return Registered(stack_mean_device(aligned), shifts.shift, shifts.peak, aligned if return_aligned else None)
 
 
+def _gpa_resident(frames, code, shape, options, return_phase, planes=False):
+    """``zk_gpa_dev`` on checked operands: ``(maps (4, B, H, W), amp, G, phase or None)`` on the device (and ``H_k`` as
+    ``(B, 2, H, W, 2)`` float64 with ``planes``)."""
+    g, sigma, reference, window = options
+    b, h, w = shape
+    maps, amp, g_out = _empty_f64((4, b, h, w), frames), _empty_f64((b, 2, h, w), frames), _empty_f64((b, 2, 2), frames)
+    phase = _empty_f64((b, 2, h, w), frames) if return_phase else None
+    hk = _empty_f64((b, 2, h, w, 2), frames) if planes else None
+    ptr = lambda a: c_void_p(a.data_ptr()) if a is not None else None
+    host = lambda a: a.ctypes.data_as(c_void_p) if a is not None else None
+    _native.check(_native.load().zk_gpa_dev(frames.device.index, ptr(frames), code, b, h, w, host(g), sigma, window, host(reference), ptr(maps),
+                                            ptr(amp), ptr(g_out), ptr(phase), ptr(hk), c_void_p(stream_ptr(frames))), "zk_gpa_dev")
+    return (maps, amp, g_out, phase, hk) if planes else (maps, amp, g_out, phase)
+
+
+def gpa_device(image, g, sigma=None, reference=None, window=None, return_phase=False):
+    """:func:`mtflearn_amd.strain.gpa` of a frame or stack resident on the GPU (a torch tensor or a
+    :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` or ``(B, H, W)`` of float32 / float64 / uint8 / uint16 / int16; ``g``
+    and ``reference`` are host values).  Returns ``GPAResult`` of float64 device arrays of the image's kind, bit for bit the host
+    function's numbers, so ``register_stack_device -> gpa_device`` needs no host frame.  Runs on torch's current stream, which
+    is synchronised before the call returns (the complex fields are released then).  Like :func:`estimate_shifts_device` it is
+    reached as ``resident.gpa_device``."""
+    from .strain import _check_image_shape, _check_options, _result
+    shape, stack = _check_image_shape(image.shape)
+    options = _check_options(g, sigma, reference, window, shape[1:])
+    frames, code = _device.resident_frame(image, "gpa_device", ndim=None)
+    return _result(*_gpa_resident(frames, code, shape, options, bool(return_phase)), stack)
+
+
 def denoise_svd_device(image, patch_size, n_components, extraction_step=None, return_s=False):
     """:func:`mtflearn_amd.denoise_svd` of a frame resident on the GPU (a torch tensor or a
     :class:`~mtflearn_amd._native.DeviceArray`, ``(H, W)`` of float32 / float64 / uint8 / uint16 / int16).  Returns the float64
