@@ -462,8 +462,14 @@ int64_t zk_local_max_last_launches(void);
  *
  * residual (optional, NULL to skip): image - background in the background's type (NumPy's wrap-around for integers), then
  * max(., 0) when clip is non-zero.  Opening and rolling ball write background and residual in the image's dtype, baseline in
- * float64.  NaN or inf pixels are not pinned.  The _dev variants take device pointers and run on hip_stream (they
- * synchronise it once their scratch is released); nothing crosses to the host.
+ * float64.  The _dev variants take device pointers and run on hip_stream (they synchronise it once their scratch is
+ * released); nothing crosses to the host.  Any 0 < height * width < 2^31 is served, a single row or column included (the
+ * kernels stride over the y extent of their grids).
+ *
+ * NaN / inf pixels: the baseline is SciPy's arithmetic and np.minimum (a NaN on either side stays a NaN); the rolling ball
+ * skips a NaN sum, as scikit-image's `if min_value > tmp` does (a NaN or +inf pixel is passed over, a -inf pixel takes the
+ * outputs whose ball holds it, an output with NaN sums only is +inf); the opening is exact on +-inf and unspecified on NaN
+ * (as SciPy's own min / max queue is); the residual is NumPy's subtraction (inf - inf = NaN) and np.clip (NaN stays NaN).
  * ------------------------------------------------------------------------------------------------------ */
 int zk_background_opening(int device, const void* image_host, int dtype, int64_t height, int64_t width, int64_t size_y,
                           int64_t size_x, int clip, void* background_host, void* residual_host);

@@ -19,6 +19,10 @@
 //
 // Residual (all three, optional): image - background in the background's type, then max(., 0) when clip is set.
 // Edges: SciPy's 'reflect' (dcba|abcd), folded again and again when a window or radius exceeds the frame.
+// NaN / inf pixels: the baseline is np.minimum's (a NaN on either side stays a NaN) and the residual NumPy's subtraction and
+// np.clip; the rolling ball skips a NaN sum as scikit-image's `if min_value > tmp` does (no finite sum at all: +inf); the
+// opening is exact on +-inf and unspecified on NaN (as SciPy's own min / max queue is).
+// Long axes: every kernel that puts rows on grid.y strides over it (grid_y below), so a frame of one column is served.
 #pragma clang fp contract(off)
 
 #include <math.h>
@@ -54,6 +58,9 @@ __device__ __forceinline__ T pick(T a, T b) {
   else return b < a ? b : a;
 }
 
+// The y extent of a grid is 16 bits wide: more row blocks than that are strided over by the kernel (for (...; += gridDim.y ...)).
+inline unsigned grid_y(long long blocks) { return (unsigned)std::min<long long>(blocks, 65535); }
+
 // ---------------------------------------------------------------------------------------------------------------------
 // opening
 // ---------------------------------------------------------------------------------------------------------------------
@@ -65,22 +72,23 @@ __device__ __forceinline__ T pick(T a, T b) {
 template <typename T, bool MAX>
 __global__ __launch_bounds__(256) void vh_column_kernel(const T* __restrict__ in, T* __restrict__ out, int H, int W, int k, int a) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-  const long long seg = (long long)blockIdx.y * 4 + (threadIdx.x >> 6);
-  const long long s = seg * k;
-  if (x >= W || s >= H) return;
-  const long long B = s - a;
-  T run = in[(long long)reflect_index((int)(B + k - 1), H) * W + x];
-  if (k - 1 + s < H) out[(s + k - 1) * W + x] = run;
-  for (int j = k - 2; j >= 0; --j) {
-    run = pick<MAX>(run, in[(long long)reflect_index((int)(B + j), H) * W + x]);
-    if (s + j < H) out[(s + j) * W + x] = run;
-  }
-  T pre = run;  // overwritten at j = 1
-  for (int j = 1; j < k && s + j < H; ++j) {
-    const T v = in[(long long)reflect_index((int)(B + k - 1 + j), H) * W + x];
-    pre = j == 1 ? v : pick<MAX>(pre, v);
-    const long long o = (s + j) * W + x;
-    out[o] = pick<MAX>(out[o], pre);
+  if (x >= W) return;
+  for (long long seg = (long long)blockIdx.y * 4 + (threadIdx.x >> 6); seg * k < H; seg += (long long)gridDim.y * 4) {
+    const long long s = seg * k;
+    const long long B = s - a;
+    T run = in[(long long)reflect_index((int)(B + k - 1), H) * W + x];
+    if (k - 1 + s < H) out[(s + k - 1) * W + x] = run;
+    for (int j = k - 2; j >= 0; --j) {
+      run = pick<MAX>(run, in[(long long)reflect_index((int)(B + j), H) * W + x]);
+      if (s + j < H) out[(s + j) * W + x] = run;
+    }
+    T pre = run;  // overwritten at j = 1
+    for (int j = 1; j < k && s + j < H; ++j) {
+      const T v = in[(long long)reflect_index((int)(B + k - 1 + j), H) * W + x];
+      pre = j == 1 ? v : pick<MAX>(pre, v);
+      const long long o = (s + j) * W + x;
+      out[o] = pick<MAX>(out[o], pre);
+    }
   }
 }
 
@@ -88,30 +96,35 @@ __global__ __launch_bounds__(256) void vh_column_kernel(const T* __restrict__ in
 template <typename T>
 __global__ __launch_bounds__(256) void transpose_kernel(const T* __restrict__ in, T* __restrict__ out, int H, int W) {
   __shared__ T tile[64][65];
-  const int bx = blockIdx.x * 64, by = blockIdx.y * 64;
+  const int bx = blockIdx.x * 64;
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  for (int r = ty; r < 64; r += 4) {
-    const int y = by + r, x = bx + tx;
-    if (y < H && x < W) tile[r][tx] = in[(long long)y * W + x];
-  }
-  __syncthreads();
-  for (int r = ty; r < 64; r += 4) {
-    const int x = bx + r, y = by + tx;
-    if (x < W && y < H) out[(long long)x * H + y] = tile[tx][r];
+  for (long long by = (long long)blockIdx.y * 64; by < H; by += (long long)gridDim.y * 64) {
+    for (int r = ty; r < 64; r += 4) {
+      const long long y = by + r;
+      const int x = bx + tx;
+      if (y < H && x < W) tile[r][tx] = in[y * W + x];
+    }
+    __syncthreads();
+    for (int r = ty; r < 64; r += 4) {
+      const int x = bx + r;
+      const long long y = by + tx;
+      if (x < W && y < H) out[(long long)x * H + y] = tile[tx][r];
+    }
+    __syncthreads();  // the tile is refilled by the next block of rows
   }
 }
 
 template <typename T, bool MAX>
 int column_pass(const T* in, T* out, int H, int W, int k, int a, hipStream_t s) {
   const long long segs = (H + (long long)k - 1) / k;
-  hipLaunchKernelGGL((vh_column_kernel<T, MAX>), dim3(blocks_of(W, 64), blocks_of(segs, 4)), dim3(256), 0, s, in, out, H, W, k, a);
+  hipLaunchKernelGGL((vh_column_kernel<T, MAX>), dim3(blocks_of(W, 64), grid_y(blocks_of(segs, 4))), dim3(256), 0, s, in, out, H, W, k, a);
   ZK_HIP(hipGetLastError());
   return 0;
 }
 
 template <typename T>
 int transpose(const T* in, T* out, int H, int W, hipStream_t s) {
-  hipLaunchKernelGGL(transpose_kernel<T>, dim3(blocks_of(W, 64), blocks_of(H, 64)), dim3(256), 0, s, in, out, H, W);
+  hipLaunchKernelGGL(transpose_kernel<T>, dim3(blocks_of(W, 64), grid_y(blocks_of(H, 64))), dim3(256), 0, s, in, out, H, W);
   ZK_HIP(hipGetLastError());
   return 0;
 }
@@ -163,24 +176,27 @@ __global__ __launch_bounds__(256) void widen_kernel(const T* __restrict__ in, do
 template <bool ALONG_X, bool WITH_MIN>
 __global__ __launch_bounds__(256) void gauss_kernel(const double* __restrict__ in, double* __restrict__ out,
                                                     const double* __restrict__ img, int H, int W, const double* __restrict__ w, int r) {
-  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (x >= W || y >= H) return;
-  const int n = ALONG_X ? W : H, i = ALONG_X ? x : y;
-  const long long stride = ALONG_X ? 1 : W;
-  const double* line = ALONG_X ? in + (long long)y * W : in + x;
-  double t = line[i * stride] * w[0];
-  if (i - r >= 0 && i + r < n) {
-    for (int j = r; j >= 1; --j) t += (line[(i - j) * stride] + line[(i + j) * stride]) * w[j];
-  } else {
-    for (int j = r; j >= 1; --j)
-      t += (line[(long long)reflect_index(i - j, n) * stride] + line[(long long)reflect_index(i + j, n) * stride]) * w[j];
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (x >= W) return;
+  for (long long yy = (long long)blockIdx.y * 4 + (threadIdx.x >> 6); yy < H; yy += (long long)gridDim.y * 4) {
+    const int y = (int)yy;
+    const int n = ALONG_X ? W : H, i = ALONG_X ? x : y;
+    const long long stride = ALONG_X ? 1 : W;
+    const double* line = ALONG_X ? in + (long long)y * W : in + x;
+    double t = line[i * stride] * w[0];
+    if (i - r >= 0 && i + r < n) {
+      for (int j = r; j >= 1; --j) t += (line[(i - j) * stride] + line[(i + j) * stride]) * w[j];
+    } else {
+      for (int j = r; j >= 1; --j)
+        t += (line[(long long)reflect_index(i - j, n) * stride] + line[(long long)reflect_index(i + j, n) * stride]) * w[j];
+    }
+    const long long o = (long long)y * W + x;
+    if (WITH_MIN) {
+      const double v = img[o];
+      t = (v < t || v != v) ? v : t;  // np.minimum: a NaN on either side stays a NaN
+    }
+    out[o] = t;
   }
-  const long long o = (long long)y * W + x;
-  if (WITH_MIN) {
-    const double v = img[o];
-    t = v < t ? v : t;
-  }
-  out[o] = t;
 }
 
 template <typename T>
@@ -204,7 +220,7 @@ int baseline_core(const void* img_v, int H, int W, const double* wy_host, int ry
   double* wx = wy + ry + 1;
   ZK_HIP(hipMemcpyAsync(wy, wy_host, (size_t)(ry + 1) * 8, hipMemcpyHostToDevice, s));
   ZK_HIP(hipMemcpyAsync(wx, wx_host, (size_t)(rx + 1) * 8, hipMemcpyHostToDevice, s));
-  const dim3 grid(blocks_of(W, 64), blocks_of(H, 4));
+  const dim3 grid(blocks_of(W, 64), grid_y(blocks_of(H, 4)));
   for (int it = 0; it < iters; ++it) {
     hipLaunchKernelGGL((gauss_kernel<false, false>), grid, dim3(256), 0, s, it ? bg : img, d_tmp.as<double>(), nullptr, H, W, wy, ry);
     ZK_HIP(hipGetLastError());
@@ -219,9 +235,31 @@ int baseline_core(const void* img_v, int H, int W, const double* wy_host, int ry
 // rolling ball
 // ---------------------------------------------------------------------------------------------------------------------
 
+// The smallest of acc and the sums s (and s2), a NaN sum skipped, as v_min / v_min3: no operand is ever a signalling NaN (acc is
+// +inf or an earlier minimum, a sum the result of an add), so the instruction keeps the other operands where one is a NaN, which
+// is fmin().  Spelled as the instruction because fmin() makes the compiler quiet acc again on every tap (a canonicalising v_max
+// per v_min).
+__device__ __forceinline__ float min_skip_nan(float acc, float s) {
+  float r;
+  asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(acc), "v"(s));
+  return r;
+}
+__device__ __forceinline__ double min_skip_nan(double acc, double s) {
+  double r;
+  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(acc), "v"(s));
+  return r;
+}
+__device__ __forceinline__ float min_skip_nan(float acc, float s, float s2) {
+  float r;
+  asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(acc), "v"(s), "v"(s2));
+  return r;
+}
+__device__ __forceinline__ double min_skip_nan(double acc, double s, double s2) { return min_skip_nan(min_skip_nan(acc, s), s2); }
+
 // diff: (2R + 2) rows of 2R + 1 (+inf off the ball; the last row all +inf); chord[dy + R]: the half-width of row dy, -1 when it is empty.
 // Lane l of wave v owns outputs (y0 + v RB_TY + t, x0 + l + 64 u); LDS holds two staged input rows of columns
-// x0 - R .. x0 + RB_TW + R - 1 (+inf off the frame); rows off the frame are skipped (+inf contributes nothing).
+// x0 - R .. x0 + RB_TW + R - 1 (+inf off the frame); rows off the frame are skipped (+inf contributes nothing).  A workgroup
+// takes the tiles y0 = (blockIdx.y + i gridDim.y) RB_TH in turn.
 template <typename T, typename A>
 __global__ __launch_bounds__(256) void rolling_ball_kernel(const T* __restrict__ img, T* __restrict__ out, int H, int W, int R,
                                                            const A* __restrict__ diff, const int* __restrict__ chord) {
@@ -230,16 +268,8 @@ __global__ __launch_bounds__(256) void rolling_ball_kernel(const T* __restrict__
   const int LW = RB_TW + 2 * R, PW = 2 * R + 1;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int x0 = blockIdx.x * RB_TW, y0 = blockIdx.y * RB_TH;
-  const int yw = y0 + wave * RB_TY;
+  const int x0 = blockIdx.x * RB_TW;
   const A inf = std::numeric_limits<A>::infinity();
-  A acc[RB_TY][RB_NX];
-#pragma unroll
-  for (int t = 0; t < RB_TY; ++t)
-#pragma unroll
-    for (int u = 0; u < RB_NX; ++u) acc[t][u] = inf;
-
-  const int yi_lo = max(y0 - R, 0), yi_hi = min(y0 + RB_TH - 1 + R, H - 1);
   auto stage = [&](int yi, A* dst) {
     const T* src = img + (long long)yi * W;
     for (int c = threadIdx.x; c < LW; c += 256) {
@@ -247,45 +277,65 @@ __global__ __launch_bounds__(256) void rolling_ball_kernel(const T* __restrict__
       dst[c] = (gx >= 0 && gx < W) ? (A)src[gx] : inf;
     }
   };
-  stage(yi_lo, rows);
-  __syncthreads();
-  for (int yi = yi_lo, b = 0; yi <= yi_hi; ++yi, b ^= 1) {
-    if (yi < yi_hi) stage(yi + 1, rows + (b ^ 1) * LW);
-    const A* row = rows + b * LW + R + lane;  // row[dx + 64 u] = input (yi, x0 + lane + 64 u + dx)
-    int wm = -1;
-    int base[RB_TY];  // diff row offset + R of each output row; the all-inf row when its ball row is empty or off the ball
+  for (long long tile = blockIdx.y; tile * RB_TH < H; tile += gridDim.y) {
+    const int y0 = (int)(tile * RB_TH);
+    const int yw = y0 + wave * RB_TY;
+    A acc[RB_TY][RB_NX];
 #pragma unroll
-    for (int t = 0; t < RB_TY; ++t) {
-      const int dy = yi - (yw + t);
-      const int w = (dy >= -R && dy <= R && yw + t < H) ? chord[dy + R] : -1;
-      base[t] = (w >= 0 ? dy + R : PW) * PW + R;
-      wm = max(wm, w);
-    }
-    // branch-free over the rows: a row outside its chord adds +inf (the table is +inf there), which min ignores
-#pragma unroll 2
-    for (int dx = -wm; dx <= wm; ++dx) {
-      A v[RB_NX];
+    for (int t = 0; t < RB_TY; ++t)
 #pragma unroll
-      for (int u = 0; u < RB_NX; ++u) v[u] = row[dx + 64 * u];
+      for (int u = 0; u < RB_NX; ++u) acc[t][u] = inf;
+
+    const int yi_lo = max(y0 - R, 0), yi_hi = min(y0 + RB_TH - 1 + R, H - 1);
+    stage(yi_lo, rows);  // the last tile's reads ended at its closing barrier
+    __syncthreads();
+    for (int yi = yi_lo, b = 0; yi <= yi_hi; ++yi, b ^= 1) {
+      if (yi < yi_hi) stage(yi + 1, rows + (b ^ 1) * LW);
+      const A* row = rows + b * LW + R + lane;  // row[dx + 64 u] = input (yi, x0 + lane + 64 u + dx)
+      int wm = -1;
+      int base[RB_TY];  // diff row offset + R of each output row; the all-inf row when its ball row is empty or off the ball
 #pragma unroll
       for (int t = 0; t < RB_TY; ++t) {
-        const A d = diff[base[t] + dx];
+        const int dy = yi - (yw + t);
+        const int w = (dy >= -R && dy <= R && yw + t < H) ? chord[dy + R] : -1;
+        base[t] = (w >= 0 ? dy + R : PW) * PW + R;
+        wm = max(wm, w);
+      }
+      // branch-free over the rows: a row outside its chord adds +inf (the table is +inf there), which min ignores; a -inf pixel
+      // there gives -inf + inf = NaN, which it skips
+      // the tap at dx, and with PAIR the one at dx + 1: skimage keeps the smaller of the two; a NaN sum is skipped
+      auto tap = [&](int dx, auto pair) {
+        constexpr bool PAIR = decltype(pair)::value;
+        A v[RB_NX], v2[RB_NX];
 #pragma unroll
         for (int u = 0; u < RB_NX; ++u) {
-          acc[t][u] = fmin(acc[t][u], v[u] + d);  // skimage keeps the smaller of the two; a NaN sum is skipped
+          v[u] = row[dx + 64 * u];
+          if constexpr (PAIR) v2[u] = row[dx + 1 + 64 * u];
         }
-      }
+#pragma unroll
+        for (int t = 0; t < RB_TY; ++t) {
+          const A d = diff[base[t] + dx];
+#pragma unroll
+          for (int u = 0; u < RB_NX; ++u) {
+            if constexpr (PAIR) acc[t][u] = min_skip_nan(acc[t][u], v[u] + d, v2[u] + diff[base[t] + dx + 1]);
+            else acc[t][u] = min_skip_nan(acc[t][u], v[u] + d);
+          }
+        }
+      };
+      // the 2 wm + 1 taps two at a time (written out: the compiler does not unroll a loop around the v_min above by itself)
+      for (int dx = -wm; dx < wm; dx += 2) tap(dx, std::true_type());
+      if (wm >= 0) tap(wm, std::false_type());
+      __syncthreads();
     }
-    __syncthreads();
-  }
 #pragma unroll
-  for (int t = 0; t < RB_TY; ++t) {
-    const int y = yw + t;
-    if (y >= H) continue;
+    for (int t = 0; t < RB_TY; ++t) {
+      const int y = yw + t;
+      if (y >= H) continue;
 #pragma unroll
-    for (int u = 0; u < RB_NX; ++u) {
-      const int x = x0 + lane + 64 * u;
-      if (x < W) out[(long long)y * W + x] = (T)acc[t][u];  // integer types: truncation, as astype
+      for (int u = 0; u < RB_NX; ++u) {
+        const int x = x0 + lane + 64 * u;
+        if (x < W) out[(long long)y * W + x] = (T)acc[t][u];  // integer types: truncation, as astype
+      }
     }
   }
 }
@@ -320,7 +370,7 @@ int rolling_ball_core(const void* img, int H, int W, double radius, void* bg, hi
   ZK_HIP(hipMemcpyAsync(d_diff.p, diff.data(), diff.size() * sizeof(A), hipMemcpyHostToDevice, s));
   ZK_HIP(hipMemcpyAsync(d_chord.p, chord.data(), chord.size() * sizeof(int), hipMemcpyHostToDevice, s));
   const size_t lds = (size_t)2 * (RB_TW + 2 * R) * sizeof(A);
-  hipLaunchKernelGGL((rolling_ball_kernel<T, A>), dim3(blocks_of(W, RB_TW), blocks_of(H, RB_TH)), dim3(256), lds, s, (const T*)img,
+  hipLaunchKernelGGL((rolling_ball_kernel<T, A>), dim3(blocks_of(W, RB_TW), grid_y(blocks_of(H, RB_TH))), dim3(256), lds, s, (const T*)img,
                      (T*)bg, H, W, R, d_diff.as<A>(), d_chord.as<int>());
   ZK_HIP(hipGetLastError());
   ZK_HIP(hipStreamSynchronize(s));  // the tables are freed on return

@@ -12,7 +12,17 @@ returns ``(residual, background)``, and a parameter picker built on
   SciPy's.
 
 Every estimator runs on the device (``zk_background_*``, ``csrc/zk_background.hip``), the residual included; the parameter
-picker is host arithmetic.  NaN or inf pixels are not pinned by any of the three.
+picker is host arithmetic.  Frames of one row or one column are served up to the ``height * width < 2^31`` the entry checks.
+
+NaN and inf pixels (float frames), as pinned by ``tests/test_gpu_background_kernels.py``:
+
+* ``baseline``: SciPy's and NumPy's arithmetic, ``np.minimum`` included -- a NaN on either side stays a NaN, so a NaN pixel
+  (or ``inf - inf`` under the filter) spreads over the filter's reach; bit for bit, NaN positions and the signs of infinities;
+* ``rolling_ball``: scikit-image's ``if min_value > tmp`` rule -- a NaN sum is skipped, so a NaN or ``+inf`` pixel is passed over,
+  a ``-inf`` pixel takes every output whose ball holds it and no other, and an output whose ball holds NaN only is ``+inf``;
+* ``opening``: exact on ``+inf`` and ``-inf``; NaN pixels are **unspecified** (SciPy's own 1-D min / max queue depends on the
+  order it meets them in);
+* residuals: NumPy's ``image - background`` (``inf - inf`` is NaN) and ``np.clip(., 0, None)`` (a NaN stays a NaN).
 """
 from __future__ import annotations
 

@@ -4,7 +4,9 @@ the published algorithms (scikit-image's rolling ball, SciPy's symmetric correla
 
 * ``rolling_ball``: scikit-image's ``restoration.rolling_ball`` (0.19-0.25) -- ``ball_kernel``, ``diff = kernel[centre] -
   kernel``, the image padded with +inf, ``min over offsets (img[p + o] + diff[o])``, float32 for float16 / float32 images and
-  float64 otherwise, cast back with ``astype``.
+  float64 otherwise, cast back with ``astype``.  ``skip_nan`` keeps scikit-image's ``if min_value > tmp`` rule on non-finite
+  pixels (a NaN sum is skipped); ``rolling_ball_dense`` is the same minimum taken source pixel by source pixel, which costs
+  ``H W`` passes whatever the radius.
 * ``gaussian_filter`` / ``baseline``: SciPy's ``gaussian_filter`` in SciPy's own summation order for symmetric weights
   (``t = x[0] w[0]``, then ``t += (x[-j] + x[+j]) w[j]`` for j from the radius down to 1), mode 'reflect'.
 """
@@ -31,8 +33,25 @@ def ball_diff(radius, dtype=np.float64):
     return diff.astype(dtype)
 
 
-def rolling_ball(image, radius):
-    """scikit-image's ``rolling_ball(image, radius=radius)``, one ball offset at a time over the whole frame."""
+def ball_diff_window(radius, dtype, ry, rx):
+    """The values of :func:`ball_diff` at the offsets ``[-ry, ry] x [-rx, rx]`` only (``[dy + ry, dx + rx]``), by the same
+    expressions element by element; +inf off the ball, also beyond ``ceil(radius)``."""
+    dy = np.arange(-ry, ry + 1, dtype=np.float64)[:, None]
+    dx = np.arange(-rx, rx + 1, dtype=np.float64)[None, :]
+    ss = dy ** 2 + dx ** 2
+    kernel = np.sqrt(np.clip(radius ** 2 - ss, 0, None))
+    kernel[np.sqrt(ss) > radius] = np.inf
+    kernel = kernel.astype(dtype)
+    centre = np.sqrt(np.clip(np.float64(radius) ** 2, 0, None)).astype(dtype)
+    diff = centre - kernel
+    diff[kernel == np.inf] = np.inf
+    return diff.astype(dtype)
+
+
+def rolling_ball(image, radius, skip_nan=False):
+    """scikit-image's ``rolling_ball(image, radius=radius)``, one ball offset at a time over the whole frame.  ``skip_nan``:
+    accumulate with ``np.fmin`` from +inf, which is scikit-image's ``if min_value > tmp: min_value = tmp`` on non-finite
+    pixels -- a NaN sum is skipped and a neighbourhood of NaN sums only gives +inf (``np.minimum`` propagates the NaN)."""
     image = np.asarray(image)
     ft = float_type(image.dtype)
     img = image.astype(ft)
@@ -41,9 +60,33 @@ def rolling_ball(image, radius):
     h, w = img.shape
     padded = np.pad(img, R, mode="constant", constant_values=np.inf)
     out = np.full((h, w), np.inf, dtype=ft)
-    for dy, dx in zip(*np.nonzero(np.isfinite(diff))):
-        np.minimum(out, padded[dy:dy + h, dx:dx + w] + diff[dy, dx], out=out)
+    smaller = np.fmin if skip_nan else np.minimum
+    with np.errstate(invalid="ignore"):                                  # -inf + inf
+        for dy, dx in zip(*np.nonzero(np.isfinite(diff))):
+            smaller(out, padded[dy:dy + h, dx:dx + w] + diff[dy, dx], out=out)
     return out.astype(image.dtype)
+
+
+def rolling_ball_dense(image, radius, return_source=False):
+    """:func:`rolling_ball` with the loops exchanged: every pixel of the frame in turn as the source ``s`` of
+    ``img[s] + diff[s - p]`` for all outputs ``p``.  The same ``ball_diff`` values, type rule and ``astype``, and ``H W`` passes
+    over the frame whatever the radius.  ``return_source``: also the flat index of the source pixel each output took its
+    minimum from (the first in row-major order among equals)."""
+    image = np.asarray(image)
+    ft = float_type(image.dtype)
+    img = image.astype(ft)
+    h, w = img.shape
+    diff = ball_diff_window(radius, ft, h - 1, w - 1)                    # diff[sy - y + h - 1, sx - x + w - 1]
+    out = np.full((h, w), np.inf, dtype=ft)
+    source = np.full((h, w), -1, dtype=np.int64)
+    for sy in range(h):
+        for sx in range(w):
+            cand = img[sy, sx] + diff[sy:sy + h, sx:sx + w][::-1, ::-1]
+            if return_source:
+                source[cand < out] = sy * w + sx
+            np.minimum(out, cand, out=out)
+    out = out.astype(image.dtype)
+    return (out, source) if return_source else out
 
 
 def rolling_ball_at(image, radius, points):

@@ -154,3 +154,71 @@ def test_rolling_ball_restatement_types():
     assert bo.ball_diff(4, np.float32).dtype == np.float32
     diff = bo.ball_diff(2.5)
     assert diff.shape == (7, 7) and diff[3, 3] == 0 and np.isinf(diff[0, 0]) and np.isinf(diff[3, 0])
+
+
+# ------------------------------------------------------------------------------------------------ licences of the oracle forms
+# that tests/test_gpu_background_kernels.py leans on
+def _finite_frames():
+    """The finite frames the rolling-ball restatement is checked on above."""
+    rng = np.random.default_rng(7)
+    yield rng.random((45, 38)) * 10
+    rng = np.random.default_rng(8)
+    yield (rng.random((20, 24)) * 200).astype(np.uint8)
+    yield rng.random((20, 24)).astype(np.float32)
+
+
+@pytest.mark.parametrize("radius", [1, 2.5, 3, 6, 7.5, 20])
+def test_rolling_ball_skip_nan_is_the_restatement_on_finite_frames(radius):
+    for img in _finite_frames():
+        got, want = bo.rolling_ball(img, radius, skip_nan=True), bo.rolling_ball(img, radius)
+        assert got.dtype == want.dtype and got.tobytes() == want.tobytes()
+
+
+def test_rolling_ball_skip_nan_by_hand():
+    # radius 1: the pixel itself (diff 0) and its four neighbours (diff 1); a NaN sum is skipped
+    inf, nan = np.inf, np.nan
+    img = np.array([[1.0, 5.0, -inf],
+                    [nan, 2.0, 9.0],
+                    [7.0, inf, 4.0]])
+    want = np.array([[1.0, -inf, -inf],
+                     [2.0, 2.0, -inf],
+                     [7.0, 3.0, 4.0]])
+    for dtype in (np.float64, np.float32):
+        got = bo.rolling_ball(img.astype(dtype), 1, skip_nan=True)
+        assert got.dtype == dtype
+        np.testing.assert_array_equal(got, want.astype(dtype))
+    # np.minimum keeps the NaN wherever the ball touches it: the two rules differ exactly there
+    np.testing.assert_array_equal(np.isnan(bo.rolling_ball(img, 1)),
+                                  [[True, False, False], [True, True, False], [True, False, False]])
+    # nothing but NaN sums: +inf
+    np.testing.assert_array_equal(bo.rolling_ball(np.full((3, 3), nan), 1, skip_nan=True), np.full((3, 3), inf))
+
+
+@pytest.mark.parametrize("radius", [1, 2.5, 6, 20])
+def test_rolling_ball_dense_is_the_restatement(radius):
+    rng = np.random.default_rng(7)
+    img = rng.random((45, 38)) * 10
+    for frame in (img, img.astype(np.float32), (img * 25).astype(np.uint8)):
+        got, want = bo.rolling_ball_dense(frame, radius), bo.rolling_ball(frame, radius)
+        assert got.dtype == want.dtype and got.tobytes() == want.tobytes()
+    got, source = bo.rolling_ball_dense(img, radius, return_source=True)
+    np.testing.assert_array_equal(got, bo.rolling_ball(img, radius))
+    # the source named for every output gives that output's value, and lies on the ball
+    sy, sx = np.divmod(source, img.shape[1])
+    yy, xx = np.mgrid[0:45, 0:38]
+    assert np.all(np.hypot(sy - yy, sx - xx) <= radius)
+    R = int(np.ceil(radius))
+    np.testing.assert_array_equal(img[sy, sx] + bo.ball_diff(radius)[sy - yy + R, sx - xx + R], got)
+
+
+def test_ball_diff_window_is_a_window_of_ball_diff():
+    for radius in (0.5, 1, 2.5, 6, 20, 33.5):
+        R = int(np.ceil(radius))
+        for dtype in (np.float64, np.float32):
+            full = bo.ball_diff(radius, dtype)
+            for ry, rx in ((R, R), (0, R), (R, 0), (2, 1), (R + 3, R + 5)):
+                win = bo.ball_diff_window(radius, dtype, ry, rx)
+                assert win.dtype == dtype and win.shape == (2 * ry + 1, 2 * rx + 1)
+                padded = np.pad(full, ((max(ry - R, 0),) * 2, (max(rx - R, 0),) * 2), constant_values=np.inf)
+                cy, cx = padded.shape[0] // 2, padded.shape[1] // 2
+                np.testing.assert_array_equal(win, padded[cy - ry:cy + ry + 1, cx - rx:cx + rx + 1])
