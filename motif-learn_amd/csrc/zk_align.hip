@@ -41,10 +41,12 @@
 // rows into the plan's scratch matrix (P, band, W), the planes kernel turns the band into its part of the maps, band after
 // band on one stream: the (P, H, W) moments never exist.  A band holds at most 1 GiB of moments (zk_align_set_band_bytes: less),
 // at least one row, whole multiples of 8 rows where it can (a block of the dense kernels).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <optional>
 
 #include "zk_ring.h"
 
@@ -350,32 +352,30 @@ struct align_slot {
 };
 
 struct align_state {
-  hipStream_t stream = nullptr;  // kernels of the host variants
-  zk_ring ring;                  // their staging (zk_ring.h)
-  size_t host_chunk = 0;
-  size_t band_bytes = 0;         // moments per band of zk_frame_align; 0 = 1 GiB
+  zk_stage stage;  // the host variants: their kernel stream and staging (zk_ring.h)
   std::vector<align_table> tables;
   align_slot slots[ZK_ALIGN_SLOTS];
   int next = 0;
 };
 
-std::mutex g_mu;                   // one call at a time per process: the state below is shared
-align_state* g_state[64] = {};     // per device, created on first use, kept for the life of the process
+std::mutex g_mu;                                // one call at a time per process: the state below is shared
+align_state* g_state[ZK_DEVICE_TABLE] = {};     // per device, created on first use, kept for the life of the process
+zk_device_bytes g_host_chunk;                   // zk_align_set_host_chunk: input + output of a chunk of the host variants; 0: 256 MiB
+zk_device_bytes g_band_bytes;                   // zk_align_set_band_bytes: moments per band of zk_frame_align; 0: 1 GiB
 
 int get_state(int device, align_state** out) {
-  if (device < 0 || device >= 64) return zk_fail(ZK_E_BADARG, "device index out of range");
   if (!g_state[device]) {
     align_state* s = new (std::nothrow) align_state();
     if (!s) return zk_fail(ZK_E_NOMEM, "out of host memory");
-    hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-    int rc = e == hipSuccess ? zk_ring_create(&s->ring) : zk_hip_fail(e, "hipStreamCreateWithFlags");
-    for (int k = 0; k < ZK_ALIGN_SLOTS && !rc; ++k)
-      if ((e = hipEventCreateWithFlags(&s->slots[k].ev, hipEventDisableTiming)) != hipSuccess) rc = zk_hip_fail(e, "hipEventCreateWithFlags");
+    int rc = zk_stage_create(&s->stage);
+    for (int k = 0; k < ZK_ALIGN_SLOTS && !rc; ++k) {
+      const hipError_t e = hipEventCreateWithFlags(&s->slots[k].ev, hipEventDisableTiming);
+      if (e != hipSuccess) rc = zk_hip_fail(e, "hipEventCreateWithFlags");
+    }
     if (rc) {
-      zk_ring_destroy(&s->ring);
+      zk_stage_destroy(&s->stage);
       for (int k = 0; k < ZK_ALIGN_SLOTS; ++k)
         if (s->slots[k].ev) (void)hipEventDestroy(s->slots[k].ev);
-      if (s->stream) (void)hipStreamDestroy(s->stream);
       delete s;
       return rc;
     }
@@ -385,12 +385,27 @@ int get_state(int device, align_state** out) {
   return 0;
 }
 
-int check_device(int device) {
-  const int ndev = zk_device_count();
-  if (ndev < 0) return ndev;
-  if (ndev == 0) return zk_fail(ZK_E_NODEVICE, "no HIP device visible");
-  if (device < 0 || device >= ndev || device >= 64) return zk_fail(ZK_E_BADARG, "device index out of range");
-  return 0;
+// how every entry point opens, once its arguments have passed: the device is there and current, the call is the only one, and
+// the device's state exists
+struct align_call {
+  std::optional<zk_device_scope> scope;
+  std::unique_lock<std::mutex> lock;
+  align_state* s = nullptr;
+  int open(int device) {
+    const int rc = zk_check_device(device, ZK_DEVICE_TABLE);
+    if (rc) return rc;
+    scope.emplace(device);
+    if (scope->err != hipSuccess) return zk_hip_fail(scope->err, "hipSetDevice");
+    lock = std::unique_lock<std::mutex>(g_mu);
+    return get_state(device, &s);
+  }
+};
+
+// the two byte knobs only keep a number; like every entry point they refuse a device that is not there
+int set_bytes(zk_device_bytes* knob, int device, int64_t bytes) {
+  if (bytes < 0) return zk_fail(ZK_E_BADARG, "bad arguments");
+  const int rc = zk_check_device(device, ZK_DEVICE_TABLE);
+  return rc ? rc : knob->set(device, bytes, "bad arguments");
 }
 
 // the next operand slot with room for `bytes`; its previous reader has finished (a wait only when ZK_ALIGN_SLOTS calls are
@@ -656,17 +671,7 @@ int launch_rotate(const align_job& j, const double* rows, int64_t n, const doubl
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
-extern "C" int zk_align_set_host_chunk(int device, int64_t chunk_bytes) {
-  if (chunk_bytes < 0) return zk_fail(ZK_E_BADARG, "bad arguments");
-  int rc = check_device(device);
-  if (rc) return rc;
-  ZK_ON_DEVICE(device);
-  std::lock_guard<std::mutex> lock(g_mu);
-  align_state* s = nullptr;
-  if ((rc = get_state(device, &s))) return rc;
-  s->host_chunk = (size_t)chunk_bytes;
-  return 0;
-}
+extern "C" int zk_align_set_host_chunk(int device, int64_t chunk_bytes) { return set_bytes(&g_host_chunk, device, chunk_bytes); }
 
 extern "C" int zk_align_rows_dev(int device, const double* rows_dev, int64_t n_rows, int n_poly, const int32_t* n, const int32_t* m,
                                  const double* templates_host, int n_templates, const int32_t* select, int n_theta, int symmetry,
@@ -677,11 +682,9 @@ extern "C" int zk_align_rows_dev(int device, const double* rows_dev, int64_t n_r
                        trig_m, key_values_host, &a);
   if (rc) return rc;
   if (n_rows == 0) return 0;
-  if ((rc = check_device(device))) return rc;
-  ZK_ON_DEVICE(device);
-  std::lock_guard<std::mutex> lock(g_mu);
-  align_state* s = nullptr;
-  if ((rc = get_state(device, &s))) return rc;
+  align_call call;
+  if ((rc = call.open(device))) return rc;
+  align_state* s = call.s;
   const hipStream_t stream = (hipStream_t)hip_stream;  // exactly the caller's stream
   align_job job;
   if ((rc = prepare_align(s, a, n_poly, n_templates, n_theta, symmetry, newton_iters, key, trig_host, trig_m, stream, &job))) return rc;
@@ -699,26 +702,24 @@ extern "C" int zk_align_rows(int device, const double* rows_host, int64_t n_rows
                        trig_m, key_values_host, &a);
   if (rc) return rc;
   if (n_rows == 0) return 0;
-  if ((rc = check_device(device))) return rc;
-  ZK_ON_DEVICE(device);
-  std::lock_guard<std::mutex> lock(g_mu);
-  align_state* s = nullptr;
-  if ((rc = get_state(device, &s))) return rc;
+  align_call call;
+  if ((rc = call.open(device))) return rc;
+  align_state* s = call.s;
   align_job job;
-  if ((rc = prepare_align(s, a, n_poly, n_templates, n_theta, symmetry, newton_iters, key, trig_host, trig_m, s->stream, &job))) return rc;
-  zk_ring* r = &s->ring;
+  if ((rc = prepare_align(s, a, n_poly, n_templates, n_theta, symmetry, newton_iters, key, trig_host, trig_m, s->stage.stream, &job))) return rc;
+  zk_ring* r = &s->stage.ring;
   const size_t T = (size_t)n_templates, in_unit = (size_t)n_poly * sizeof(double), out_unit = T * 2 * sizeof(double) + sizeof(int32_t);
-  const size_t budget = s->host_chunk ? s->host_chunk : (size_t)256 << 20;
+  const size_t budget = g_host_chunk.get(device, (size_t)256 << 20);
   const zk_chunks ch = zk_chunk_plan(budget, in_unit + out_unit, 256, n_rows);
   // a slot's output: angle (chunk, T) | score (chunk, T) | best (chunk), each at the offset of a full chunk
   const size_t plane = (size_t)ch.chunk * T * sizeof(double);
   rc = zk_ring_run(
-      r, s->stream, ch.n_chunks,
+      r, s->stage.stream, ch.n_chunks,
       [&](int64_t c, int slot) -> int {
         int e = zk_ring_slot(r, slot, (size_t)ch.chunk * in_unit, 2 * plane + (size_t)ch.chunk * sizeof(int32_t));
-        if (!e) e = zk_ring_up(r, s->stream, c, slot, r->d_in[slot], rows_host + (size_t)ch.first(c) * n_poly, (size_t)ch.count(c) * in_unit);
+        if (!e) e = zk_ring_up(r, s->stage.stream, c, slot, r->d_in[slot], rows_host + (size_t)ch.first(c) * n_poly, (size_t)ch.count(c) * in_unit);
         char* o = (char*)r->d_out[slot];
-        return e ? e : launch_align(job, (const double*)r->d_in[slot], ch.count(c), (double*)o, (double*)(o + plane), (int32_t*)(o + 2 * plane), s->stream);
+        return e ? e : launch_align(job, (const double*)r->d_in[slot], ch.count(c), (double*)o, (double*)(o + plane), (int32_t*)(o + 2 * plane), s->stage.stream);
       },
       [&](int64_t c, int slot) -> int {
         const char* o = (const char*)r->d_out[slot];
@@ -729,21 +730,11 @@ extern "C" int zk_align_rows(int device, const double* rows_host, int64_t n_rows
         return 0;
       });
   job.slot->used = false;  // the job has drained
-  if (zk_ring_bytes(r) > ((size_t)32 << 20)) zk_ring_free_slots(r);  // a large job's slots go back at once (as zk_synth_apply)
+  zk_stage_trim(&s->stage, ZK_STAGE_KEEP_ROWS);
   return rc;
 }
 
-extern "C" int zk_align_set_band_bytes(int device, int64_t bytes) {
-  if (bytes < 0) return zk_fail(ZK_E_BADARG, "bad arguments");
-  int rc = check_device(device);
-  if (rc) return rc;
-  ZK_ON_DEVICE(device);
-  std::lock_guard<std::mutex> lock(g_mu);
-  align_state* s = nullptr;
-  if ((rc = get_state(device, &s))) return rc;
-  s->band_bytes = (size_t)bytes;
-  return 0;
-}
+extern "C" int zk_align_set_band_bytes(int device, int64_t bytes) { return set_bytes(&g_band_bytes, device, bytes); }
 
 extern "C" int zk_align_planes_dev(int device, const double* planes_dev, int64_t n_pixels, int64_t plane_stride, int n_poly, const int32_t* n,
                                    const int32_t* m, const double* templates_host, int n_templates, const int32_t* select, int n_theta,
@@ -756,11 +747,9 @@ extern "C" int zk_align_planes_dev(int device, const double* planes_dev, int64_t
   if (rc) return rc;
   if ((rc = check_planes(n_pixels, plane_stride, out_plane_stride))) return rc;
   if (n_pixels == 0) return 0;
-  if ((rc = check_device(device))) return rc;
-  ZK_ON_DEVICE(device);
-  std::lock_guard<std::mutex> lock(g_mu);
-  align_state* s = nullptr;
-  if ((rc = get_state(device, &s))) return rc;
+  align_call call;
+  if ((rc = call.open(device))) return rc;
+  align_state* s = call.s;
   const hipStream_t stream = (hipStream_t)hip_stream;  // exactly the caller's stream
   align_job job;
   if ((rc = prepare_align(s, a, n_poly, n_templates, n_theta, symmetry, newton_iters, key, trig_host, trig_m, stream, &job, true))) return rc;
@@ -779,29 +768,27 @@ extern "C" int zk_align_planes(int device, const double* planes_host, int64_t n_
   if (rc) return rc;
   if ((rc = check_planes(n_pixels, plane_stride, out_plane_stride))) return rc;
   if (n_pixels == 0) return 0;
-  if ((rc = check_device(device))) return rc;
-  ZK_ON_DEVICE(device);
-  std::lock_guard<std::mutex> lock(g_mu);
-  align_state* s = nullptr;
-  if ((rc = get_state(device, &s))) return rc;
+  align_call call;
+  if ((rc = call.open(device))) return rc;
+  align_state* s = call.s;
   align_job job;
-  if ((rc = prepare_align(s, a, n_poly, n_templates, n_theta, symmetry, newton_iters, key, trig_host, trig_m, s->stream, &job, true))) return rc;
-  zk_ring* r = &s->ring;
+  if ((rc = prepare_align(s, a, n_poly, n_templates, n_theta, symmetry, newton_iters, key, trig_host, trig_m, s->stage.stream, &job, true))) return rc;
+  zk_ring* r = &s->stage.ring;
   const size_t T = (size_t)n_templates, in_unit = (size_t)n_poly * sizeof(double), out_unit = (T * 2 + 1) * sizeof(double) + sizeof(int32_t);
-  const size_t budget = s->host_chunk ? s->host_chunk : (size_t)256 << 20;
+  const size_t budget = g_host_chunk.get(device, (size_t)256 << 20);
   const zk_chunks ch = zk_chunk_plan(budget, in_unit + out_unit, 256, n_pixels);
   // a slot's input: (P, chunk) planes; its output: angle (T, chunk) | score (T, chunk) | norm2 (chunk) | best (chunk)
   const size_t line = (size_t)ch.chunk * sizeof(double), plane = T * line;
   rc = zk_ring_run(
-      r, s->stream, ch.n_chunks,
+      r, s->stage.stream, ch.n_chunks,
       [&](int64_t c, int slot) -> int {
         int e = zk_ring_slot(r, slot, (size_t)n_poly * line, 2 * plane + line + (size_t)ch.chunk * sizeof(int32_t));
         if (!e)  // a chunk of a (P, .) operand: P pieces, one per plane
-          e = zk_ring_up_2d(r, s->stream, c, slot, r->d_in[slot], line, planes_host + ch.first(c), (size_t)plane_stride * sizeof(double),
+          e = zk_ring_up_2d(r, s->stage.stream, c, slot, r->d_in[slot], line, planes_host + ch.first(c), (size_t)plane_stride * sizeof(double),
                             (size_t)ch.count(c) * sizeof(double), (size_t)n_poly);
         char* o = (char*)r->d_out[slot];
         return e ? e : launch_align_planes(job, (const double*)r->d_in[slot], ch.count(c), ch.chunk, (double*)o, (double*)(o + plane),
-                                           (int32_t*)(o + 2 * plane + line), (double*)(o + 2 * plane), ch.chunk, s->stream);
+                                           (int32_t*)(o + 2 * plane + line), (double*)(o + 2 * plane), ch.chunk, s->stage.stream);
       },
       [&](int64_t c, int slot) -> int {
         const char* o = (const char*)r->d_out[slot];
@@ -814,7 +801,7 @@ extern "C" int zk_align_planes(int device, const double* planes_host, int64_t n_
         return 0;
       });
   job.slot->used = false;  // the job has drained
-  if (zk_ring_bytes(r) > ((size_t)32 << 20)) zk_ring_free_slots(r);
+  zk_stage_trim(&s->stage, ZK_STAGE_KEEP_ROWS);
   return rc;
 }
 
@@ -825,7 +812,7 @@ static int frame_align_check(const zk_plan* p, const void* image, int dtype, boo
                              int key, const double* trig_host, int trig_m, const double* key_values, int64_t out_plane_stride,
                              align_args* a) {
   if (!p) return zk_fail(ZK_E_BADARG, "null plan");
-  if (narrow_ok ? (dtype < ZK_F32 || dtype > ZK_I16) : (dtype != ZK_F32 && dtype != ZK_F64))
+  if (narrow_ok ? !zk_is_elem(dtype) : (dtype != ZK_F32 && dtype != ZK_F64))
     return zk_fail(ZK_E_BADARG, narrow_ok ? "dtype must be ZK_F32, ZK_F64, ZK_U8, ZK_U16 or ZK_I16" : "dtype must be ZK_F32 or ZK_F64");
   if (H <= 0 || W <= 0 || H > 0x3fffffff || W > 0x3fffffff) return zk_fail(ZK_E_BADARG, "bad frame shape");
   if (row0 < 0 || n_rows < 0 || row0 + n_rows > H) return zk_fail(ZK_E_BADARG, "row band outside the frame");
@@ -852,15 +839,13 @@ extern "C" int zk_frame_align_dev(zk_plan* p, const void* image_dev, int dtype, 
                              newton_iters, key, trig_host, trig_m, key_values_host, out_plane_stride, &a);
   if (rc) return rc;
   if (n_rows == 0) return 0;
-  if ((rc = check_device(p->device))) return rc;
-  ZK_ON_PLAN_DEVICE(p);
-  std::lock_guard<std::mutex> lock(g_mu);
-  align_state* s = nullptr;
-  if ((rc = get_state(p->device, &s))) return rc;
+  align_call call;
+  if ((rc = call.open(p->device))) return rc;
+  align_state* s = call.s;
   const hipStream_t stream = (hipStream_t)hip_stream;  // exactly the caller's stream
   // rows per band: what the byte limit holds, at least one, whole blocks of the dense kernels (8 rows) where there are that many
   const size_t row_bytes = (size_t)p->n_poly * (size_t)W * sizeof(double);
-  const size_t limit = s->band_bytes && s->band_bytes < ((size_t)1 << 30) ? s->band_bytes : (size_t)1 << 30;
+  const size_t limit = std::min(g_band_bytes.get(p->device, (size_t)1 << 30), (size_t)1 << 30);
   int64_t band = (int64_t)(limit / row_bytes);
   if (band < 1) band = 1;
   if (band >= n_rows) band = n_rows;
@@ -888,11 +873,9 @@ extern "C" int zk_rotate_rows_dev(int device, const double* rows_dev, int64_t n_
   int rc = check_rotate(rows_dev, n_rows, n_poly, n, m, angles_dev, out_dev, &pr);
   if (rc) return rc;
   if (n_rows == 0) return 0;
-  if ((rc = check_device(device))) return rc;
-  ZK_ON_DEVICE(device);
-  std::lock_guard<std::mutex> lock(g_mu);
-  align_state* s = nullptr;
-  if ((rc = get_state(device, &s))) return rc;
+  align_call call;
+  if ((rc = call.open(device))) return rc;
+  align_state* s = call.s;
   const hipStream_t stream = (hipStream_t)hip_stream;
   align_job job;
   job.P = n_poly;
@@ -909,22 +892,20 @@ extern "C" int zk_rotate_rows(int device, const double* rows_host, int64_t n_row
   int rc = check_rotate(rows_host, n_rows, n_poly, n, m, angles_host, out_host, &pr);
   if (rc) return rc;
   if (n_rows == 0) return 0;
-  if ((rc = check_device(device))) return rc;
-  ZK_ON_DEVICE(device);
-  std::lock_guard<std::mutex> lock(g_mu);
-  align_state* s = nullptr;
-  if ((rc = get_state(device, &s))) return rc;
+  align_call call;
+  if ((rc = call.open(device))) return rc;
+  align_state* s = call.s;
   align_job job;
   job.P = n_poly;
   job.m_top = pr.m_top;
-  if ((rc = upload_blob(s, pr, nullptr, nullptr, 0, s->stream, &job))) return rc;
-  zk_ring* r = &s->ring;
+  if ((rc = upload_blob(s, pr, nullptr, nullptr, 0, s->stage.stream, &job))) return rc;
+  zk_ring* r = &s->stage.ring;
   const size_t row_bytes = (size_t)n_poly * sizeof(double);
-  const size_t budget = s->host_chunk ? s->host_chunk : (size_t)256 << 20;
+  const size_t budget = g_host_chunk.get(device, (size_t)256 << 20);
   const zk_chunks ch = zk_chunk_plan(budget, 2 * row_bytes + sizeof(double), 256, n_rows);
   const size_t rows_cap = (size_t)ch.chunk * row_bytes;  // a slot's input: the rows, then their angles
   rc = zk_ring_run(
-      r, s->stream, ch.n_chunks,
+      r, s->stage.stream, ch.n_chunks,
       [&](int64_t c, int slot) -> int {
         int e = zk_ring_slot(r, slot, rows_cap + (size_t)ch.chunk * sizeof(double), rows_cap);
         if (e) return e;
@@ -932,13 +913,13 @@ extern "C" int zk_rotate_rows(int device, const double* rows_host, int64_t n_row
         // the angles go up ahead of the rows on the same stream; zk_ring_up's event then covers both
         if (c >= ZK_RING_SLOTS) ZK_HIP(hipStreamWaitEvent(r->s_in, r->ev_k[slot], 0));
         ZK_HIP(hipMemcpyAsync(in + rows_cap, angles_host + ch.first(c), (size_t)ch.count(c) * sizeof(double), hipMemcpyHostToDevice, r->s_in));
-        e = zk_ring_up(r, s->stream, c, slot, in, rows_host + (size_t)ch.first(c) * n_poly, (size_t)ch.count(c) * row_bytes);
-        return e ? e : launch_rotate(job, (const double*)in, ch.count(c), (const double*)(in + rows_cap), (double*)r->d_out[slot], s->stream);
+        e = zk_ring_up(r, s->stage.stream, c, slot, in, rows_host + (size_t)ch.first(c) * n_poly, (size_t)ch.count(c) * row_bytes);
+        return e ? e : launch_rotate(job, (const double*)in, ch.count(c), (const double*)(in + rows_cap), (double*)r->d_out[slot], s->stage.stream);
       },
       [&](int64_t c, int slot) -> int {
         return zk_ring_down(r, slot, (char*)out_host + (size_t)ch.first(c) * row_bytes, (size_t)ch.count(c) * row_bytes);
       });
   job.slot->used = false;
-  if (zk_ring_bytes(r) > ((size_t)32 << 20)) zk_ring_free_slots(r);
+  zk_stage_trim(&s->stage, ZK_STAGE_KEEP_ROWS);
   return rc;
 }

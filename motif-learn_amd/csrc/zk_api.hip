@@ -38,6 +38,14 @@ extern "C" int zk_device_count(void) {
   return n;
 }
 
+int zk_check_device(int device, int table_limit) {
+  const int ndev = zk_device_count();
+  if (ndev < 0) return ndev;
+  if (ndev == 0) return zk_fail(ZK_E_NODEVICE, "no HIP device visible");
+  if (device < 0 || device >= ndev || (table_limit && device >= table_limit)) return zk_fail(ZK_E_BADARG, "device index out of range");
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------
 // profiling: one event pair per launch, resolved lazily
 // ------------------------------------------------------------------------------------
@@ -172,10 +180,8 @@ extern "C" int zk_plan_create(int size, int n_poly, const int32_t* n, const int3
   if (size <= 0 || n_poly <= 0 || !basis || !n || !m)
     return zk_fail(ZK_E_BADARG, "size and n_poly must be positive and basis/n/m non-null");
   if (size > 4096) return zk_fail(ZK_E_BADARG, "size too large");
-  const int ndev = zk_device_count();
-  if (ndev < 0) return ndev;
-  if (ndev == 0) return zk_fail(ZK_E_NODEVICE, "no HIP device visible");
-  if (device < 0 || device >= ndev) return zk_fail(ZK_E_BADARG, "device index out of range");
+  int rc = zk_check_device(device);
+  if (rc) return rc;
   zk_plan* p = new (std::nothrow) zk_plan();
   if (!p) return zk_fail(ZK_E_NOMEM, "out of host memory");
   p->size = size;
@@ -183,7 +189,6 @@ extern "C" int zk_plan_create(int size, int n_poly, const int32_t* n, const int3
   p->device = device;
   p->n.assign(n, n + n_poly);
   p->m.assign(m, m + n_poly);
-  int rc = 0;
   zk_device_scope scope(device);
   hipError_t e = scope.err;
   if (e != hipSuccess) rc = zk_hip_fail(e, "hipSetDevice");

@@ -431,17 +431,11 @@ int run_typed(const args& a, const void* img, int H, int W, int clip, void* bg, 
 }
 
 int run(const args& a, const void* img, int dtype, int H, int W, int clip, void* bg, void* res, hipStream_t s) {
-  switch (dtype) {
-    case ZK_F32: return run_typed<float>(a, img, H, W, clip, bg, res, s);
-    case ZK_F64: return run_typed<double>(a, img, H, W, clip, bg, res, s);
-    case ZK_U8: return run_typed<uint8_t>(a, img, H, W, clip, bg, res, s);
-    case ZK_U16: return run_typed<uint16_t>(a, img, H, W, clip, bg, res, s);
-    default: return run_typed<int16_t>(a, img, H, W, clip, bg, res, s);
-  }
+  return zk_with_elem(dtype, [&](auto e) { return run_typed<typename decltype(e)::type>(a, img, H, W, clip, bg, res, s); });
 }
 
 int check_common(int dtype, int64_t H, int64_t W, const void* img, const void* bg) {
-  if (dtype < ZK_F32 || dtype > ZK_I16) return zk_fail(ZK_E_BADARG, "dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
+  if (!zk_is_elem(dtype)) return zk_fail(ZK_E_BADARG, "dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
   if (H <= 0 || W <= 0 || H * W >= ((int64_t)1 << 31)) return zk_fail(ZK_E_BADARG, "bad image shape (needs 0 < height * width < 2^31)");
   if (!img || !bg) return zk_fail(ZK_E_BADARG, "null pointer");
   return 0;

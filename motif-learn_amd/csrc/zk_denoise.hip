@@ -300,7 +300,7 @@ __global__ __launch_bounds__(256) void windows_reconstruct_kernel(grid_desc g, c
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
 int check_frame(int dtype, int64_t H, int64_t W, int64_t ph, int64_t pw) {
-  if (dtype < ZK_F32 || dtype > ZK_I16) return zk_fail(ZK_E_BADARG, "dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
+  if (!zk_is_elem(dtype)) return zk_fail(ZK_E_BADARG, "dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
   if (H <= 0 || W <= 0 || H * W >= ((int64_t)1 << 31)) return zk_fail(ZK_E_BADARG, "bad image shape (needs 0 < height * width < 2^31)");
   if (ph < 1 || pw < 1 || ph > H || pw > W) return zk_fail(ZK_E_BADARG, "the patch must be at least 1 x 1 and fit the image");
   if (ph * pw > ((int64_t)1 << 23)) return zk_fail(ZK_E_BADARG, "patch too large");
@@ -412,23 +412,14 @@ int moments_typed(const void* img, int H, int W, int ph, int pw, double* mu, dou
   return 0;
 }
 
-#define ZK_DN_DISPATCH(fn, dtype, ...)                            \
-  switch (dtype) {                                                \
-    case ZK_F32: return fn<float>(__VA_ARGS__);                   \
-    case ZK_F64: return fn<double>(__VA_ARGS__);                  \
-    case ZK_U8: return fn<uint8_t>(__VA_ARGS__);                  \
-    case ZK_U16: return fn<uint16_t>(__VA_ARGS__);                \
-    default: return fn<int16_t>(__VA_ARGS__);                     \
-  }
-
 int apply_any(int dtype, const void* img, const grid_desc& g, const double* Q, int l, const double* mu, double* Y, hipStream_t s) {
-  ZK_DN_DISPATCH(apply_typed, dtype, img, g, Q, l, mu, Y, s);
+  return zk_with_elem(dtype, [&](auto e) { return apply_typed<typename decltype(e)::type>(img, g, Q, l, mu, Y, s); });
 }
 int apply_t_any(int dtype, const void* img, const grid_desc& g, const double* Y, int l, double* Z, hipStream_t s) {
-  ZK_DN_DISPATCH(apply_t_typed, dtype, img, g, Y, l, Z, s);
+  return zk_with_elem(dtype, [&](auto e) { return apply_t_typed<typename decltype(e)::type>(img, g, Y, l, Z, s); });
 }
 int moments_any(int dtype, const void* img, int H, int W, int ph, int pw, double* mu, double* C, hipStream_t s) {
-  ZK_DN_DISPATCH(moments_typed, dtype, img, H, W, ph, pw, mu, C, s);
+  return zk_with_elem(dtype, [&](auto e) { return moments_typed<typename decltype(e)::type>(img, H, W, ph, pw, mu, C, s); });
 }
 
 int check_columns(int64_t l) {

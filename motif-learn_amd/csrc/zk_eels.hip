@@ -47,7 +47,7 @@ namespace {
 
 constexpr int PF = ZK_EELS_PF;
 constexpr size_t DEFAULT_CAP = (size_t)1 << 30;
-size_t g_cap[64] = {};  // scratch cap per device; 0 = default
+zk_device_bytes g_cap;  // zk_eels_set_chunk: scratch cap per device; 0: DEFAULT_CAP
 
 // ---------------------------------------------------------------------------------------------------------------------
 // layout
@@ -392,17 +392,9 @@ struct eels_job {
   int weights_per_spectrum = 0;
 };
 
-int check_device(int device) {
-  const int ndev = zk_device_count();
-  if (ndev < 0) return ndev;
-  if (ndev == 0) return zk_fail(ZK_E_NODEVICE, "no HIP device visible");
-  if (device < 0 || device >= ndev || device >= 64) return zk_fail(ZK_E_BADARG, "device index out of range");
-  return 0;
-}
-
 int check_shape(const char* who, const void* data, int dtype, int64_t outer, int64_t length, int64_t inner, const void* baseline) {
   const std::string name(who);
-  if (dtype < ZK_F32 || dtype > ZK_I16) return zk_fail(ZK_E_BADARG, name + ": dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
+  if (!zk_is_elem(dtype)) return zk_fail(ZK_E_BADARG, name + ": dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
   if (outer < 1 || inner < 1 || length < 1) return zk_fail(ZK_E_BADARG, name + ": outer, length and inner must be positive");
   if (length >= ((int64_t)1 << 24) || outer >= ((int64_t)1 << 31) || inner >= ((int64_t)1 << 31) || outer * inner >= ((int64_t)1 << 31) ||
       outer * inner * length >= ((int64_t)1 << 40))
@@ -430,7 +422,7 @@ int check_job(const eels_job& j, int64_t length, bool has_weights) {
 
 // spectra per chunk: the largest multiple of 64 whose scratch planes stay under the device's cap
 int64_t chunk_columns(int device, int64_t L, int planes, int64_t N) {
-  const size_t cap = g_cap[device] ? g_cap[device] : DEFAULT_CAP;
+  const size_t cap = g_cap.get(device, DEFAULT_CAP);
   int64_t nc = (int64_t)(cap / ((size_t)L * 8 * (size_t)planes)) / 64 * 64;
   nc = std::max<int64_t>(nc, 64);
   return std::min<int64_t>(nc, (N + 63) / 64 * 64);
@@ -534,13 +526,7 @@ int run_typed(int device, const eels_job& j, const void* data_v, int64_t A, int6
 
 int run_dev(int device, const eels_job& j, const void* data, int dtype, int64_t A, int64_t L, int64_t B, double* baseline, double* signal,
             int32_t* iters, hipStream_t s) {
-  switch (dtype) {
-    case ZK_F32: return run_typed<float>(device, j, data, A, L, B, baseline, signal, iters, s);
-    case ZK_F64: return run_typed<double>(device, j, data, A, L, B, baseline, signal, iters, s);
-    case ZK_U8: return run_typed<uint8_t>(device, j, data, A, L, B, baseline, signal, iters, s);
-    case ZK_U16: return run_typed<uint16_t>(device, j, data, A, L, B, baseline, signal, iters, s);
-    default: return run_typed<int16_t>(device, j, data, A, L, B, baseline, signal, iters, s);
-  }
+  return zk_with_elem(dtype, [&](auto e) { return run_typed<typename decltype(e)::type>(device, j, data, A, L, B, baseline, signal, iters, s); });
 }
 
 // the host-buffer form: the cube goes up, baseline (signal, iteration counts) come down
@@ -583,17 +569,14 @@ eels_job pls_job(int mode, int order, double lam, double param, int itermax, con
 
 // ---------------------------------------------------------------------------------------------------------
 extern "C" int zk_eels_set_chunk(int device, int64_t scratch_bytes) {
-  if (scratch_bytes < 0) return zk_fail(ZK_E_BADARG, "bad arguments");
-  if (device < 0 || device >= 64) return zk_fail(ZK_E_BADARG, "device index out of range");
-  g_cap[device] = (size_t)scratch_bytes;
-  return 0;
+  return g_cap.set(device, scratch_bytes, "bad arguments");
 }
 
 extern "C" int zk_eels_snip(int device, const void* data_host, int dtype, int64_t outer, int64_t length, int64_t inner, int niter,
                             double* baseline_host, double* signal_host) {
   const eels_job j = snip_job(niter);
   int rc = check_shape("eels_snip", data_host, dtype, outer, length, inner, baseline_host);
-  if (rc || (rc = check_job(j, length, false)) || (rc = check_device(device))) return rc;
+  if (rc || (rc = check_job(j, length, false)) || (rc = zk_check_device(device, ZK_DEVICE_TABLE))) return rc;
   ZK_ON_DEVICE(device);
   return run_host(device, j, data_host, dtype, outer, length, inner, nullptr, baseline_host, signal_host, nullptr);
 }
@@ -602,7 +585,7 @@ extern "C" int zk_eels_snip_dev(int device, const void* data_dev, int dtype, int
                                 double* baseline_dev, double* signal_dev, void* hip_stream) {
   const eels_job j = snip_job(niter);
   int rc = check_shape("eels_snip", data_dev, dtype, outer, length, inner, baseline_dev);
-  if (rc || (rc = check_job(j, length, false)) || (rc = check_device(device))) return rc;
+  if (rc || (rc = check_job(j, length, false)) || (rc = zk_check_device(device, ZK_DEVICE_TABLE))) return rc;
   ZK_ON_DEVICE(device);
   return run_dev(device, j, data_dev, dtype, outer, length, inner, baseline_dev, signal_dev, nullptr, (hipStream_t)hip_stream);
 }
@@ -612,7 +595,7 @@ extern "C" int zk_eels_pls(int device, const void* data_host, int dtype, int64_t
                            double* baseline_host, double* signal_host, int32_t* iterations_host) {
   const eels_job j = pls_job(mode, order, lam, param, itermax, nullptr, weights_per_spectrum);
   int rc = check_shape("eels_pls", data_host, dtype, outer, length, inner, baseline_host);
-  if (rc || (rc = check_job(j, length, weights_host != nullptr)) || (rc = check_device(device))) return rc;
+  if (rc || (rc = check_job(j, length, weights_host != nullptr)) || (rc = zk_check_device(device, ZK_DEVICE_TABLE))) return rc;
   ZK_ON_DEVICE(device);
   return run_host(device, j, data_host, dtype, outer, length, inner, weights_host, baseline_host, signal_host, iterations_host);
 }
@@ -622,7 +605,7 @@ extern "C" int zk_eels_pls_dev(int device, const void* data_dev, int dtype, int6
                                double* baseline_dev, double* signal_dev, int32_t* iterations_dev, void* hip_stream) {
   const eels_job j = pls_job(mode, order, lam, param, itermax, weights_dev, weights_per_spectrum);
   int rc = check_shape("eels_pls", data_dev, dtype, outer, length, inner, baseline_dev);
-  if (rc || (rc = check_job(j, length, weights_dev != nullptr)) || (rc = check_device(device))) return rc;
+  if (rc || (rc = check_job(j, length, weights_dev != nullptr)) || (rc = zk_check_device(device, ZK_DEVICE_TABLE))) return rc;
   ZK_ON_DEVICE(device);
   return run_dev(device, j, data_dev, dtype, outer, length, inner, baseline_dev, signal_dev, iterations_dev, (hipStream_t)hip_stream);
 }

@@ -1,11 +1,9 @@
 // zk_frames.h -- what zk_register.hip shares with zk_strain.hip (not part of the public ABI): a stack of real frames widened
-// and windowed into a complex float64 field, a cached hipFFT plan bound to a stream for the length of a call, and the staging
-// state of a unit's host-buffer entry points.
+// and windowed into a complex float64 field, and a cached hipFFT plan bound to a stream for the length of a call.  (Both units
+// stage their host-buffer entry points through zk_ring.h.)
 #pragma once
 
 #include <math.h>
-
-#include <mutex>
 
 #include "zk_pickers.h"
 #include "zk_ring.h"
@@ -36,14 +34,10 @@ __global__ __launch_bounds__(256) void widen_kernel(const T* __restrict__ in, co
 }
 
 int launch_widen(int dtype, const void* in, const double* win, int H, int W, cplx* out, long long total, hipStream_t s) {
-  const dim3 grid(blocks_of(total)), block(256);
-  switch (dtype) {
-    case ZK_F32: hipLaunchKernelGGL(widen_kernel<float>, grid, block, 0, s, (const float*)in, win, H, W, out, total); break;
-    case ZK_F64: hipLaunchKernelGGL(widen_kernel<double>, grid, block, 0, s, (const double*)in, win, H, W, out, total); break;
-    case ZK_U8: hipLaunchKernelGGL(widen_kernel<uint8_t>, grid, block, 0, s, (const uint8_t*)in, win, H, W, out, total); break;
-    case ZK_U16: hipLaunchKernelGGL(widen_kernel<uint16_t>, grid, block, 0, s, (const uint16_t*)in, win, H, W, out, total); break;
-    default: hipLaunchKernelGGL(widen_kernel<int16_t>, grid, block, 0, s, (const int16_t*)in, win, H, W, out, total); break;
-  }
+  zk_with_elem(dtype, [&](auto e) {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(widen_kernel<T>, dim3(blocks_of(total)), dim3(256), 0, s, (const T*)in, win, H, W, out, total);
+  });
   ZK_HIP(hipGetLastError());
   return 0;
 }
@@ -64,37 +58,5 @@ struct stream_plan {
     return 0;
   }
 };
-
-bool known_dtype(int d) { return d >= ZK_F32 && d <= ZK_I16; }
-
-int check_device(int device) {
-  const int ndev = zk_device_count();
-  if (ndev < 0) return ndev;
-  if (ndev == 0) return zk_fail(ZK_E_NODEVICE, "no HIP device visible");
-  if (device < 0 || device >= ndev || device >= 64) return zk_fail(ZK_E_BADARG, "device index out of range");
-  return 0;
-}
-
-// the staging of a unit's host entry points: one ring and one stream per device, made at the first call and kept
-struct host_state {
-  std::mutex lock;
-  bool made = false;
-  zk_ring ring;
-  hipStream_t stream = nullptr;
-};
-
-int host_state_make(host_state* h) {
-  if (h->made) return 0;
-  ZK_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  const int rc = zk_ring_create(&h->ring);
-  if (rc) {
-    zk_ring_destroy(&h->ring);
-    (void)hipStreamDestroy(h->stream);
-    h->stream = nullptr;
-    return rc;
-  }
-  h->made = true;
-  return 0;
-}
 
 }  // namespace

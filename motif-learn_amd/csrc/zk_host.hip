@@ -1,12 +1,12 @@
 // zk_host.hip -- the host-buffer entry points of the C ABI (what ZPs.transform calls with NumPy arrays):
 // zk_transform_patches / zk_transform_frame / zk_transform_points / zk_frame_maps / zk_moment_maps / zk_points_maps.
-// Each cuts its job into chunks and sends them through the plan's staging ring; the protocol is zk_ring.h's.
+// Each cuts its job into chunks and sends them through the plan's stage; state and protocol are zk_ring.h's.
 #include <string.h>
 
 #include "zk_ring.h"
 
 struct zk_host_ring {
-  zk_ring ring;
+  zk_stage stage;                          // on the plan's own stream
   void* d_frame = nullptr;                 // whole frame (+ points) of the dense / key-point calls
   size_t frame_cap = 0;
   void* d_raw[ZK_RING_SLOTS] = {};         // narrow inputs (ZK_U8 / U16 / I16) as they arrive, before widening
@@ -53,7 +53,7 @@ size_t chunk_bytes(const zk_plan* p) {
 // ZK_F64, one without a frame H = W = 1, one without a count unit = nullptr.  1: an empty job, nothing to do.
 int check_job(const zk_plan* p, int dtype, int64_t H, int64_t W, const char* unit, int64_t n, bool pointers) {
   if (!p) return zk_fail(ZK_E_BADARG, "null plan");
-  if (dtype < ZK_F32 || dtype > ZK_I16) return zk_fail(ZK_E_BADARG, "dtype must be ZK_F32, ZK_F64, ZK_U8, ZK_U16 or ZK_I16");
+  if (!zk_is_elem(dtype)) return zk_fail(ZK_E_BADARG, "dtype must be ZK_F32, ZK_F64, ZK_U8, ZK_U16 or ZK_I16");
   if (H <= 0 || W <= 0) return zk_fail(ZK_E_BADARG, "bad frame shape");
   if (unit && n < 0) return zk_fail(ZK_E_BADARG, std::string("negative ") + unit + " count");
   if (unit && n == 0) return 1;
@@ -66,7 +66,7 @@ int ring_get(zk_plan* p, zk_host_ring** out) {
   if (!p->ring) {
     p->ring = new (std::nothrow) zk_host_ring();
     if (!p->ring) return zk_fail(ZK_E_NOMEM, "out of host memory");
-    const int rc = zk_ring_create(&p->ring->ring);
+    const int rc = zk_stage_create(&p->ring->stage, p->stream);
     if (rc) {
       zk_host_release(p);
       return rc;
@@ -81,7 +81,7 @@ int ring_get(zk_plan* p, zk_host_ring** out) {
 void zk_host_release(zk_plan* p) {
   zk_host_ring* h = p->ring;
   if (!h) return;
-  zk_ring_destroy(&h->ring);
+  zk_stage_destroy(&h->stage);
   for (int k = 0; k < ZK_RING_SLOTS; ++k)
     if (h->d_raw[k]) (void)hipFree(h->d_raw[k]);
   if (h->d_frame) (void)hipFree(h->d_frame);
@@ -133,7 +133,7 @@ extern "C" int zk_transform_patches(zk_plan* p, const void* patches_host, int dt
   ZK_ON_PLAN_DEVICE(p);
   zk_host_ring* h;
   if ((rc = ring_get(p, &h))) return rc;
-  zk_ring* r = &h->ring;
+  zk_ring* r = &h->stage.ring;
   const int kdt = kernel_dtype(dtype);
   const bool narrow = is_narrow(dtype);
   const size_t px_per = (size_t)p->size * p->size;
@@ -238,7 +238,7 @@ extern "C" int zk_transform_frame(zk_plan* p, const void* image_host, int dtype,
   ZK_ON_PLAN_DEVICE(p);
   zk_host_ring* h;
   if ((rc = ring_get(p, &h))) return rc;
-  zk_ring* r = &h->ring;
+  zk_ring* r = &h->stage.ring;
   if ((rc = frame_up(p, h, image_host, dtype, H, W, 0))) return zk_ring_drain(r, p->stream, rc);
   const size_t row_bytes = (size_t)p->n_poly * W * sizeof(double);
   const zk_chunks band = zk_chunk_plan(chunk_bytes(p), row_bytes, 8, H);  // whole blocks of the dense kernels
@@ -266,7 +266,7 @@ extern "C" int zk_frame_maps(zk_plan* p, const void* image_host, int dtype, int6
   ZK_ON_PLAN_DEVICE(p);
   zk_host_ring* h;
   if ((rc = ring_get(p, &h))) return rc;
-  zk_ring* r = &h->ring;
+  zk_ring* r = &h->stage.ring;
   if ((rc = frame_up(p, h, image_host, dtype, H, W, 0))) return zk_ring_drain(r, p->stream, rc);
   const maps_out o(p, rot_host, abs_host, mirror_host, n_folds);
   const size_t row_bytes = o.unit_bytes() * W;
@@ -307,7 +307,7 @@ extern "C" int zk_frame_align(zk_plan* p, const void* image_host, int dtype, int
   ZK_ON_PLAN_DEVICE(p);
   zk_host_ring* h;
   if ((rc = ring_get(p, &h))) return rc;
-  zk_ring* r = &h->ring;
+  zk_ring* r = &h->stage.ring;
   if ((rc = frame_up(p, h, image_host, dtype, H, W, 0))) return zk_ring_drain(r, p->stream, rc);
   const size_t T = (size_t)n_templates, px_bytes = (2 * T + 1) * sizeof(double) + sizeof(int32_t);
   const zk_chunks band = zk_chunk_plan(chunk_bytes(p), px_bytes * W, 8, n_rows);
@@ -344,7 +344,7 @@ extern "C" int zk_transform_points(zk_plan* p, const void* image_host, int dtype
   ZK_ON_PLAN_DEVICE(p);
   zk_host_ring* h;
   if ((rc = ring_get(p, &h))) return rc;
-  zk_ring* r = &h->ring;
+  zk_ring* r = &h->stage.ring;
   int32_t* d_pts;
   if ((rc = frame_points_up(p, h, image_host, dtype, H, W, points_host, n_points, &d_pts))) return zk_ring_drain(r, p->stream, rc);
   const size_t out_unit = (size_t)p->n_poly * sizeof(double);
@@ -373,7 +373,7 @@ extern "C" int zk_moment_maps(zk_plan* p, const double* moments_host, int64_t n_
   ZK_ON_PLAN_DEVICE(p);
   zk_host_ring* h;
   if ((rc = ring_get(p, &h))) return rc;
-  zk_ring* r = &h->ring;
+  zk_ring* r = &h->stage.ring;
   const maps_out o(p, rot_host, abs_host, mirror_host, n_folds);
   const size_t in_unit = (size_t)p->n_poly * 8, out_unit = o.unit_bytes();
   const zk_chunks ch = zk_chunk_plan(chunk_bytes(p), in_unit + out_unit, 256, n_rows);
@@ -399,7 +399,7 @@ extern "C" int zk_points_maps(zk_plan* p, const void* image_host, int dtype, int
   ZK_ON_PLAN_DEVICE(p);
   zk_host_ring* h;
   if ((rc = ring_get(p, &h))) return rc;
-  zk_ring* r = &h->ring;
+  zk_ring* r = &h->stage.ring;
   int32_t* d_pts;
   if ((rc = frame_points_up(p, h, image_host, dtype, H, W, points_host, n_points, &d_pts))) return zk_ring_drain(r, p->stream, rc);
   const maps_out o(p, rot_host, abs_host, mirror_host, n_folds);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <string>
 #include <vector>
 
@@ -134,9 +135,54 @@ static inline int zk_for_row_bands(int64_t row0, int64_t n_rows, int64_t W, int 
   return 0;
 }
 
-// bytes per element of a ZK_* dtype code
-static inline size_t zk_elem_size(int dtype) {
+// ---- per-device state of the units that keep some (staging, byte knobs): tables of ZK_DEVICE_TABLE entries
+#define ZK_DEVICE_TABLE 64
+
+// Is `device` one this process can run on?  ZK_E_NODEVICE without any, ZK_E_BADARG outside [0, count).  A unit that indexes a
+// per-device table passes table_limit = ZK_DEVICE_TABLE and refuses what lies past it as well; a plan or a synthesis object
+// carries its device with it and passes nothing.  (zk_api.hip)
+int zk_check_device(int device, int table_limit = 0);
+
+// A byte budget per device that a setter may change while calls on other threads read it; 0 = the reader's default.
+struct zk_device_bytes {
+  std::atomic<size_t> v[ZK_DEVICE_TABLE] = {};
+  // `refusal`: the setter's text for a negative value.  No device need be visible: the number is only kept.
+  int set(int device, int64_t bytes, const char* refusal) {
+    if (bytes < 0) return zk_fail(ZK_E_BADARG, refusal);
+    if (device < 0 || device >= ZK_DEVICE_TABLE) return zk_fail(ZK_E_BADARG, "device index out of range");
+    v[device].store((size_t)bytes);
+    return 0;
+  }
+  size_t get(int device, size_t dflt) const {  // `device` has passed zk_check_device(device, ZK_DEVICE_TABLE)
+    const size_t set = v[device].load();
+    return set ? set : dflt;
+  }
+};
+
+// ---- element types of the ZK_* dtype codes
+static inline size_t zk_elem_size(int dtype) {  // bytes per element
   return dtype == ZK_F64 ? 8 : dtype == ZK_F32 ? 4 : dtype == ZK_U8 ? 1 : 2;
+}
+
+static inline bool zk_is_elem(int dtype) { return dtype >= ZK_F32 && dtype <= ZK_I16; }
+
+template <typename T>
+struct zk_elem {
+  using type = T;
+};
+
+// f(zk_elem<T>{}) for the T of `dtype`, and what it returns: the one place that maps a code to a type.  Callers write
+//   zk_with_elem(dtype, [&](auto e) { return run_typed<typename decltype(e)::type>(...); });
+// and have refused other codes with zk_is_elem before (int16_t is the default arm).
+template <class F>
+static inline auto zk_with_elem(int dtype, F&& f) -> decltype(f(zk_elem<float>{})) {
+  switch (dtype) {
+    case ZK_F32: return f(zk_elem<float>{});
+    case ZK_F64: return f(zk_elem<double>{});
+    case ZK_U8: return f(zk_elem<uint8_t>{});
+    case ZK_U16: return f(zk_elem<uint16_t>{});
+    default: return f(zk_elem<int16_t>{});
+  }
 }
 
 // grow-only device buffer

@@ -26,6 +26,7 @@
 #include <math.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -299,13 +300,9 @@ int local_max_core(const void* img, int dtype, int H, int W, double r, int has_t
   temp_store tmp;
   int rc;
   if ((rc = d_mm.alloc(16)) || (rc = d_flag.alloc((size_t)npx)) || (rc = d_count.alloc(8))) return rc;
-  switch (dtype) {
-    case ZK_F32: rc = launch_front<float>(img, H, W, d_mm.as<unsigned long long>(), has_threshold, threshold, d_flag.as<uint8_t>(), s); break;
-    case ZK_F64: rc = launch_front<double>(img, H, W, d_mm.as<unsigned long long>(), has_threshold, threshold, d_flag.as<uint8_t>(), s); break;
-    case ZK_U8: rc = launch_front<uint8_t>(img, H, W, d_mm.as<unsigned long long>(), has_threshold, threshold, d_flag.as<uint8_t>(), s); break;
-    case ZK_U16: rc = launch_front<uint16_t>(img, H, W, d_mm.as<unsigned long long>(), has_threshold, threshold, d_flag.as<uint8_t>(), s); break;
-    default: rc = launch_front<int16_t>(img, H, W, d_mm.as<unsigned long long>(), has_threshold, threshold, d_flag.as<uint8_t>(), s); break;
-  }
+  rc = zk_with_elem(dtype, [&](auto e) {
+    return launch_front<typename decltype(e)::type>(img, H, W, d_mm.as<unsigned long long>(), has_threshold, threshold, d_flag.as<uint8_t>(), s);
+  });
   if (rc) return rc;
 
   // raster-ordered candidate list (the count crosses to the host: it sizes everything after)
@@ -338,13 +335,11 @@ int local_max_core(const void* img, int dtype, int H, int W, double r, int has_t
   if ((rc = d_keys.alloc((size_t)n * 2 * key_size)) || (rc = d_sorted.alloc((size_t)n * 4)) || (rc = d_rank.alloc((size_t)npx * 4)) ||
       (rc = d_state.alloc((size_t)n)) || (rc = d_temp2.alloc(temp2_bytes)))
     return rc;
-  switch (dtype) {
-    case ZK_F32: rc = sort_candidates<float, unsigned int>(img, d_pix.as<int32_t>(), n, d_sorted.as<int32_t>(), d_keys.p, d_temp2.p, sort_bytes, s); break;
-    case ZK_F64: rc = sort_candidates<double, unsigned long long>(img, d_pix.as<int32_t>(), n, d_sorted.as<int32_t>(), d_keys.p, d_temp2.p, sort_bytes, s); break;
-    case ZK_U8: rc = sort_candidates<uint8_t, unsigned int>(img, d_pix.as<int32_t>(), n, d_sorted.as<int32_t>(), d_keys.p, d_temp2.p, sort_bytes, s); break;
-    case ZK_U16: rc = sort_candidates<uint16_t, unsigned int>(img, d_pix.as<int32_t>(), n, d_sorted.as<int32_t>(), d_keys.p, d_temp2.p, sort_bytes, s); break;
-    default: rc = sort_candidates<int16_t, unsigned int>(img, d_pix.as<int32_t>(), n, d_sorted.as<int32_t>(), d_keys.p, d_temp2.p, sort_bytes, s); break;
-  }
+  rc = zk_with_elem(dtype, [&](auto e) {
+    using T = typename decltype(e)::type;  // float64 pixels sort by 64-bit keys, every other format by 32-bit ones (key_size above)
+    using K = typename std::conditional<std::is_same<T, double>::value, unsigned long long, unsigned int>::type;
+    return sort_candidates<T, K>(img, d_pix.as<int32_t>(), n, d_sorted.as<int32_t>(), d_keys.p, d_temp2.p, sort_bytes, s);
+  });
   if (rc) return rc;
   ZK_HIP(hipMemsetAsync(d_rank.p, 0xff, (size_t)npx * 4, s));
   hipLaunchKernelGGL(rank_kernel, dim3(blocks_of(n)), dim3(256), 0, s, d_sorted.as<int32_t>(), n, d_rank.as<int32_t>(), d_state.as<uint8_t>());
@@ -413,7 +408,7 @@ int local_max_core(const void* img, int dtype, int H, int W, double r, int has_t
 }
 
 int check_args(int dtype, int64_t H, int64_t W, const void* img, double r, int64_t capacity, const void* out, const int64_t* n_found) {
-  if (dtype < ZK_F32 || dtype > ZK_I16) return zk_fail(ZK_E_BADARG, "dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
+  if (!zk_is_elem(dtype)) return zk_fail(ZK_E_BADARG, "dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
   if (H <= 0 || W <= 0 || H * W >= ((int64_t)1 << 31)) return zk_fail(ZK_E_BADARG, "bad image shape (needs 0 < height * width < 2^31)");
   if (!img || !n_found) return zk_fail(ZK_E_BADARG, "null pointer");
   if (!(r >= 0.0) || !isfinite(r)) return zk_fail(ZK_E_BADARG, "min_distance must be a finite number >= 0");

@@ -25,7 +25,6 @@
 #include <math.h>
 
 #include <algorithm>
-#include <mutex>
 
 #include "zk_frames.h"
 
@@ -38,7 +37,6 @@ constexpr int GA_PITCH = GT + 1;                       // complex numbers betwee
 constexpr size_t FIELD_BYTES = (size_t)1 << 30;        // the two complex fields of one run
 constexpr size_t TABLE_BYTES = (size_t)1 << 30;        // twiddle tables, T and C of one run
 constexpr size_t MEAN_BUDGET = (size_t)256 << 20;      // input + output of one chunk of zk_stack_mean
-constexpr size_t RING_KEEP = (size_t)64 << 20;         // staging kept between host calls
 
 struct partial {
   double v;
@@ -335,7 +333,7 @@ struct job {
 };
 
 int check_job(const job& j, const void* stack, const void* ref, const void* shifts, const void* peak) {
-  if (!known_dtype(j.dtype)) return zk_fail(ZK_E_BADARG, "register_shifts: dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
+  if (!zk_is_elem(j.dtype)) return zk_fail(ZK_E_BADARG, "register_shifts: dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
   if (j.B < 1 || j.B >= ((int64_t)1 << 31) || j.H < 2 || j.W < 2 || j.H > 16384 || j.W > 16384)
     return zk_fail(ZK_E_BADARG, "register_shifts: needs 1 .. 2^31 - 1 frames of 2 x 2 .. 16384 x 16384 samples");
   if (j.upsample < 1 || j.upsample > 1000) return zk_fail(ZK_E_BADARG, "register_shifts: upsample must be in 1 .. 1000");
@@ -348,7 +346,7 @@ int check_job(const job& j, const void* stack, const void* ref, const void* shif
     if (j.ref_index < 0 || j.ref_index >= j.B) return zk_fail(ZK_E_BADARG, "register_shifts: the reference index is outside the stack");
   } else if (j.ref_mode == ZK_REGISTER_REF_FRAME) {
     if (!ref) return zk_fail(ZK_E_BADARG, "register_shifts: null pointer");
-    if (!known_dtype(j.ref_dtype)) return zk_fail(ZK_E_BADARG, "register_shifts: ref_dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
+    if (!zk_is_elem(j.ref_dtype)) return zk_fail(ZK_E_BADARG, "register_shifts: ref_dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
   } else if (j.ref_mode != ZK_REGISTER_REF_PREVIOUS) {
     return zk_fail(ZK_E_BADARG, "register_shifts: ref_mode must be one of ZK_REGISTER_REF_*");
   }
@@ -467,27 +465,23 @@ int run_frames(state& st, const job& j, const void* frames_dev, int64_t first, i
 }
 
 int launch_mean(int dtype, const void* in, int64_t B, long long pitch, long long count, double* out, hipStream_t s) {
-  const dim3 grid(blocks_of(count)), block(256);
-  switch (dtype) {
-    case ZK_F32: hipLaunchKernelGGL(mean_kernel<float>, grid, block, 0, s, (const float*)in, (long long)B, pitch, count, out); break;
-    case ZK_F64: hipLaunchKernelGGL(mean_kernel<double>, grid, block, 0, s, (const double*)in, (long long)B, pitch, count, out); break;
-    case ZK_U8: hipLaunchKernelGGL(mean_kernel<uint8_t>, grid, block, 0, s, (const uint8_t*)in, (long long)B, pitch, count, out); break;
-    case ZK_U16: hipLaunchKernelGGL(mean_kernel<uint16_t>, grid, block, 0, s, (const uint16_t*)in, (long long)B, pitch, count, out); break;
-    default: hipLaunchKernelGGL(mean_kernel<int16_t>, grid, block, 0, s, (const int16_t*)in, (long long)B, pitch, count, out); break;
-  }
+  zk_with_elem(dtype, [&](auto e) {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(mean_kernel<T>, dim3(blocks_of(count)), dim3(256), 0, s, (const T*)in, (long long)B, pitch, count, out);
+  });
   ZK_HIP(hipGetLastError());
   return 0;
 }
 
 int check_mean(const void* stack, int dtype, int64_t B, int64_t H, int64_t W, const void* out) {
-  if (!known_dtype(dtype)) return zk_fail(ZK_E_BADARG, "stack_mean: dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
+  if (!zk_is_elem(dtype)) return zk_fail(ZK_E_BADARG, "stack_mean: dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
   if (B < 1 || H < 1 || W < 1 || H > ((int64_t)1 << 21) || W > ((int64_t)1 << 21) || B >= ((int64_t)1 << 31) || B * H * W >= ((int64_t)1 << 40))
     return zk_fail(ZK_E_BADARG, "stack_mean: needs B, H, W positive, H, W <= 2^21, B < 2^31 and fewer than 2^40 samples");
   if (!stack || !out) return zk_fail(ZK_E_BADARG, "stack_mean: null pointer");
   return 0;
 }
 
-host_state g_host[64];  // the staging of the host entry points (zk_frames.h)
+zk_device_stage g_host[ZK_DEVICE_TABLE];  // the staging of the host entry points (zk_ring.h)
 
 }  // namespace
 
@@ -497,7 +491,7 @@ extern "C" int zk_register_shifts_dev(int device, const void* stack_dev, int dty
                                       int window, double* shifts_dev, double* peak_dev, double* corr_dev, double* up_dev, void* hip_stream) {
   const job j{dtype, B, H, W, ref_mode, ref_index, ref_dtype, upsample, max_shift, normalization, window};
   int rc = check_job(j, stack_dev, ref_dev, shifts_dev, peak_dev);
-  if (rc || (rc = check_device(device)) || (rc = zk_fft_load())) return rc;
+  if (rc || (rc = zk_check_device(device, ZK_DEVICE_TABLE)) || (rc = zk_fft_load())) return rc;
   ZK_ON_DEVICE(device);
   hipStream_t s = (hipStream_t)hip_stream;
   const size_t frame_bytes = j.per() * zk_elem_size(dtype);
@@ -520,11 +514,11 @@ extern "C" int zk_register_shifts(int device, const void* stack_host, int dtype,
                                   double* shifts_host, double* peak_host, double* corr_host, double* up_host) {
   const job j{dtype, B, H, W, ref_mode, ref_index, ref_dtype, upsample, max_shift, normalization, window};
   int rc = check_job(j, stack_host, ref_host, shifts_host, peak_host);
-  if (rc || (rc = check_device(device)) || (rc = zk_fft_load())) return rc;
+  if (rc || (rc = zk_check_device(device, ZK_DEVICE_TABLE)) || (rc = zk_fft_load())) return rc;
   ZK_ON_DEVICE(device);
-  host_state* h = &g_host[device];
-  std::lock_guard<std::mutex> guard(h->lock);
-  if ((rc = host_state_make(h))) return rc;
+  std::lock_guard<std::mutex> guard(g_host[device].lock);
+  zk_stage* h = &g_host[device].stage;
+  if ((rc = zk_stage_create(h))) return rc;
   zk_ring* r = &h->ring;
   const size_t per = j.per(), up_per = j.up_per(), in_unit = per * zk_elem_size(dtype);
   const bool by_index = ref_mode == ZK_REGISTER_REF_INDEX;
@@ -561,7 +555,7 @@ extern "C" int zk_register_shifts(int device, const void* stack_host, int dtype,
   } else {
     (void)hipStreamSynchronize(h->stream);
   }
-  if (zk_ring_bytes(r) > RING_KEEP) zk_ring_free_slots(r);
+  zk_stage_trim(h, ZK_STAGE_KEEP_STACKS);
   if (rc) return rc;  // zk_ring_run has drained every stream: the fields may go
   if ((rc = d_res.download(shifts_host, shift_bytes))) return rc;
   ZK_HIP(hipMemcpy(peak_host, d_res.as<double>() + 2 * B, peak_bytes, hipMemcpyDeviceToHost));
@@ -570,18 +564,18 @@ extern "C" int zk_register_shifts(int device, const void* stack_host, int dtype,
 
 extern "C" int zk_stack_mean_dev(int device, const void* stack_dev, int dtype, int64_t B, int64_t H, int64_t W, double* out_dev, void* hip_stream) {
   int rc = check_mean(stack_dev, dtype, B, H, W, out_dev);
-  if (rc || (rc = check_device(device))) return rc;
+  if (rc || (rc = zk_check_device(device, ZK_DEVICE_TABLE))) return rc;
   ZK_ON_DEVICE(device);
   return launch_mean(dtype, stack_dev, B, (long long)H * W, (long long)H * W, out_dev, (hipStream_t)hip_stream);
 }
 
 extern "C" int zk_stack_mean(int device, const void* stack_host, int dtype, int64_t B, int64_t H, int64_t W, double* out_host) {
   int rc = check_mean(stack_host, dtype, B, H, W, out_host);
-  if (rc || (rc = check_device(device))) return rc;
+  if (rc || (rc = zk_check_device(device, ZK_DEVICE_TABLE))) return rc;
   ZK_ON_DEVICE(device);
-  host_state* h = &g_host[device];
-  std::lock_guard<std::mutex> guard(h->lock);
-  if ((rc = host_state_make(h))) return rc;
+  std::lock_guard<std::mutex> guard(g_host[device].lock);
+  zk_stage* h = &g_host[device].stage;
+  if ((rc = zk_stage_create(h))) return rc;
   zk_ring* r = &h->ring;
   const size_t es = zk_elem_size(dtype);
   const int64_t per = H * W;
@@ -596,6 +590,6 @@ extern "C" int zk_stack_mean(int device, const void* stack_host, int dtype, int6
         return e ? e : launch_mean(dtype, r->d_in[slot], B, (long long)ch.chunk, (long long)ch.count(c), (double*)r->d_out[slot], h->stream);
       },
       [&](int64_t c, int slot) -> int { return zk_ring_down(r, slot, out_host + ch.first(c), (size_t)ch.count(c) * 8); });
-  if (zk_ring_bytes(r) > RING_KEEP) zk_ring_free_slots(r);
+  zk_stage_trim(h, ZK_STAGE_KEEP_STACKS);
   return rc;
 }

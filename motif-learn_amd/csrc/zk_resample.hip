@@ -11,7 +11,7 @@
 // goes in runs of whole frames, and since no kernel looks across frames the run length cannot show in the result.
 // Nothing here is fused by the compiler (-ffp-contract=off, csrc/Makefile): the tap sums are the reference's expressions.
 #include <algorithm>
-#include <mutex>
+#include <type_traits>
 
 #include "zk_interp.h"
 #include "zk_ring.h"
@@ -25,9 +25,8 @@ constexpr int ROW_SPAN = ROW_SEG + 2 * ZK_SPLINE_WARMUP;      // columns it hold
 constexpr int ROW_PITCH = ROW_SPAN + 1;                       // odd: the lanes of the filter pass spread over the banks
 constexpr int COL_SEG = 128;                                  // rows of a column segment
 constexpr size_t DEFAULT_BUDGET = (size_t)256 << 20;          // input + output + scratch of one run
-constexpr size_t RING_KEEP = (size_t)64 << 20;                // staging kept between host calls
 
-size_t g_budget[64] = {};
+zk_device_bytes g_budget;  // zk_scan_resample_set_chunk; 0: DEFAULT_BUDGET
 
 // ---------------------------------------------------------------------------------------------------------------------
 // order 3: the prefilter
@@ -130,7 +129,7 @@ struct job {
 };
 
 int check_job(const job& j, const void* stack, const void* dx, const void* dy, const void* out) {
-  if (j.dtype < ZK_F32 || j.dtype > ZK_I16) return zk_fail(ZK_E_BADARG, "scan_resample: dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
+  if (!zk_is_elem(j.dtype)) return zk_fail(ZK_E_BADARG, "scan_resample: dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
   if (j.Z < 1 || j.H < 1 || j.W < 1) return zk_fail(ZK_E_BADARG, "scan_resample: Z, H and W must be positive");
   // grid.y of the row prefilter carries H / 64 and grid.x of the gather H * ceil(W / 256)
   if (j.H > ((int64_t)1 << 21) || j.W > ((int64_t)1 << 21) || j.Z >= ((int64_t)1 << 31) || j.Z * j.H * j.W >= ((int64_t)1 << 40) ||
@@ -144,15 +143,7 @@ int check_job(const job& j, const void* stack, const void* dx, const void* dy, c
   return 0;
 }
 
-int check_device(int device) {
-  const int ndev = zk_device_count();
-  if (ndev < 0) return ndev;
-  if (ndev == 0) return zk_fail(ZK_E_NODEVICE, "no HIP device visible");
-  if (device < 0 || device >= ndev || device >= 64) return zk_fail(ZK_E_BADARG, "device index out of range");
-  return 0;
-}
-
-size_t budget_of(int device) { return g_budget[device] ? g_budget[device] : DEFAULT_BUDGET; }
+size_t budget_of(int device) { return g_budget.get(device, DEFAULT_BUDGET); }
 
 // frames per run: what `bytes` holds at `unit` bytes a frame, at least one, at most the launch's grid.y
 int64_t frames_per_run(size_t bytes, size_t unit, int64_t Z) {
@@ -189,46 +180,20 @@ int run_typed(const job& j, const void* in_v, const double* dx, const double* dy
 }
 
 int run_dev(const job& j, const void* in, const double* dx, const double* dy, void* out, int64_t nz, int64_t per, double* scratch, hipStream_t s) {
-  switch (j.dtype) {
-    case ZK_F32: return run_typed<float, float>(j, in, dx, dy, out, nz, per, scratch, s);
-    case ZK_F64: return run_typed<double, double>(j, in, dx, dy, out, nz, per, scratch, s);
-    case ZK_U8: return run_typed<uint8_t, double>(j, in, dx, dy, out, nz, per, scratch, s);
-    case ZK_U16: return run_typed<uint16_t, double>(j, in, dx, dy, out, nz, per, scratch, s);
-    default: return run_typed<int16_t, double>(j, in, dx, dy, out, nz, per, scratch, s);
-  }
+  return zk_with_elem(j.dtype, [&](auto e) {
+    using T = typename decltype(e)::type;  // float32 comes back as float32, every other format as float64
+    using TOUT = typename std::conditional<std::is_same<T, float>::value, float, double>::type;
+    return run_typed<T, TOUT>(j, in, dx, dy, out, nz, per, scratch, s);
+  });
 }
 
-// the staging of the host entry point: one ring and one stream per device, made at the first call and kept
-struct host_state {
-  std::mutex lock;
-  bool made = false;
-  zk_ring ring;
-  hipStream_t stream = nullptr;
-};
-host_state g_host[64];
-
-int host_state_make(host_state* h) {
-  if (h->made) return 0;
-  ZK_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  const int rc = zk_ring_create(&h->ring);
-  if (rc) {
-    zk_ring_destroy(&h->ring);
-    (void)hipStreamDestroy(h->stream);
-    h->stream = nullptr;
-    return rc;
-  }
-  h->made = true;
-  return 0;
-}
+zk_device_stage g_host[ZK_DEVICE_TABLE];  // the staging of the host entry point (zk_ring.h)
 
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------
 extern "C" int zk_scan_resample_set_chunk(int device, int64_t budget_bytes) {
-  if (budget_bytes < 0) return zk_fail(ZK_E_BADARG, "bad arguments");
-  if (device < 0 || device >= 64) return zk_fail(ZK_E_BADARG, "device index out of range");
-  g_budget[device] = (size_t)budget_bytes;
-  return 0;
+  return g_budget.set(device, budget_bytes, "bad arguments");
 }
 
 extern "C" int zk_scan_resample_dev(int device, const void* stack_dev, int dtype, int64_t Z, int64_t H, int64_t W, const double* dx_dev,
@@ -239,7 +204,7 @@ extern "C" int zk_scan_resample_dev(int device, const void* stack_dev, int dtype
   if (rc) return rc;
   if (scratch_dev && (scratch_bytes < 0 || (size_t)scratch_bytes < j.scratch_frame()))
     return zk_fail(ZK_E_BADARG, "scan_resample: the scratch must hold one frame's two float64 planes (16 H W bytes at order 3)");
-  if ((rc = check_device(device))) return rc;
+  if ((rc = zk_check_device(device, ZK_DEVICE_TABLE))) return rc;
   ZK_ON_DEVICE(device);
   hipStream_t s = (hipStream_t)hip_stream;
   if (order != 3 || scratch_dev) {  // nothing of the library's own to release: enqueued and left running
@@ -258,11 +223,11 @@ extern "C" int zk_scan_resample(int device, const void* stack_host, int dtype, i
                                 const double* dy_host, int order, int mode, void* out_host) {
   const job j{dtype, order, mode, Z, H, W};
   int rc = check_job(j, stack_host, dx_host, dy_host, out_host);
-  if (rc || (rc = check_device(device))) return rc;
+  if (rc || (rc = zk_check_device(device, ZK_DEVICE_TABLE))) return rc;
   ZK_ON_DEVICE(device);
-  host_state* h = &g_host[device];
-  std::lock_guard<std::mutex> guard(h->lock);
-  if ((rc = host_state_make(h))) return rc;
+  std::lock_guard<std::mutex> guard(g_host[device].lock);
+  zk_stage* h = &g_host[device].stage;
+  if ((rc = zk_stage_create(h))) return rc;
   zk_ring* r = &h->ring;
   const size_t in_unit = j.in_frame(), out_unit = j.out_frame();
   const zk_chunks ch = zk_chunk_plan(budget_of(device), in_unit + out_unit + j.scratch_frame(), 1, Z);
@@ -283,6 +248,6 @@ extern "C" int zk_scan_resample(int device, const void* stack_host, int dtype, i
                            h->stream);
       },
       [&](int64_t c, int slot) -> int { return zk_ring_down(r, slot, (char*)out_host + (size_t)ch.first(c) * out_unit, (size_t)ch.count(c) * out_unit); });
-  if (zk_ring_bytes(r) > RING_KEEP) zk_ring_free_slots(r);
+  zk_stage_trim(h, ZK_STAGE_KEEP_STACKS);
   return rc;  // zk_ring_run has drained every stream: shifts and scratch may go
 }

@@ -1,5 +1,6 @@
-// zk_ring.h -- the staging protocol of the NumPy-in / NumPy-out calls: the host-buffer entry points of a plan (zk_host.hip) and
-// zk_synth_apply (zk_synth.hip).
+// zk_ring.h -- the staging of the NumPy-in / NumPy-out calls, for every unit that has them (zk_host, zk_synth, zk_align,
+// zk_resample, zk_register, zk_strain): the ring and its protocol, and zk_stage, the state a unit keeps for it -- its kernel
+// stream, the ring, and how much of the ring stays on the device between calls.
 //
 // A job is cut into chunks of at most `budget` bytes of input + output (default 256 MiB); chunk c goes
 //     H2D on the ring's copy-in stream  ->  kernel on the caller's stream  ->  D2H on the ring's copy-out stream
@@ -12,6 +13,8 @@
 // link speed and fully asynchronously; pageable arrays go through the runtime's own staging, which blocks
 // the calling thread per copy (the kernel of the chunk before still overlaps with it).
 #pragma once
+
+#include <mutex>
 
 #include "zk_internal.h"
 
@@ -69,6 +72,52 @@ static inline void zk_ring_destroy(zk_ring* r) {
   if (r->s_in) (void)hipStreamDestroy(r->s_in);
   if (r->s_out) (void)hipStreamDestroy(r->s_out);
   *r = zk_ring();
+}
+
+// The staging state of a unit's host-buffer entry points: the stream their kernels run on and the ring.  A plan lends its own
+// stream (`kernel`); every other owner (a synthesis object, the per-device state of zk_align / zk_resample / zk_register /
+// zk_strain) has the stage make a non-blocking one, which then goes with it.
+struct zk_stage {
+  hipStream_t stream = nullptr;
+  bool own_stream = false, made = false;
+  zk_ring ring;
+};
+
+static inline void zk_stage_destroy(zk_stage* st) {
+  zk_ring_destroy(&st->ring);
+  if (st->own_stream && st->stream) (void)hipStreamDestroy(st->stream);
+  *st = zk_stage();
+}
+
+// the stream, then the ring; nothing on a stage that is made already, and nothing is left of one that could not be
+static inline int zk_stage_create(zk_stage* st, hipStream_t kernel = nullptr) {
+  if (st->made) return 0;
+  st->stream = kernel;
+  st->own_stream = !kernel;
+  if (!kernel) ZK_HIP(hipStreamCreateWithFlags(&st->stream, hipStreamNonBlocking));
+  const int rc = zk_ring_create(&st->ring);
+  if (rc) {
+    zk_stage_destroy(st);
+    return rc;
+  }
+  st->made = true;
+  return 0;
+}
+
+// a unit whose host entry points take a device index keeps a table of these: a stage per device, made at the first call there
+// and kept, one call at a time
+struct zk_device_stage {
+  std::mutex lock;
+  zk_stage stage;
+};
+
+// What a stage keeps on the device between calls: slots of up to `keep_bytes` stay (repeated small calls allocate nothing), the
+// slots of a larger job, up to three chunks, go back at once.  No job may be in flight.
+constexpr size_t ZK_STAGE_KEEP_STACKS = (size_t)64 << 20;  // per device: zk_resample, zk_register, zk_strain
+constexpr size_t ZK_STAGE_KEEP_ROWS = (size_t)32 << 20;    // zk_align, and per object in zk_synth: callers hold several at a time
+
+static inline void zk_stage_trim(zk_stage* st, size_t keep_bytes) {
+  if (zk_ring_bytes(&st->ring) > keep_bytes) zk_ring_free_slots(&st->ring);
 }
 
 // The chunks of a job of n units (patches, points, rows) of `unit` bytes each, input + output: as many units as the budget

@@ -22,7 +22,6 @@
 // Frames go in runs whose three complex fields stay under RUN_BYTES (zk_gpa_set_run_bytes: another budget); no kernel looks
 // across frames, so a frame's numbers do not depend on the run length.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 
 #include "zk_frames.h"
@@ -31,7 +30,6 @@ namespace {
 
 constexpr int RED_PER_BLOCK = 4096;                // reference pixels per 256-thread block of the reduction
 constexpr size_t RUN_BYTES = (size_t)1 << 30;      // the spectrum and the two planes of one run
-constexpr size_t RING_KEEP = (size_t)64 << 20;     // staging kept between host calls
 constexpr int MAX_RUN = 32767;                     // 2 n planes are the y extent of a grid
 
 // what the kernels know about a call; [k]: the Bragg vector, [a]: 0 = y, 1 = x
@@ -196,7 +194,7 @@ __global__ __launch_bounds__(256) void strain_kernel(const cplx* __restrict__ Hk
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-std::atomic<size_t> g_run_bytes[64];  // 0: RUN_BYTES
+zk_device_bytes g_run_bytes;  // zk_gpa_set_run_bytes; 0: RUN_BYTES
 
 struct job {
   int dtype;
@@ -217,7 +215,7 @@ cplx unit(double turns) {
 // everything but the device and the output pointers; fills j
 int check_job(job& j, const void* stack, int dtype, int64_t B, int64_t H, int64_t W, const double* g, double sigma, int window, const int64_t* ref,
               const void* maps, const void* amp, const void* g_out) {
-  if (!known_dtype(dtype)) return zk_fail(ZK_E_BADARG, "gpa: dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
+  if (!zk_is_elem(dtype)) return zk_fail(ZK_E_BADARG, "gpa: dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
   if (B < 1 || B >= ((int64_t)1 << 31) || H < 4 || W < 4 || H > 16384 || W > 16384)
     return zk_fail(ZK_E_BADARG, "gpa: needs 1 .. 2^31 - 1 frames of 4 x 4 .. 16384 x 16384 samples");
   if (window != ZK_GPA_WINDOW_NONE && window != ZK_GPA_WINDOW_HANN) return zk_fail(ZK_E_BADARG, "gpa: window must be one of ZK_GPA_WINDOW_*");
@@ -255,8 +253,7 @@ int check_job(job& j, const void* stack, int dtype, int64_t B, int64_t H, int64_
 inline int parts_of(long long n) { return (int)((n + RED_PER_BLOCK - 1) / RED_PER_BLOCK); }
 
 int run_length(const job& j, int device) {
-  const size_t set = g_run_bytes[device].load(), budget = set ? set : RUN_BYTES;
-  const int64_t n = std::max<int64_t>(1, (int64_t)(budget / (j.per() * 48)));
+  const int64_t n = std::max<int64_t>(1, (int64_t)(g_run_bytes.get(device, RUN_BYTES) / (j.per() * 48)));
   return (int)std::min<int64_t>(std::min<int64_t>(n, j.B), MAX_RUN);
 }
 
@@ -318,16 +315,13 @@ int run_frames(state& st, const job& j, const void* frames_dev, int n, double* m
   return 0;
 }
 
-host_state g_host[64];  // the staging of the host entry point (zk_frames.h)
+zk_device_stage g_host[ZK_DEVICE_TABLE];  // the staging of the host entry point (zk_ring.h)
 
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------
 extern "C" int zk_gpa_set_run_bytes(int device, int64_t bytes) {
-  if (bytes < 0) return zk_fail(ZK_E_BADARG, "gpa_set_run_bytes: bytes must be >= 0 (0: the default)");
-  if (device < 0 || device >= 64) return zk_fail(ZK_E_BADARG, "device index out of range");
-  g_run_bytes[device].store((size_t)bytes);
-  return 0;
+  return g_run_bytes.set(device, bytes, "gpa_set_run_bytes: bytes must be >= 0 (0: the default)");
 }
 
 extern "C" int zk_gpa_dev(int device, const void* stack_dev, int dtype, int64_t B, int64_t H, int64_t W, const double* g, double sigma, int window,
@@ -335,7 +329,7 @@ extern "C" int zk_gpa_dev(int device, const void* stack_dev, int dtype, int64_t 
                           void* hip_stream) {
   job j;
   int rc = check_job(j, stack_dev, dtype, B, H, W, g, sigma, window, reference, maps_dev, amp_dev, g_out_dev);
-  if (rc || (rc = check_device(device)) || (rc = zk_fft_load())) return rc;
+  if (rc || (rc = zk_check_device(device, ZK_DEVICE_TABLE)) || (rc = zk_fft_load())) return rc;
   ZK_ON_DEVICE(device);
   hipStream_t s = (hipStream_t)hip_stream;
   const size_t per = j.per(), frame_bytes = per * zk_elem_size(dtype);
@@ -357,11 +351,11 @@ extern "C" int zk_gpa(int device, const void* stack_host, int dtype, int64_t B, 
                       const int64_t* reference, double* maps_host, double* amp_host, double* g_out_host, double* phase_host, void* planes_host) {
   job j;
   int rc = check_job(j, stack_host, dtype, B, H, W, g, sigma, window, reference, maps_host, amp_host, g_out_host);
-  if (rc || (rc = check_device(device)) || (rc = zk_fft_load())) return rc;
+  if (rc || (rc = zk_check_device(device, ZK_DEVICE_TABLE)) || (rc = zk_fft_load())) return rc;
   ZK_ON_DEVICE(device);
-  host_state* h = &g_host[device];
-  std::lock_guard<std::mutex> guard(h->lock);
-  if ((rc = host_state_make(h))) return rc;
+  std::lock_guard<std::mutex> guard(g_host[device].lock);
+  zk_stage* h = &g_host[device].stage;
+  if ((rc = zk_stage_create(h))) return rc;
   zk_ring* r = &h->ring;
   const size_t per = j.per(), in_unit = per * zk_elem_size(dtype);
   // a frame's share of a slot's output, in doubles per pixel: four maps, two amplitudes, two phases, two complex planes
@@ -396,7 +390,7 @@ extern "C" int zk_gpa(int device, const void* stack_host, int dtype, int64_t B, 
   } else {
     (void)hipStreamSynchronize(h->stream);
   }
-  if (zk_ring_bytes(r) > RING_KEEP) zk_ring_free_slots(r);
+  zk_stage_trim(h, ZK_STAGE_KEEP_STACKS);
   if (rc) return rc;  // zk_ring_run has drained every stream: the fields may go
   return d_g.download(g_out_host, (size_t)B * 32);
 }

@@ -24,7 +24,6 @@
 #define ZK_SYNTH_COLS 256
 #define ZK_SYNTH_KC 96                    // coefficients of a row held in LDS at a time
 #define ZK_SYNTH_PITCH (ZK_SYNTH_KC + 2)  // doubles; pitch = 2 mod 32: the 32 lanes (i, k < 2) of a half-wave read 32 different bank pairs
-#define ZK_SYNTH_KEEP_BYTES ((size_t)32 << 20)  // device slots an object keeps between host-variant calls
 
 struct zk_synth {
   int device = 0;
@@ -33,8 +32,7 @@ struct zk_synth {
   int64_t n_pixels = 0;
   double* d_table = nullptr;  // (p_pad, n_pixels)
   size_t host_chunk = 0;      // bytes of coefficients + output per chunk of the host variant; 0 = default
-  hipStream_t stream = nullptr;  // kernels of the host variant
-  zk_ring ring;                  // its staging (zk_ring.h): coefficients up, patches down
+  zk_stage stage;             // the host variant (zk_ring.h): its kernel stream; coefficients up, patches down
 };
 
 namespace {
@@ -144,9 +142,8 @@ int check_apply(const zk_synth* s, const void* coeffs, int64_t n_rows, int out_d
 }
 
 void release(zk_synth* s) {
-  zk_ring_destroy(&s->ring);
+  zk_stage_destroy(&s->stage);
   if (s->d_table) (void)hipFree(s->d_table);
-  if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
 
@@ -155,8 +152,7 @@ int build(zk_synth* s, const double* table_host) {
   ZK_HIP(hipMalloc((void**)&s->d_table, all));
   ZK_HIP(hipMemcpy(s->d_table, table_host, live, hipMemcpyHostToDevice));
   if (all > live) ZK_HIP(hipMemset((char*)s->d_table + live, 0, all - live));
-  ZK_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  const int rc = zk_ring_create(&s->ring);
+  const int rc = zk_stage_create(&s->stage);
   if (rc) return rc;
   ZK_HIP(hipDeviceSynchronize());  // the table is in place before any stream of any caller reads it
   return 0;
@@ -170,10 +166,8 @@ extern "C" int zk_synth_create(int device, int n_funcs, int64_t n_pixels, const 
   if (n_funcs < 1 || n_funcs > 4096) return zk_fail(ZK_E_BADARG, "n_funcs must be between 1 and 4096");
   if (n_pixels < 1 || n_pixels > ((int64_t)1 << 24)) return zk_fail(ZK_E_BADARG, "n_pixels must be between 1 and 2^24");
   if (!table_host) return zk_fail(ZK_E_BADARG, "null table pointer");
-  const int ndev = zk_device_count();
-  if (ndev < 0) return ndev;
-  if (ndev == 0) return zk_fail(ZK_E_NODEVICE, "no HIP device visible");
-  if (device < 0 || device >= ndev) return zk_fail(ZK_E_BADARG, "device index out of range");
+  int rc = zk_check_device(device);
+  if (rc) return rc;
   ZK_ON_DEVICE(device);
   zk_synth* s = new (std::nothrow) zk_synth();
   if (!s) return zk_fail(ZK_E_NOMEM, "out of host memory");
@@ -181,8 +175,7 @@ extern "C" int zk_synth_create(int device, int n_funcs, int64_t n_pixels, const 
   s->n_funcs = n_funcs;
   s->p_pad = (n_funcs + 3) & ~3;
   s->n_pixels = n_pixels;
-  const int rc = build(s, table_host);
-  if (rc) {
+  if ((rc = build(s, table_host))) {
     release(s);
     return rc;
   }
@@ -193,7 +186,7 @@ extern "C" int zk_synth_create(int device, int n_funcs, int64_t n_pixels, const 
 extern "C" int zk_synth_destroy(zk_synth* s) {
   if (!s) return 0;
   ZK_ON_DEVICE(s->device);
-  (void)hipStreamSynchronize(s->stream);
+  (void)hipStreamSynchronize(s->stage.stream);
   release(s);  // waits for the copy streams
   return 0;
 }
@@ -217,22 +210,21 @@ extern "C" int zk_synth_apply(zk_synth* s, const double* coeffs_host, int64_t n_
   if (rc) return rc;
   if (n_rows == 0) return 0;
   ZK_ON_DEVICE(s->device);
-  zk_ring* r = &s->ring;
+  zk_ring* r = &s->stage.ring;
+  const hipStream_t stream = s->stage.stream;
   const size_t in_unit = (size_t)s->n_funcs * sizeof(double), out_unit = (size_t)s->n_pixels * zk_elem_size(out_dtype);
   const size_t budget = s->host_chunk ? s->host_chunk : (size_t)256 << 20;
   const zk_chunks ch = zk_chunk_plan(budget, in_unit + out_unit, ZK_SYNTH_ROWS, n_rows);  // whole row tiles
   rc = zk_ring_run(
-      r, s->stream, ch.n_chunks,
+      r, stream, ch.n_chunks,
       [&](int64_t c, int slot) -> int {
         int e = zk_ring_slot(r, slot, (size_t)ch.chunk * in_unit, (size_t)ch.chunk * out_unit);
-        if (!e) e = zk_ring_up(r, s->stream, c, slot, r->d_in[slot], coeffs_host + (size_t)ch.first(c) * s->n_funcs, (size_t)ch.count(c) * in_unit);
-        return e ? e : launch(s, (const double*)r->d_in[slot], ch.count(c), out_dtype, r->d_out[slot], s->stream);
+        if (!e) e = zk_ring_up(r, stream, c, slot, r->d_in[slot], coeffs_host + (size_t)ch.first(c) * s->n_funcs, (size_t)ch.count(c) * in_unit);
+        return e ? e : launch(s, (const double*)r->d_in[slot], ch.count(c), out_dtype, r->d_out[slot], stream);
       },
       [&](int64_t c, int slot) -> int {
         return zk_ring_down(r, slot, (char*)out_host + (size_t)ch.first(c) * out_unit, (size_t)ch.count(c) * out_unit);
       });
-  // an object keeps at most ZK_SYNTH_KEEP_BYTES of slots between calls (a notebook's repeated small calls allocate nothing); the
-  // slots of a large job, up to three chunks, go back at once: callers hold one object per table, several at a time
-  if (zk_ring_bytes(r) > ZK_SYNTH_KEEP_BYTES) zk_ring_free_slots(r);
+  zk_stage_trim(&s->stage, ZK_STAGE_KEEP_ROWS);  // callers hold one object per table, several at a time
   return rc;
 }

@@ -219,13 +219,7 @@ int stats_run(const void* img, int dtype, long long n, int mode, double c, float
   int rc;
   if ((rc = d_parts.alloc(blocks * sizeof(stats_part))) || (rc = d_out.alloc(sizeof(stats_result)))) return rc;
   stats_part* parts = d_parts.as<stats_part>();
-  switch (dtype) {
-    case ZK_F32: launch_stats<float>(img, n, mode, c, parts, blocks, s); break;
-    case ZK_F64: launch_stats<double>(img, n, mode, c, parts, blocks, s); break;
-    case ZK_U8: launch_stats<uint8_t>(img, n, mode, c, parts, blocks, s); break;
-    case ZK_U16: launch_stats<uint16_t>(img, n, mode, c, parts, blocks, s); break;
-    default: launch_stats<int16_t>(img, n, mode, c, parts, blocks, s); break;
-  }
+  zk_with_elem(dtype, [&](auto e) { launch_stats<typename decltype(e)::type>(img, n, mode, c, parts, blocks, s); });
   ZK_HIP(hipGetLastError());
   hipLaunchKernelGGL(stats_final_kernel, dim3(1), dim3(256), 0, s, parts, (int)blocks, d_out.as<stats_result>());
   ZK_HIP(hipGetLastError());
@@ -369,13 +363,7 @@ int order_stats_run(const void* img, int dtype, long long n, int mode, float c, 
   hipLaunchKernelGGL(select_init_kernel, dim3(1), dim3(256), 0, s, st, d_ranks, n_ranks);
   ZK_HIP(hipGetLastError());
   for (int pass = 0; pass < 4; ++pass) {
-    switch (dtype) {
-      case ZK_F32: launch_count<float>(img, n, mode, c, pass, st, blocks, s); break;
-      case ZK_F64: launch_count<double>(img, n, mode, c, pass, st, blocks, s); break;
-      case ZK_U8: launch_count<uint8_t>(img, n, mode, c, pass, st, blocks, s); break;
-      case ZK_U16: launch_count<uint16_t>(img, n, mode, c, pass, st, blocks, s); break;
-      default: launch_count<int16_t>(img, n, mode, c, pass, st, blocks, s); break;
-    }
+    zk_with_elem(dtype, [&](auto e) { launch_count<typename decltype(e)::type>(img, n, mode, c, pass, st, blocks, s); });
     ZK_HIP(hipGetLastError());
     hipLaunchKernelGGL(select_step_kernel, dim3(1), dim3(256), 0, s, st, pass, d_values);
     ZK_HIP(hipGetLastError());
@@ -453,13 +441,7 @@ int map_run(const void* img, int dtype, long long n, int op, const double* param
   p.d = (float)params[3];
   p.mean = params[0];
   p.std = params[1];
-  switch (dtype) {
-    case ZK_F32: launch_map<float>(img, out, n, op, p, keep, s); break;
-    case ZK_F64: launch_map<double>(img, out, n, op, p, keep, s); break;
-    case ZK_U8: launch_map<uint8_t>(img, out, n, op, p, keep, s); break;
-    case ZK_U16: launch_map<uint16_t>(img, out, n, op, p, keep, s); break;
-    default: launch_map<int16_t>(img, out, n, op, p, keep, s); break;
-  }
+  zk_with_elem(dtype, [&](auto e) { launch_map<typename decltype(e)::type>(img, out, n, op, p, keep, s); });
   ZK_HIP(hipGetLastError());
   return 0;
 }
@@ -469,7 +451,7 @@ int map_run(const void* img, int dtype, long long n, int op, const double* param
 // ---------------------------------------------------------------------------------------------------------------------
 
 int check_image(const void* img, int dtype, int64_t n) {
-  if (dtype < ZK_F32 || dtype > ZK_I16) return zk_fail(ZK_E_BADARG, "dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
+  if (!zk_is_elem(dtype)) return zk_fail(ZK_E_BADARG, "dtype must be one of ZK_F32, ZK_F64, ZK_U8, ZK_U16, ZK_I16");
   if (n < 1 || n >= ((int64_t)1 << 31)) return zk_fail(ZK_E_BADARG, "bad element count (needs 1 <= n < 2^31)");
   if (!img) return zk_fail(ZK_E_BADARG, "null pointer");
   return 0;

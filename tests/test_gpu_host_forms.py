@@ -10,6 +10,8 @@ called with every output present.
     zk_tmd_render            frames without masks, and masks without frames (no blur), against ``tmd_frames_device``
     zk_eels_pls              without iterations (and without signal), against the full host call and ``baseline_device``
     zk_com_refine            without thresholds and iterations, against ``com_refine_points`` and ``com_refine_device``
+
+And the five per-device byte knobs of these entry points, at what they refuse: negative bytes, and a device outside the table.
 """
 from ctypes import POINTER, c_double, c_int64, c_void_p
 
@@ -89,3 +91,23 @@ def test_com_refine_without_thresholds_and_iterations():
     dev = resident.com_refine_device(_native.DeviceArray.from_numpy(img, _native.default_device()),
                                      _native.DeviceArray.from_numpy(pts, _native.default_device()), size)
     np.testing.assert_array_equal(dev.numpy(), want)
+
+
+# setter -> its text for negative bytes
+BYTE_KNOBS = {
+    "zk_eels_set_chunk": "bad arguments",
+    "zk_scan_resample_set_chunk": "bad arguments",
+    "zk_gpa_set_run_bytes": "gpa_set_run_bytes: bytes must be >= 0 (0: the default)",
+    "zk_align_set_host_chunk": "bad arguments",
+    "zk_align_set_band_bytes": "bad arguments",
+}
+
+
+@pytest.mark.parametrize("name", list(BYTE_KNOBS))
+def test_byte_knobs_refuse_negative_bytes_and_devices_outside_the_table(name):
+    setter = getattr(_native.load(), name)
+    for device, nbytes, text in [(0, -1, BYTE_KNOBS[name]), (64, 0, "device index out of range"), (-1, 0, "device index out of range")]:
+        with pytest.raises(RuntimeError) as info:
+            _native.check(setter(device, nbytes), name)
+        assert str(info.value) == f"{name} failed with code {_native.ZK_E_BADARG}: {text}", (device, nbytes)
+    _native.check(setter(0, 0), name)                                           # the default, on a device that is there
